@@ -24,6 +24,12 @@ the launch stream); `corr_volume` = the dense materialised volume kernel that BA
 >= 50 % HBM-roofline target refer to, timed right after the steps; `mfma_util` / `traffic` come from the committed rocprofv3 PMC
 passes of the same kernels at the same shapes (profiles/r04_pmc.json, else the newest earlier one: counters cannot be read from inside this process);
 `cpu_baseline` = the oracle (CPU restatement of the reference) timed on this box's host cores.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the figures read from the timed
+steps' own HIP events).  Everything that takes runs of its own -- the repeat blocks and one-step latency, the pair kernel alone,
+`clips_mode`, `value_f16x3` / `value_unrefined`, `corr_volume`, `cpu_baseline` -- runs with `--full` only.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0): DIR/traj.npy (T, P, 2) and, for a video, DIR/order.npy (P,),
+float64.  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -270,6 +276,16 @@ class KernelProbe:
         return (sum(a.elapsed_time(b) for a, b in ev) / len(ev), len(ev)) if ev else (None, 0)
 
 
+def dump_outputs(out_dir: str, **arrays):
+    """`--dump-outputs`: every array given as out_dir/<name>.npy in float64 (None = not produced by this mode).  The timed path
+    returns trajectories of a few points (T x P x 2): far below the 64 MB a dump may take, so nothing is sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float64).numpy())
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -281,15 +297,20 @@ def parse_args():
                          "all_gather in the data path); clips = an independent T-frame clip per rank per step (no collective)")
     ap.add_argument("--halo", default="exchange", choices=["exchange", "recompute", "auto"],
                     help="auto: exchange or recompute from the schedule's byte and pair counts and a 16 MB link ping at start-up (fgvc_amd.dist.choose_halo)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-corr-volume", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything the headline figure does not need: the repeat blocks and one-step latency, "
+                         "the pair kernel alone, the clips-mode and precision lines, the dense corr-volume section, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-corr-volume", action="store_true", help="with --full: skip the dense corr-volume section")
     ap.add_argument("--no-autotune", action="store_true", help="MIOpen immediate mode (clean profiles)")
     ap.add_argument("--pair-precision", default="auto", choices=["auto", "f32", "split"],
                     help="pair top-k kernel: split = the 16-bit matrix pipe (default where it applies), f32 = fgvc_pair_topk_f32")
     ap.add_argument("--pair-fmt", default="auto", choices=["auto", "f16", "f16f6"],
                     help="arithmetic of the split pair kernel: f16 = fgvc_pair_topk_f16x3 (three f16 products, 1e-7-grade), f16f6 = "
                          "fgvc_pair_topk_f16f6 (f16 + FP6 cross terms, ~6e-5 logit); auto = f16f6 with an f16f8 encoder, f16 otherwise")
-    ap.add_argument("--no-f16x3-line", action="store_true", help="skip the extra steps in the highest-precision arithmetic (`value_f16x3`)")
+    ap.add_argument("--no-f16x3-line", action="store_true", help="with --full: skip the extra steps in the highest-precision arithmetic (`value_f16x3`)")
     ap.add_argument("--encoder-lanes", type=int, default=None,
                     help="batch slices of the encoder run on this many HIP streams at once (default: ResNet.split_lanes)")
     ap.add_argument("--sync-tail", action="store_true",
@@ -316,8 +337,8 @@ def parse_args():
     ap.add_argument("--res-split", action="store_true", help="layer-1 identities from the split form instead of dense f32 copies (A/B)")
     ap.add_argument("--enc-arith", default=None, choices=["f16f8", "f16f6", "bf16x3", "f16x3"],
                     help="arithmetic of the encoder's wide convolutions (default: ResNet.arith = f16f6; f16f8 = round 3's, bf16x3 = round 2's)")
-    ap.add_argument("--no-clips-line", action="store_true", help="skip the extra `--mode clips` measurement that a `video` run appends")
-    ap.add_argument("--repeats", type=int, default=5, help="extra blocks of 20 steps after the timed region, for the spread")
+    ap.add_argument("--no-clips-line", action="store_true", help="with --full: skip the extra `--mode clips` measurement that a `video` run appends")
+    ap.add_argument("--repeats", type=int, default=5, help="with --full: extra blocks of 20 steps after the timed region, for the spread")
     ap.add_argument("--set-option", action="append", default=[], metavar="NAME=VALUE",
                     help="fgvc_set_option knobs for A/B runs, e.g. --set-option conv_narrow=1")
     ap.add_argument("--comm-timeout", type=float, default=180.0, help="seconds before a collective that does not complete aborts the job (rc != 0)")
@@ -420,13 +441,14 @@ def setup_workload(L):
 
 
 def timed_steps(L):
-    """warm-up, EXACTLY a.steps timed steps between barrier + synchronise (max over ranks), failure flags, the repeat blocks.  `L`: the run's namespace (main() threads one dict through the phases)."""
+    """warm-up, EXACTLY a.steps timed steps between barrier + synchronise (max over ranks), failure flags, `--dump-outputs`, the repeat blocks (--full).  `L`: the run's namespace (main() threads one dict through the phases)."""
     T, _, a, backend, cfg, dev, engine, fdist, h, model, ops, plan1 = L.get("T"), L.get("_"), L.get("a"), L.get("backend"), L.get("cfg"), L.get("dev"), L.get("engine"), L.get("fdist"), L.get("h"), L.get("model"), L.get("ops"), L.get("plan1")
     probe, pts, qp, rgbs, sched_cache, state, tail_stream, timing, w, world = L.get("probe"), L.get("pts"), L.get("qp"), L.get("rgbs"), L.get("sched_cache"), L.get("state"), L.get("tail_stream"), L.get("timing"), L.get("w"), L.get("world")
+    rank = L.get("rank")
     def step(timed: bool):
         if a.mode == "video":
-            traj, _ = fdist.track_points_sharded(backend, rgbs, qp, cfg, device=dev, halo=a.halo, timing=timing if timed else None,
-                                                  cache=sched_cache, check=False)      # (the failure flags are read once after the timed loop)
+            traj, state["order"] = fdist.track_points_sharded(backend, rgbs, qp, cfg, device=dev, halo=a.halo, timing=timing if timed else None,
+                                                               cache=sched_cache, check=False)      # (the failure flags are read once after the timed loop)
             return traj
         feats, Hf, Wf = model.get_feats_hwc(rgbs, split=True)          # encoder + normalise (+ split), all T frames
         state["geom"] = (Hf, Wf, feats)
@@ -465,10 +487,12 @@ def timed_steps(L):
     if model.backbone.check_overflow():
         raise SystemExit("bench.py: an encoder activation left the f16 range of its calibrated scale: results invalid")
     n_frames_total = T * a.steps if a.mode == "video" else world * T * a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, traj=out_coords, order=state.get("order") if a.mode == "video" else None)
 
     # spread: a few more short blocks (not part of `value`)
     rep = []
-    for _ in range(max(0, a.repeats)):
+    for _ in range(max(0, a.repeats) if a.full else 0):
         barrier()
         t1 = time.perf_counter()
         for _ in range(20):
@@ -478,7 +502,7 @@ def timed_steps(L):
     # one step at a time (synchronised on both sides): what a caller with ONE clip waits for -- the timed region above overlaps each
     # step's side-stream work (pair top-k, merge, sweep with --tail-from pairs) with the next step's encoder
     lat = []
-    for _ in range(10 if a.repeats > 0 else 0):
+    for _ in range(10 if a.full and a.repeats > 0 else 0):
         barrier()
         t1 = time.perf_counter()
         step(False)
@@ -556,8 +580,14 @@ def roofline_objects(L):
             "ms_per_launch": pair_ms, "pairs_per_launch": pair_tag[1], "launches_timed": n_l,
             "mfma_util": pm.get("mfma_util"), "traffic": pm.get("hbm_bytes_per_launch")}
         # In the step the launch runs on the side stream BESIDE the next step's encoder (--tail-from pairs): its in-step duration is
-        # stretched by what it shares the CUs with.  The kernel's own figure: the same launch alone on an idle chip, timed right here.
-        if split and a.mode == "video" and world == 1 and pair_tag[1] == n_pairs_clip and not a.sync_tail and a.tail_from == "pairs":
+        # stretched by what it shares the CUs with.  The kernel's own figure: the same launch alone on an idle chip, timed right here (--full).
+        alone_applies = split and a.mode == "video" and world == 1 and pair_tag[1] == n_pairs_clip and not a.sync_tail and a.tail_from == "pairs"
+        if alone_applies and not a.full:      # every key means what it does in a --full run: the alone figures are not measured here
+            kernels["pair_topk"].update(ms_per_launch_in_step=pair_ms, ms_per_launch=None, achieved=None, frac=None, executed_tflops=None,
+                                        frac_executed=None, frac_of_f32_mfma_peak=None,
+                                        launch_note="ms_per_launch and the fractions (the launch ALONE on an idle chip): --full only; "
+                                                    "ms_per_launch_in_step: HIP events in the timed region, where it runs beside the next step's encoder")
+        if alone_applies and a.full:
             import torch
             model, rgbs, engine = L.get("model"), L.get("rgbs"), L.get("engine")
             torch.cuda.synchronize()
@@ -933,11 +963,12 @@ def main():
     timed_steps(L)
     roofline_objects(L)
     assemble_record(L)
-    clips_line(L)
-    precision_lines(L)
-    corr_volume_section(L)
+    if a.full:                                                       # what the headline figure does not need: runs of their own
+        clips_line(L)
+        precision_lines(L)
+        corr_volume_section(L)
     a, halo_why, out, rank, wl, world = L.get("a"), L.get("halo_why"), L.get("out"), L.get("rank"), L.get("wl"), L.get("world")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:          # reported at N = 1 only (the other ranks would sit at the barrier)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:          # reported at N = 1 only (the other ranks would sit at the barrier)
         out["cpu_baseline"] = cpu_baseline(wl)
     if halo_why is not None:
         out["halo_auto"] = {"mode": halo_why["mode"], "link_gbps": halo_why["link_gbps"],

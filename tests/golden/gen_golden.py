@@ -342,6 +342,20 @@ def gen_tv_keymap():
     print(f"  tv_keymap.json  {sum(v is not None for v in keymap.values())} of {len(keymap)} own tensors filled from the checkpoint")
 
 
+def gen_eval_config():
+    """tests/golden/eval_config_res18_d1.json: the values of the reference's shipped eval config (configs/eval/res18_d1_eval.py) --
+    the model, the DAVIS test settings and the names the f-strings build.  The file is executed as plain Python (its own keys need
+    nothing from its _base_), NOT through fgvc_amd's Config: the fixture is independent of the parser the test checks."""
+    with open(os.path.join(ref_import.REF_ROOT, "configs/eval/res18_d1_eval.py")) as f:
+        cfg = {}
+        exec(compile(f.read(), f.name, "exec"), {}, cfg)
+    plain = lambda v: {k: plain(x) for k, x in v.items()} if isinstance(v, dict) else [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
+    rec = {k: plain(cfg[k]) for k in ("model", "test_cfg_davis", "exp_name", "work_dir")}
+    with open(os.path.join(HERE, "eval_config_res18_d1.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+    print(f"  eval_config_res18_d1.json  {', '.join(rec)}")
+
+
 def gen_dense_api():
     """tests/golden/dense_api_10x12.npz: the three dense / window operators of the A5'' row that have no shipped caller --
     `propagate` (affinity_utils.py:33-50, with and without topk), `non_local_attention` (correlation.py:32-83: att_only, per_ref,
@@ -684,6 +698,7 @@ if __name__ == "__main__":
         gen_hr_tracker()
         gen_extra_modes()
         gen_tv_keymap()
+        gen_eval_config()
         gen_tracker_cfg0()
         gen_dense_api()
         gen_tracker_8f()

@@ -97,13 +97,20 @@ def test_registry_builder_config(tmp_path):
     assert cfg.get("eval_arc", "VanillaTracker") == "VanillaTracker"
 
 
-def test_reference_eval_config_loads():
-    """the shipped eval config of the reference parses with our Config (only if the tree is present)."""
-    path = "/root/reference/configs/eval/res18_d1_eval.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+def test_reference_eval_config_loads(tmp_path):
+    """the shipped eval config of the reference (its values, recorded by gen_golden.py from the file executed as plain Python:
+    tests/golden/eval_config_res18_d1.json) parses with our Config when written out in the same shape -- the model in a `_base_`
+    file, an f-string work_dir -- to the same values, and builds the tracker it names."""
+    import json
     import fgvc_amd.mmpt_api as api
-    cfg = api.Config.fromfile(path)
+    with open(os.path.join(ROOT, "tests", "golden", "eval_config_res18_d1.json")) as f:
+        rec = json.load(f)
+    tup = lambda v: {k: tup(x) for k, x in v.items()} if isinstance(v, dict) else tuple(tup(x) for x in v) if isinstance(v, list) else v
+    (tmp_path / "base.py").write_text(f"model = {tup(rec['model'])!r}\n")
+    (tmp_path / "res18_d1_eval.py").write_text(f"_base_ = './base.py'\nexp_name = {rec['exp_name']!r}\n"
+                                               f"test_cfg_davis = {tup(rec['test_cfg_davis'])!r}\nwork_dir = f'./eval/{{exp_name}}'\n")
+    cfg = api.Config.fromfile(str(tmp_path / "res18_d1_eval.py"))
+    assert cfg.work_dir == rec["work_dir"] and tup(cfg.model) == tup(rec["model"])
     assert cfg.model.type == "VanillaTracker" and cfg.test_cfg_davis.neighbor_range == 30
     tc = cfg["test_cfg_davis"]
     model = api.build_model(dict(type=cfg.get("eval_arc", "VanillaTracker"),
@@ -364,6 +371,28 @@ def test_bench_encoder_flops_matches_hand_count():
     want += 2.0 * h2 * w2 * 128 * 256 * 9 + 3 * 2.0 * h2 * w2 * 256 * 256 * 9 + 2.0 * h2 * w2 * 128 * 256    # stage 3 (+ 1x1 projection)
     got = bench.encoder_flops(bench.WORKLOADS["cfg2_480p_8f"], 8)
     assert abs(got - 8 * want) < 1e-6 * got
+
+
+def test_bench_plain_run_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: `--full` is off by default, `--steps` / `--dump-outputs` are taken as given, and the dump writes every array it
+    is handed as <name>.npy in float64 (and skips the ones a mode does not produce)."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "3", "--full", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == str(tmp_path / "d") and a.steps == 3
+    traj = torch.arange(8 * 3 * 2, dtype=torch.float64).reshape(8, 3, 2) / 7
+    bench.dump_outputs(a.dump_outputs, traj=traj, order=torch.tensor([2, 0, 1]), labels=None)
+    assert sorted(os.listdir(a.dump_outputs)) == ["order.npy", "traj.npy"]
+    t = np.load(os.path.join(a.dump_outputs, "traj.npy"))
+    o = np.load(os.path.join(a.dump_outputs, "order.npy"))
+    assert t.dtype == o.dtype == np.float64 and (t == traj.numpy()).all() and o.tolist() == [2.0, 0.0, 1.0]
 
 
 def test_f16_scale_exponents_of_degenerate_tensors():

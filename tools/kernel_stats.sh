@@ -8,7 +8,7 @@ ROOT=$(pwd)
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 rm -rf "$OUT/raw"
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/raw" -- python3 "$ROOT/bench.py" --steps 40 --repeats 1 --no-cpu-baseline --no-f16x3-line --no-clips-line) > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/raw" -- python3 "$ROOT/bench.py" --full --steps 40 --repeats 1 --no-cpu-baseline --no-f16x3-line --no-clips-line) > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.err"
 f=$(find "$OUT/raw" -name "*kernel_stats.csv" | head -1)
 cp "$f" "$OUT/$NAME"
 # ... and per (symbol, grid): one template instance serves launches of different sizes (conv256p_kernel<256, 3, false, false, ...> is the
