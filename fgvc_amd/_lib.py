@@ -89,6 +89,11 @@ SIGNATURES = {
     "fgvc_gaussian_labels_f32": (_i, [_p, _i, _i, _i, _i, _f, _p, _p]),
     "fgvc_softargmax_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fgvc_softargmax_top5_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _f, _p, _p, _p]),
+    "fgvc_seg_max_label_u8": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_onehot_labels_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_hard_onehot_f32": (_i, [_p, _i, _i, _p, _p]),
+    "fgvc_seg_readout_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fgvc_seg_readout_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

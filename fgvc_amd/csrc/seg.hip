@@ -1,0 +1,357 @@
+// Segmentation-mask ends of the label-propagation path (semi-supervised VOS, vanilla_tracker.py:663-830): first-frame index map ->
+// one-hot labels on the feature grid, hard propagation (argmax -> one-hot of a bank row), and the read-out of C-channel logits to a
+// full-resolution index mask.  The middle of the path (pair top-k, merge, fgvc_propagate_topk_f32) is the points path's, with P = C.
+#include "common.hpp"
+
+namespace fgvc {
+
+namespace {
+
+// Pillow's NEAREST resize (ImagingScaleAffine, Geometry.c): the source coordinate of output o is a running double sum
+// a/2 + a + ... + a with a = in/out, truncated.  The running sum is not floor((o + 0.5) * in / out): at sizes such as 100 -> 27 the
+// two differ where the exact value is an integer.  Sequential by construction, so one lane builds each table.
+__device__ void pil_nearest_table(int n_in, int n_out, int* __restrict__ tab) {
+  const double a = (double)n_in / (double)n_out;
+  double xo = a * 0.5;
+  for (int o = 0; o < n_out; ++o) {
+    const int xi = (int)xo;
+    tab[o] = xi < n_in - 1 ? xi : n_in - 1;
+    xo += a;
+  }
+}
+
+// PyTorch area_pixel_compute_source_index (align_corners=False) in f32, as the points read-out evaluates it (post.hip src_index)
+__device__ __forceinline__ void seg_src_index(int d, float scale, int in_size, int& i0, int& i1, float& l1) {
+  float s = scale * ((float)d + 0.5f) - 0.5f;
+  s = s < 0.f ? 0.f : s;
+  i0 = imin((int)s, in_size - 1);
+  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  l1 = s - (float)i0;
+}
+
+// Taps of one output coordinate through bilinear(in -> padded size), crop at `off`, bilinear(unpadded -> out): feature-grid
+// indices t[0..3] and weights w[0..3].  COMPOSED = false: the second resize is the identity (out size == unpadded size), t[2..3]
+// and w[2..3] are unused.
+template <bool COMPOSED>
+struct Taps {
+  int t[4];
+  float w[4];
+  __device__ __forceinline__ void make(int o, float s2, int n_unpad, int off, float s1, int n_feat) {
+    int a0, a1, f0, f1;
+    float la, lf;
+    if constexpr (COMPOSED) {
+      seg_src_index(o, s2, n_unpad, a0, a1, la);
+      seg_src_index(a0 + off, s1, n_feat, f0, f1, lf);
+      t[0] = f0; t[1] = f1; w[0] = (1.f - la) * (1.f - lf); w[1] = (1.f - la) * lf;
+      seg_src_index(a1 + off, s1, n_feat, f0, f1, lf);
+      t[2] = f0; t[3] = f1; w[2] = la * (1.f - lf); w[3] = la * lf;
+    } else {
+      seg_src_index(o + off, s1, n_feat, f0, f1, lf);
+      t[0] = f0; t[1] = f1; w[0] = 1.f - lf; w[1] = lf;
+    }
+  }
+};
+
+// one pixel of the composed field in channel c: rows y.t (offsets already multiplied by Wf * C), columns x.t (by C)
+template <bool COMPOSED>
+__device__ __forceinline__ float field_value(const float* __restrict__ lab, const Taps<COMPOSED>& y, const Taps<COMPOSED>& x) {
+  constexpr int N = COMPOSED ? 4 : 2;
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    float row = 0.f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) row = fmaf(x.w[j], lab[y.t[i] + x.t[j]], row);
+    acc = fmaf(y.w[i], row, acc);
+  }
+  return acc;
+}
+
+constexpr int SEG_BLOCK = 256;
+constexpr int SEG_PX = 4;                       // output pixels per lane (one 4-byte store)
+constexpr int SEG_CHUNK = SEG_BLOCK * SEG_PX;   // pixels per workgroup iteration
+constexpr int SEG_NB = 32;                      // phase-1 workgroups per frame (= rows of the partials slab)
+// the label kernels' dynamic LDS holds the Hf + Wf source tables (4 B each) beside seg_max_label_kernel's 16 B of static LDS: within 64 KiB
+constexpr int SEG_MAX_TABLE = (65536 - 16) / 4;
+
+struct ReadoutGeom {
+  int Hf, Wf, C, h, w, h0, w0, top, left;
+  float s1y, s1x, s2y, s2x;  // feature / padded and unpadded / output scales
+};
+
+// the taps of one lane's SEG_PX pixels starting at p (pixels past HW get clamped coordinates: their values are never used)
+template <bool COMPOSED>
+__device__ __forceinline__ void lane_taps(const ReadoutGeom& g, int p, int HW, Taps<COMPOSED> (&ty)[SEG_PX],
+                                          Taps<COMPOSED> (&tx)[SEG_PX]) {
+#pragma unroll
+  for (int k = 0; k < SEG_PX; ++k) {
+    const int q = imin(p + k, HW - 1);
+    const int oy = q / g.w0, ox = q - oy * g.w0;
+    ty[k].make(oy, g.s2y, g.h, g.top, g.s1y, g.Hf);
+    tx[k].make(ox, g.s2x, g.w, g.left, g.s1x, g.Wf);
+#pragma unroll
+    for (int i = 0; i < (COMPOSED ? 4 : 2); ++i) {   // Taps<false>::make fills t[0..1] only
+      ty[k].t[i] *= g.Wf * g.C;
+      tx[k].t[i] *= g.C;
+    }
+  }
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------
+// frame-0 labels: Pillow-nearest sample of the padded index map to (Hf, Wf), then one-hot with C channels
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void seg_max_label_kernel(const uint8_t* __restrict__ map, int hp, int wp, int Hf, int Wf,
+                                                            int32_t* __restrict__ out) {
+  extern __shared__ int tab[];  // [Hf] rows | [Wf] columns
+  __shared__ int wmax[4];
+  int* ry = tab;
+  int* rx = tab + Hf;
+  if (threadIdx.x == 0) pil_nearest_table(hp, Hf, ry);
+  if (threadIdx.x == 64) pil_nearest_table(wp, Wf, rx);
+  __syncthreads();
+  int m = 0;
+  for (int i = threadIdx.x; i < Hf * Wf; i += 256) {
+    const int y = i / Wf, x = i - y * Wf;
+    m = max(m, (int)map[(size_t)ry[y] * wp + rx[x]]);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+}
+
+__global__ __launch_bounds__(256) void seg_onehot_kernel(const uint8_t* __restrict__ map, int hp, int wp, int Hf, int Wf, int C,
+                                                         float* __restrict__ out) {
+  extern __shared__ int tab[];
+  int* ry = tab;
+  int* rx = tab + Hf;
+  if (threadIdx.x == 0) pil_nearest_table(hp, Hf, ry);
+  if (threadIdx.x == 64) pil_nearest_table(wp, Wf, rx);
+  __syncthreads();
+  const long long n = (long long)Hf * Wf * C;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const int pix = (int)(i / C), c = (int)(i - (long long)pix * C);
+    const int y = pix / Wf, x = pix - y * Wf;
+    out[i] = (int)map[(size_t)ry[y] * wp + rx[x]] == c ? 1.f : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// hard propagation: row r of `in` (rows, C) -> one_hot(argmax) in `out` (may alias `in`); the first maximum wins
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void seg_hard_onehot_kernel(const float* in, int rows, int C, float* out) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  const float* src = in + (size_t)r * C;
+  float best = src[0];
+  int bi = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = src[c];
+    if (v > best) { best = v; bi = c; }
+  }
+  float* dst = out + (size_t)r * C;
+  for (int c = 0; c < C; ++c) dst[c] = c == bi ? 1.f : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------
+// read-out phase 1: per (frame, channel) min / max of the composed field over the whole output frame.
+// Grid (SEG_NB, n): each workgroup strides over the frame's pixel chunks; per channel the lanes reduce their SEG_PX values, the
+// wave reduces with shuffles and lane 0 folds it into its wave's LDS slot; the workgroup's partial goes to row blockIdx.x of the
+// slab part[n][SEG_NB][C][2] (no atomics: deterministic, and no buffer to clear first).
+// ------------------------------------------------------------------------------------------
+template <bool COMPOSED>
+__global__ __launch_bounds__(SEG_BLOCK) void seg_minmax_kernel(const float* __restrict__ labels, ReadoutGeom g,
+                                                               float* __restrict__ part) {
+  extern __shared__ float red[];  // [4 waves][C][2]
+  const int f = blockIdx.y, C = g.C, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int HW = g.h0 * g.w0;
+  const float* lab = labels + (size_t)f * g.Hf * g.Wf * C;
+  for (int i = threadIdx.x; i < 4 * C; i += SEG_BLOCK) {
+    red[2 * i] = INFINITY;
+    red[2 * i + 1] = -INFINITY;
+  }
+  __syncthreads();
+  for (int p0 = blockIdx.x * SEG_CHUNK; p0 < HW; p0 += SEG_NB * SEG_CHUNK) {
+    const int p = p0 + threadIdx.x * SEG_PX;
+    Taps<COMPOSED> ty[SEG_PX], tx[SEG_PX];
+    lane_taps<COMPOSED>(g, p, HW, ty, tx);
+    const int nvalid = imin(SEG_PX, HW - p);   // may be <= 0 for the last chunk's tail lanes
+    for (int c = 0; c < C; ++c) {
+      float mn = INFINITY, mx = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < SEG_PX; ++k) {
+        const float v = field_value<COMPOSED>(lab + c, ty[k], tx[k]);
+        if (k < nvalid) {
+          mn = fminf(mn, v);
+          mx = fmaxf(mx, v);
+        }
+      }
+      mn = wave_min(mn);
+      mx = wave_max(mx);
+      if (lane == 0) {
+        float* s = red + 2 * (wave * C + c);
+        s[0] = fminf(s[0], mn);
+        s[1] = fmaxf(s[1], mx);
+      }
+    }
+  }
+  __syncthreads();
+  float* dst = part + ((size_t)f * SEG_NB + blockIdx.x) * C * 2;
+  for (int c = threadIdx.x; c < C; c += SEG_BLOCK) {
+    float mn = red[2 * c], mx = red[2 * c + 1];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      mn = fminf(mn, red[2 * (w * C + c)]);
+      mx = fmaxf(mx, red[2 * (w * C + c) + 1]);
+    }
+    dst[2 * c] = mn;
+    dst[2 * c + 1] = mx;
+  }
+}
+
+// read-out phase 2: fold the slab into per-channel (min, max) in LDS, then per pixel normalise, argmax (first maximum wins) and
+// store SEG_PX index bytes per lane in one 4-byte store where the destination is aligned.
+template <bool COMPOSED>
+__global__ __launch_bounds__(SEG_BLOCK) void seg_argmax_kernel(const float* __restrict__ labels, ReadoutGeom g,
+                                                               const float* __restrict__ part, int norm,
+                                                               uint8_t* __restrict__ masks) {
+  extern __shared__ float mm[];  // [C][2]: min, max
+  const int f = blockIdx.y, C = g.C;
+  const int HW = g.h0 * g.w0;
+  const float* lab = labels + (size_t)f * g.Hf * g.Wf * C;
+  const float* src = part + (size_t)f * SEG_NB * C * 2;
+  for (int c = threadIdx.x; c < C; c += SEG_BLOCK) {
+    float mn = INFINITY, mx = -INFINITY;
+    for (int b = 0; b < SEG_NB; ++b) {
+      mn = fminf(mn, src[(b * C + c) * 2]);
+      mx = fmaxf(mx, src[(b * C + c) * 2 + 1]);
+    }
+    mm[2 * c] = mn;
+    mm[2 * c + 1] = mx;
+  }
+  __syncthreads();
+  const int p = blockIdx.x * SEG_CHUNK + threadIdx.x * SEG_PX;
+  if (p >= HW) return;
+  Taps<COMPOSED> ty[SEG_PX], tx[SEG_PX];
+  lane_taps<COMPOSED>(g, p, HW, ty, tx);
+  float best[SEG_PX];
+  int bi[SEG_PX];
+#pragma unroll
+  for (int k = 0; k < SEG_PX; ++k) {
+    best[k] = -INFINITY;
+    bi[k] = 0;
+  }
+  for (int c = 0; c < C; ++c) {
+    const float mn = mm[2 * c], mx = mm[2 * c + 1];
+    // torch.where(max > 0, (x - min) / (max - min + 1e-12), x)
+    const bool nrm = norm && mx > 0.f;
+    const float den = (mx - mn) + 1e-12f;
+#pragma unroll
+    for (int k = 0; k < SEG_PX; ++k) {
+      float v = field_value<COMPOSED>(lab + c, ty[k], tx[k]);
+      if (nrm) v = (v - mn) / den;
+      if (c == 0 || v > best[k]) {
+        best[k] = v;
+        bi[k] = c;
+      }
+    }
+  }
+  uint8_t* dst = masks + (size_t)f * HW + p;
+  if (p + SEG_PX <= HW && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
+    const uint32_t word = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
+    *reinterpret_cast<uint32_t*>(dst) = word;
+  } else {
+#pragma unroll
+    for (int k = 0; k < SEG_PX; ++k)
+      if (p + k < HW) dst[k] = (uint8_t)bi[k];
+  }
+}
+
+size_t seg_readout_workspace_bytes(int n, int C) { return (size_t)n * SEG_NB * C * 2 * sizeof(float); }
+
+}  // namespace fgvc
+
+using namespace fgvc;
+
+extern "C" {
+
+int fgvc_seg_max_label_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int32_t* out, void* stream) {
+  FGVC_REQUIRE(map && out, FGVC_ERR_INVALID_ARG, "fgvc_seg_max_label_u8: null pointer");
+  FGVC_REQUIRE(hp > 0 && wp > 0 && Hf > 0 && Wf > 0, FGVC_ERR_INVALID_ARG, "fgvc_seg_max_label_u8: bad shape");
+  FGVC_REQUIRE(Hf + Wf <= SEG_MAX_TABLE, FGVC_ERR_UNSUPPORTED, "fgvc_seg_max_label_u8: Hf + Wf > %d", SEG_MAX_TABLE);
+  seg_max_label_kernel<<<1, 256, (Hf + Wf) * sizeof(int), (hipStream_t)stream>>>(map, hp, wp, Hf, Wf, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_max_label_u8");
+  return FGVC_OK;
+}
+
+int fgvc_seg_onehot_labels_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int C, float* out, void* stream) {
+  FGVC_REQUIRE(map && out, FGVC_ERR_INVALID_ARG, "fgvc_seg_onehot_labels_u8: null pointer");
+  FGVC_REQUIRE(hp > 0 && wp > 0 && Hf > 0 && Wf > 0 && C >= 1 && C <= 256, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_onehot_labels_u8: bad shape (1 <= C <= 256)");
+  FGVC_REQUIRE(Hf + Wf <= SEG_MAX_TABLE, FGVC_ERR_UNSUPPORTED, "fgvc_seg_onehot_labels_u8: Hf + Wf > %d", SEG_MAX_TABLE);
+  const long long n = (long long)Hf * Wf * C;
+  const int blocks = (int)(n < 256ll * 1024 ? (n + 255) / 256 : 1024);
+  seg_onehot_kernel<<<blocks, 256, (Hf + Wf) * sizeof(int), (hipStream_t)stream>>>(map, hp, wp, Hf, Wf, C, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_onehot_labels_u8");
+  return FGVC_OK;
+}
+
+int fgvc_seg_hard_onehot_f32(const float* in, int rows, int C, float* out, void* stream) {
+  FGVC_REQUIRE(in && out, FGVC_ERR_INVALID_ARG, "fgvc_seg_hard_onehot_f32: null pointer");
+  FGVC_REQUIRE(rows > 0 && C >= 1, FGVC_ERR_INVALID_ARG, "fgvc_seg_hard_onehot_f32: bad shape");
+  seg_hard_onehot_kernel<<<cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(in, rows, C, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_hard_onehot_f32");
+  return FGVC_OK;
+}
+
+size_t fgvc_seg_readout_workspace_bytes(int n, int C) {
+  if (n < 0 || C < 1) return 0;
+  return seg_readout_workspace_bytes(n, C);
+}
+
+int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
+                        int w0, int norm, uint8_t* masks, void* workspace, void* stream) {
+  FGVC_REQUIRE(labels && masks, FGVC_ERR_INVALID_ARG, "fgvc_seg_readout_u8: null pointer");
+  FGVC_REQUIRE(n >= 0 && n <= 65535 && Hf > 0 && Wf > 0 && C >= 1 && C <= 256 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_u8: bad shape (1 <= C <= 256, n <= 65535)");
+  FGVC_REQUIRE(h > 0 && w > 0 && top >= 0 && left >= 0 && top + h <= hp && left + w <= wp, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_u8: the unpadded window must lie inside the padded frame");
+  FGVC_REQUIRE((long long)h0 * w0 < (1ll << 31) - SEG_CHUNK, FGVC_ERR_UNSUPPORTED, "fgvc_seg_readout_u8: h0*w0 out of range");
+  FGVC_REQUIRE(workspace != nullptr || n == 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_u8: workspace of fgvc_seg_readout_workspace_bytes() bytes required");
+  if (n == 0) return FGVC_OK;
+  ReadoutGeom g;
+  g.Hf = Hf; g.Wf = Wf; g.C = C; g.h = h; g.w = w; g.h0 = h0; g.w0 = w0; g.top = top; g.left = left;
+  g.s1y = (float)Hf / (float)hp; g.s1x = (float)Wf / (float)wp;
+  g.s2y = (float)h / (float)h0; g.s2x = (float)w / (float)w0;
+  const bool composed = !(h == h0 && w == w0);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  const int HW = h0 * w0;
+  const dim3 g1(SEG_NB, n), g2(cdiv(HW, SEG_CHUNK), n);
+  if (composed) {
+    seg_minmax_kernel<true><<<g1, SEG_BLOCK, 8 * C * sizeof(float), s>>>(labels, g, part);
+    seg_argmax_kernel<true><<<g2, SEG_BLOCK, 2 * C * sizeof(float), s>>>(labels, g, part, norm, masks);
+  } else {
+    seg_minmax_kernel<false><<<g1, SEG_BLOCK, 8 * C * sizeof(float), s>>>(labels, g, part);
+    seg_argmax_kernel<false><<<g2, SEG_BLOCK, 2 * C * sizeof(float), s>>>(labels, g, part, norm, masks);
+  }
+  FGVC_CHECK_LAUNCH("fgvc_seg_readout_u8");
+  return FGVC_OK;
+}
+
+}  // extern "C"

@@ -356,3 +356,55 @@ def badja_evaluate(model, dataset: "BadjaPoses"):
         preds.append(dataset.pose_prediction(out[2]))
         js.append(meta["joints"]); vs.append(meta["visibles"]); ss.append(meta["segs"])
     return metrics.badja_pck(preds, js, vs, ss)
+
+
+class Davis2017:
+    """DAVIS-2017 semi-supervised VOS in the sample format VanillaTracker.forward_test's mask path consumes (the reference's mask
+    pipelines yield `imgs` / `ref_seg_map` / `img_meta`, configs/eval/base_data.py:15-39).
+
+    Files: `ImageSets/2017/<split>.txt` (one sequence per line), `JPEGImages/480p/<seq>/*.jpg`, `Annotations/480p/<seq>/*.png` (palette
+    PNGs: the palette index is the object id, 0 = background).  Frames go through the RGB->Lab + Normalize contract at their native size
+    (no resize).  Item i = (data, meta): data = dict(imgs (1,1,3,T,h,w), ref_seg_map (1,h,w) uint8 = the first annotation,
+    img_meta = [dict(original_shape=(h,w))]); meta = dict(name, gt (T,h,w) uint8 -- every annotation the set has, frames without
+    one are all-zero -- n_objects)."""
+
+    def __init__(self, root: str, split: str = "val", resolution: str = "480p", device="cpu", max_frames: int = -1):
+        self.root, self.res, self.device, self.max_frames = root, resolution, device, int(max_frames)
+        with open(os.path.join(root, "ImageSets", "2017", f"{split}.txt")) as f:
+            self.sequences = [ln.strip() for ln in f if ln.strip()]
+
+    def __len__(self):
+        return len(self.sequences)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        seq = self.sequences[i]
+        jdir = os.path.join(self.root, "JPEGImages", self.res, seq)
+        adir = os.path.join(self.root, "Annotations", self.res, seq)
+        names = sorted(os.path.splitext(n)[0] for n in os.listdir(jdir) if n.endswith(".jpg"))
+        if self.max_frames > 0:
+            names = names[:self.max_frames]
+        frames = torch.from_numpy(np.stack([np.asarray(Image.open(os.path.join(jdir, n + ".jpg")).convert("RGB")) for n in names]))
+        h, w = frames.shape[1:3]
+        gt = np.zeros((len(names), h, w), np.uint8)
+        for t, n in enumerate(names):
+            p = os.path.join(adir, n + ".png")
+            if os.path.exists(p):
+                im = Image.open(p)
+                gt[t] = np.asarray(im if im.mode in ("P", "L") else im.convert("L"))
+        rgbs = preprocess_tapvid_frames(frames.to(self.device), (h, w))                    # (1,T,3,h,w), native size
+        imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()                      # (1,1,3,T,h,w)
+        ref = torch.from_numpy(gt[0].copy()).unsqueeze(0).to(self.device)
+        data = dict(imgs=imgs, ref_seg_map=ref, img_meta=[dict(original_shape=(h, w))])
+        return data, dict(name=seq, gt=gt, n_objects=int(gt[0].max()))
+
+
+def davis_evaluate(model, dataset: "Davis2017") -> dict:
+    """Run the mask path over the set and score it (metrics.davis_jf)."""
+    from . import metrics
+    seqs = {}
+    for i in range(len(dataset)):
+        data, meta = dataset[i]
+        pred = model(test_mode=True, **data)[0]
+        seqs[meta["name"]] = (meta["gt"], pred)
+    return metrics.davis_jf(seqs)

@@ -57,6 +57,8 @@ class TrackerConfig:
                                    # order wherever the approximate scores are within `pair_refine_eps` of the exact products (round 5: the
                                    # reference's own lists, profiles/r05_precision_ledger.json).  False: round 4's plain merge of approximate scores
     pair_refine_eps: float = ops.REFINE_EPS
+    hard_prop: bool = False        # mask path: a frame's bank row is one_hot(argmax) of its logits (vanilla_tracker.py:81, :763-769)
+    norm_mask: bool = True         # mask path: per-channel min-max normalisation before the argmax (vanilla_tracker.py:82, :787-797)
 
     @staticmethod
     def from_test_cfg(cfg) -> "TrackerConfig":
@@ -84,7 +86,8 @@ class TrackerConfig:
             with_first=bool(g("with_first", True)), regroup=bool(g("with_first", False)),
             with_first_neighbor=with_first_neighbor, with_norm=with_norm, sim_mode=sim_mode, test_mode=test_mode,
             pair_precision=g("pair_precision", "auto"), pair_split_fmt=g("pair_split_fmt", "f16"),   # from here on: extension keys
-            pair_refine=bool(g("pair_refine", True)), pair_refine_eps=float(g("pair_refine_eps", ops.REFINE_EPS)))
+            pair_refine=bool(g("pair_refine", True)), pair_refine_eps=float(g("pair_refine_eps", ops.REFINE_EPS)),
+            hard_prop=bool(g("hard_prop", False)), norm_mask=bool(g("norm_mask", True)))
 
     @property
     def bank_fmt(self) -> str:
@@ -392,3 +395,50 @@ def track_points(feats_hwc: torch.Tensor, Hf: int, Wf: int, h: int, w: int, quer
         order.extend(sel.tolist())
         K += sel.numel()
     return traj, torch.tensor(order, dtype=torch.int64)
+
+
+def pad_divide_by(h: int, w: int, d: int) -> Tuple[Tuple[int, int], Tuple[int, int, int, int]]:
+    """common/utils.py:397-410 on sizes: ((hp, wp), (left, right, top, bottom)) -- zeros, floor(extra / 2) before, the rest after."""
+    hp, wp = -(-h // d) * d, -(-w // d) * d
+    lh, lw = (hp - h) // 2, (wp - w) // 2
+    return (hp, wp), (lw, wp - w - lw, lh, hp - h - lh)
+
+
+def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
+                    out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
+                    stats_out: Optional[list] = None, events: Optional[dict] = None) -> torch.Tensor:
+    """Semi-supervised VOS for one clip (vanilla_tracker.py:663-830 with VanillaTracker's affinity, :366-378).
+    feats_hwc: the clip's bank as run_affinity takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame
+    index map; pad = (left, right, top, bottom) as pad_divide_by gives it; out_shape = (h0, w0).
+    Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
+    resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output).
+    `events`: torch.cuda.Events keyed 'labels', 'affinity', 'propagation', 'readout', 'end', recorded before each phase."""
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    hp, wp = seg_map.shape
+    lw, uw, lh, uh = pad
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    rec("labels")
+    C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
+    bank = torch.zeros((T, Hf * Wf, C), device=dev, dtype=torch.float32)
+    ops.seg_onehot_labels(seg_map, Hf, Wf, C, out=bank[0])
+    rec("affinity")
+    plan = plan_clip(T, [0], cfg)
+    tk = run_affinity(feats_hwc, Hf, Wf, plan, cfg, channels=channels)
+    if stats_out is not None and tk.refine_stats is not None:
+        stats_out.append(tk.refine_stats)
+    rec("propagation")
+    soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
+    for f in range(1, T):
+        row = tk.row(plan.out_rows[(0, f)])
+        ops.propagate_topk(bank, tk.slot_frame[row], tk.idx[row], tk.weight[row], Hf, Wf, Hf, Wf, out=soft[f])
+        if cfg.hard_prop:
+            ops.seg_hard_onehot(soft[f], out=bank[f])
+    rec("readout")
+    masks = torch.empty((T, *out_shape), device=dev, dtype=torch.uint8)
+    if T > 1:
+        ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[1:])
+    # frame 0: the unpadded input map, nearest-resized to the output size (:708-711)
+    ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]
+    masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
+    rec("end")
+    return masks

@@ -210,3 +210,147 @@ def badja_pck(pred_poses: Sequence[np.ndarray], joints: Sequence[Sequence[Option
     out = {f"PCK@{r}": (100.0 * float(np.mean(counts[r])) if counts[r] else float("nan")) for r in ratios}
     out["PCK@0.2 per-video mean"] = float(np.mean(per_video)) if per_video else float("nan")
     return out
+
+
+# ---- DAVIS-2017 semi-supervised J&F (mmpt/core/evaluation/metrics.py: db_eval_iou, db_eval_boundary, db_statistics, JFM) -----------
+# The reference dilates boundaries with cv2.dilate and a skimage disk; neither is installed here, so the dilation is
+# scipy.ndimage.binary_dilation with the same disk footprint (x^2 + y^2 <= r^2).  A symmetric footprint and a zero border make the two
+# the same operation.
+
+def db_eval_iou(annotation: np.ndarray, segmentation: np.ndarray, void_pixels: Optional[np.ndarray] = None):
+    """Region similarity J: intersection over union of two binary masks (..., h, w); an empty union scores 1."""
+    assert annotation.shape == segmentation.shape, (annotation.shape, segmentation.shape)
+    a, s = annotation.astype(bool), segmentation.astype(bool)
+    keep = np.ones_like(a) if void_pixels is None else ~void_pixels.astype(bool)
+    inter = np.sum(a & s & keep, axis=(-2, -1))
+    union = np.sum((a | s) & keep, axis=(-2, -1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        j = inter / union
+    if np.ndim(j) == 0:
+        return 1.0 if np.isclose(union, 0) else float(j)
+    j = np.asarray(j, dtype=np.float64)
+    j[np.isclose(union, 0)] = 1.0
+    return j
+
+
+def _seg2bmap(seg: np.ndarray) -> np.ndarray:
+    """1-pixel-wide boundary map of a binary mask: a pixel is on the boundary when it differs from its east, south or south-east
+    neighbour (the last row compares east only, the last column south only, the corner is never a boundary)."""
+    s = seg.astype(bool)
+    e, so, se = np.zeros_like(s), np.zeros_like(s), np.zeros_like(s)
+    e[:, :-1], so[:-1, :], se[:-1, :-1] = s[:, 1:], s[1:, :], s[1:, 1:]
+    b = (s ^ e) | (s ^ so) | (s ^ se)
+    b[-1, :] = s[-1, :] ^ e[-1, :]
+    b[:, -1] = s[:, -1] ^ so[:, -1]
+    b[-1, -1] = False
+    return b
+
+
+def _disk(r: int) -> np.ndarray:
+    y, x = np.mgrid[-r:r + 1, -r:r + 1]
+    return (x * x + y * y) <= r * r
+
+
+def f_measure(foreground_mask: np.ndarray, gt_mask: np.ndarray, void_pixels: Optional[np.ndarray] = None,
+              bound_th: float = 0.008) -> float:
+    """Boundary F of one frame: precision / recall of the boundary pixels within a disk of ceil(bound_th * diagonal) pixels."""
+    from scipy.ndimage import binary_dilation
+    keep = np.ones(foreground_mask.shape, bool) if void_pixels is None else ~void_pixels.astype(bool)
+    r = bound_th if bound_th >= 1 else math.ceil(bound_th * np.linalg.norm(foreground_mask.shape))
+    fg_b = _seg2bmap(foreground_mask.astype(bool) & keep)
+    gt_b = _seg2bmap(gt_mask.astype(bool) & keep)
+    fp = _disk(int(r))
+    fg_d = binary_dilation(fg_b, structure=fp) if fg_b.any() else fg_b
+    gt_d = binary_dilation(gt_b, structure=fp) if gt_b.any() else gt_b
+    n_fg, n_gt = int(fg_b.sum()), int(gt_b.sum())
+    if n_fg == 0 and n_gt == 0:
+        precision = recall = 1.0
+    elif n_fg == 0:
+        precision, recall = 1.0, 0.0
+    elif n_gt == 0:
+        precision, recall = 0.0, 1.0
+    else:
+        precision = float((fg_b & gt_d).sum()) / n_fg
+        recall = float((gt_b & fg_d).sum()) / n_gt
+    return 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
+
+
+def db_eval_boundary(annotation: np.ndarray, segmentation: np.ndarray, void_pixels: Optional[np.ndarray] = None,
+                     bound_th: float = 0.008):
+    """Boundary F of (h, w) masks (a float) or of (T, h, w) stacks (an array over T)."""
+    assert annotation.shape == segmentation.shape
+    if annotation.ndim == 2:
+        return f_measure(segmentation, annotation, void_pixels, bound_th)
+    if annotation.ndim != 3:
+        raise ValueError(f"db_eval_boundary: {annotation.ndim}-D masks")
+    return np.array([f_measure(segmentation[t], annotation[t], None if void_pixels is None else void_pixels[t], bound_th)
+                     for t in range(annotation.shape[0])])
+
+
+def db_statistics(per_frame_values: np.ndarray):
+    """(mean, recall = share of frames above 0.5, decay = mean of the first quarter - mean of the last) of per-frame values, NaNs
+    ignored.  The quarters are the reference's: bin edges round(linspace(1, n, 5)) - 1, each bin including its upper edge."""
+    v = np.asarray(per_frame_values, dtype=np.float64)
+    with np.errstate(invalid="ignore"), _quiet():
+        M = np.nanmean(v)
+        O = np.nanmean(v > 0.5)
+        ids = (np.round(np.linspace(1, len(v), 5) + 1e-10) - 1).astype(np.uint8)
+        bins = [v[ids[i]:ids[i + 1] + 1] for i in range(4)]
+        D = np.nanmean(bins[0]) - np.nanmean(bins[3])
+    return M, O, D
+
+
+class _quiet:
+    def __enter__(self):
+        import warnings
+        self._w = warnings.catch_warnings()
+        self._w.__enter__()
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+
+    def __exit__(self, *a):
+        return self._w.__exit__(*a)
+
+
+def JFM(all_gt_masks: np.ndarray, all_res_masks: np.ndarray, num_objects: Optional[int] = None) -> Dict[str, list]:
+    """Per-object J / F statistics of one sequence.  all_gt_masks, all_res_masks: (objects, T, h, w) binary (a result with fewer objects
+    is padded with empty masks; more objects than the annotation is an error).  Returns {'JM','JR','JD','FM','FR','FD'}: lists over
+    the objects."""
+    gt, res = np.asarray(all_gt_masks), np.asarray(all_res_masks)
+    if res.shape[0] > gt.shape[0]:
+        raise ValueError("JFM: the result has more objects than the annotation")
+    if res.shape[0] < gt.shape[0]:
+        res = np.concatenate([res, np.zeros((gt.shape[0] - res.shape[0], *res.shape[1:]), res.dtype)], 0)
+    out = {k: [] for k in ("JM", "JR", "JD", "FM", "FR", "FD")}
+    for o in range(gt.shape[0]):
+        j = np.asarray(db_eval_iou(gt[o], res[o]), dtype=np.float64)
+        f = db_eval_boundary(gt[o], res[o])
+        for key, vals in (("J", j), ("F", f)):
+            m, r, d = db_statistics(vals)
+            out[key + "M"].append(m)
+            out[key + "R"].append(r)
+            out[key + "D"].append(d)
+    return out
+
+
+def davis_masks_to_objects(masks: np.ndarray, n_objects: int) -> np.ndarray:
+    """(T, h, w) index masks -> (n_objects, T, h, w) binary masks of ids 1..n_objects."""
+    m = np.asarray(masks)
+    return np.stack([m == k for k in range(1, n_objects + 1)], 0) if n_objects else np.zeros((0, *m.shape), bool)
+
+
+def davis_jf(sequences: Dict[str, tuple]) -> Dict[str, object]:
+    """sequences: name -> (gt (T, h, w) ids, prediction (T, h, w) ids).  Frame 0 (the given annotation) and the last frame are left
+    out of the statistics as the DAVIS-2017 semi-supervised evaluation does.  Returns the J&F mean, J mean, F mean and per-sequence
+    J&F / J / F means (each a mean over the sequence's objects)."""
+    per_seq, Js, Fs = {}, [], []
+    for name, (gt, pred) in sequences.items():
+        gt, pred = np.asarray(gt), np.asarray(pred)
+        n = int(gt.max())
+        sl = slice(1, -1) if gt.shape[0] > 2 else slice(0, gt.shape[0])
+        r = JFM(davis_masks_to_objects(gt, n)[:, sl], davis_masks_to_objects(np.rint(pred).astype(np.int64), n)[:, sl], n)
+        Js.extend(r["JM"])
+        Fs.extend(r["FM"])
+        jm, fm = float(np.mean(r["JM"])), float(np.mean(r["FM"]))
+        per_seq[name] = {"J&F": (jm + fm) / 2, "J": jm, "F": fm}
+    jm, fm = float(np.mean(Js)), float(np.mean(Fs))
+    return {"J&F-Mean": (jm + fm) / 2, "J-Mean": jm, "F-Mean": fm, "sequences": per_seq}

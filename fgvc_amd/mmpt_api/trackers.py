@@ -185,9 +185,17 @@ class VanillaTracker(BaseTracker):
 
     # ---- A10: regrouping by query time ----------------------------------------------------------
     @torch.no_grad()
-    def forward_test(self, rgbs, query_points, trajectories, visibilities, save_image=False, save_path=None,
-                     iteration=None):
-        """rgbs (1,T,3,h,w), query_points (1,P,3)=(t,x,y), trajectories (1,T,P,2), visibilities (1,T,P)."""
+    def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,
+                     iteration=None, imgs=None, ref_seg_map=None, img_meta=None):
+        """rgbs (1,T,3,h,w), query_points (1,P,3)=(t,x,y), trajectories (1,T,P,2), visibilities (1,T,P).
+        Called with imgs= / ref_seg_map= / img_meta= (what BaseModel.forward(test_mode=True, **data) passes for the reference's mask
+        datasets) it propagates segmentation masks instead: forward_test_seg."""
+        if imgs is not None or ref_seg_map is not None or img_meta is not None:
+            if rgbs is not None or query_points is not None:
+                raise TypeError("VanillaTracker.forward_test: give either rgbs= / query_points= (points) or imgs= / ref_seg_map= / img_meta= (masks)")
+            return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        if rgbs is None or query_points is None:
+            raise TypeError("VanillaTracker.forward_test: missing rgbs / query_points")
         if not rgbs.is_cuda:
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
         assert rgbs.shape[0] == 1, "batch size must be 1 (vanilla_tracker.py:134)"
@@ -219,6 +227,60 @@ class VanillaTracker(BaseTracker):
         self._check_kernels()
         return (trajectories[:, :, order], visibilities[:, :, order], traj_pred,
                 torch.zeros_like(visibilities), query_points[:, order])
+
+    def output_stride(self) -> int:
+        """The encoder's output stride d (frame size / feature size): the mask path pads the frames to a multiple of it
+        (pad_divide_by), so that the feature grid is exactly the padded size / d.  (The reference's VanillaTracker has no `stride`
+        attribute; HRVanillaTracker's is the one its mask path reads.)"""
+        bb = self.backbone
+        if not all(hasattr(bb, a) for a in ("strides", "out_indices", "conv1")):
+            raise NotImplementedError(f"fgvc_amd: the mask path needs the output stride of the encoder; unknown for {type(bb).__name__}")
+        d = bb.conv1.conv.stride[0] * (2 if getattr(bb, "pool", None) is not None else 1)
+        for s_ in bb.strides[:max(bb.out_indices) + 1]:
+            d *= s_
+        return d * (int(self.stride_sample) if self.stride_sample else 1)
+
+    @torch.no_grad()
+    def forward_test_seg(self, imgs, ref_seg_map, img_meta, save_image=False, save_path=None, iteration=None, ref=None):
+        """Semi-supervised video object segmentation: HRVanillaTracker.forward_test_backward_save_mem (vanilla_tracker.py:663-830) with
+        VanillaTracker's dense masked affinity (:366-378).  imgs (1,1,3,T,h,w) Lab-normalised frames, ref_seg_map (1,h,w) integer ids
+        (0 = background), img_meta[0]['original_shape'] = (h0, w0).  Returns a list over the batch of one ndarray (T, h0, w0) of ids
+        (frame 0 = the given map, nearest-resized), as the reference does; the array is float64 here (the reference's is float32: the
+        ids are small integers, exact in either)."""
+        g = self.test_cfg.get
+        if ref_seg_map is None or imgs is None or img_meta is None:
+            raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
+        if ref_seg_map.ndim == 4 or g("coords", False):
+            raise NotImplementedError("fgvc_amd: soft (4-D) first-frame labels and coords=True (the JHMDB / BADJA heat-map form) are not on "
+                                      "the mask path; track the joints as query points instead (forward_test(rgbs=, query_points=, ...))")
+        if g("save_np", False):
+            raise NotImplementedError("fgvc_amd: save_np=True is not supported; the masks are returned (save them with numpy.save)")
+        if imgs.shape[0] != 1 or imgs.shape[1] != 1 or ref_seg_map.shape[0] != 1:     # (B, clips, 3, T, h, w): :676 folds clips into B
+            raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
+        if ref_seg_map.dtype != torch.uint8:
+            lo, hi = int(ref_seg_map.min()), int(ref_seg_map.max())
+            if hi > 255:
+                raise NotImplementedError(f"fgvc_amd: the mask path takes at most 255 object ids (largest id {hi}); split the objects "
+                                          "over several calls")
+            if lo < 0:
+                raise ValueError(f"ref_seg_map: negative id {lo}")
+        if not imgs.is_cuda:
+            raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
+        cfg = self.engine_config()
+        h, w = imgs.shape[-2:]
+        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
+        d = self.output_stride()
+        (hp, wp), pad = engine.pad_divide_by(h, w, d)
+        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
+        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
+        if (Hf * d, Wf * d) != (hp, wp):
+            raise RuntimeError(f"fgvc_amd: features {Hf}x{Wf} are not the padded frame {hp}x{wp} / {d}")
+        stats = []
+        masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats)
+        self._refine_stats = stats or None
+        self._check_kernels()
+        return [masks.cpu().numpy().astype("float64")]
 
     @torch.no_grad()
     def forward_test_main(self, rgbs, query_points, trajectories, visibilities):

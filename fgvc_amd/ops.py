@@ -1131,3 +1131,69 @@ def softargmax_top5(labels: torch.Tensor, Hf: int, Wf: int, h: int, w: int,
     _lib.call("fgvc_softargmax_top5_f32", _ptr(labels), n, Hf, Wf, P, h, w, _ptr(gauss_points), float(sigma),
               _ptr(coords), _ptr(ws), _stream(labels))
     return coords
+
+
+# ---- segmentation masks (semi-supervised VOS, vanilla_tracker.py:663-830) ------------------------------------------------------------
+
+def pil_nearest_index(n_in: int, n_out: int) -> torch.Tensor:
+    """Source rows (or columns) of Pillow's NEAREST resize from n_in to n_out (pil_nearest_interpolate, common/utils.py:39), as
+    fgvc_seg_*_u8 compute them: a running double sum of in/out starting at half a step, truncated, clamped to n_in - 1.  (Not
+    floor((o + 0.5) * in / out): at 100 -> 27 the two differ where the exact value is an integer.)"""
+    a, xo, out = n_in / n_out, n_in / n_out * 0.5, []
+    for _ in range(n_out):
+        out.append(min(int(xo), n_in - 1))
+        xo += a
+    return torch.tensor(out, dtype=torch.int64)
+
+
+def seg_max_label(seg_map: torch.Tensor, Hf: int, Wf: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """seg_map (hp, wp) uint8 -> (1,) int32 on the device: the largest id of the map sampled to (Hf, Wf) by Pillow's NEAREST rule."""
+    seg_map = _chk(seg_map, torch.uint8, "seg_map")
+    hp, wp = seg_map.shape
+    if out is None:
+        out = torch.empty((1,), device=seg_map.device, dtype=torch.int32)
+    _lib.call("fgvc_seg_max_label_u8", _ptr(seg_map), hp, wp, Hf, Wf, _ptr(out), _stream(seg_map))
+    return out
+
+
+def seg_onehot_labels(seg_map: torch.Tensor, Hf: int, Wf: int, C: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """seg_map (hp, wp) uint8 -> (HfWf, C) f32 = one_hot(pil_nearest(seg_map, (Hf, Wf)), C) (vanilla_tracker.py:700-707)."""
+    seg_map = _chk(seg_map, torch.uint8, "seg_map")
+    hp, wp = seg_map.shape
+    if out is None:
+        out = torch.empty((Hf * Wf, C), device=seg_map.device, dtype=torch.float32)
+    else:
+        assert out.is_contiguous() and out.shape == (Hf * Wf, C) and out.dtype == torch.float32
+    _lib.call("fgvc_seg_onehot_labels_u8", _ptr(seg_map), hp, wp, Hf, Wf, C, _ptr(out), _stream(seg_map))
+    return out
+
+
+def seg_hard_onehot(labels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """labels (..., C) f32 -> one_hot(argmax over C) (vanilla_tracker.py:767-769); the first maximum wins.  `out` may be `labels`."""
+    labels = _chk(labels, torch.float32, "labels")
+    C = labels.shape[-1]
+    if out is None:
+        out = torch.empty_like(labels)
+    else:
+        assert out.is_contiguous() and out.shape == labels.shape and out.dtype == torch.float32
+    _lib.call("fgvc_seg_hard_onehot_f32", _ptr(labels), labels.numel() // C, C, _ptr(out), _stream(labels))
+    return out
+
+
+def seg_readout(labels: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, int], pad: Tuple[int, int, int, int],
+                out_shape: Tuple[int, int], norm: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """labels (n, HfWf, C) f32 -> masks (n, h0, w0) uint8 (vanilla_tracker.py:773-802): bilinear to pad_shape (hp, wp), unpad by
+    pad = (left, right, top, bottom) (pad_divide_by's order), bilinear to out_shape (h0, w0), per-channel min-max normalisation where the
+    maximum is > 0 (norm), argmax over C.  Evaluated per output pixel from the feature grid: no (C, hp, wp) map."""
+    labels = _chk(labels, torch.float32, "labels")
+    n, C = labels.shape[0], labels.shape[2]
+    assert labels.shape[1] == Hf * Wf
+    (hp, wp), (lw, uw, lh, uh), (h0, w0) = pad_shape, pad, out_shape
+    if out is None:
+        out = torch.empty((n, h0, w0), device=labels.device, dtype=torch.uint8)
+    else:
+        assert out.is_contiguous() and out.shape == (n, h0, w0) and out.dtype == torch.uint8
+    ws = torch.empty((max(_lib.load().fgvc_seg_readout_workspace_bytes(n, C), 4) + 3) // 4, device=labels.device, dtype=torch.float32)
+    _lib.call("fgvc_seg_readout_u8", _ptr(labels), n, Hf, Wf, C, hp, wp, lh, lw, hp - lh - uh, wp - lw - uw, h0, w0, int(bool(norm)),
+              _ptr(out), _ptr(ws), _stream(labels))
+    return out

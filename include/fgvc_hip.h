@@ -473,6 +473,28 @@ int fgvc_softargmax_top5_f32(const float* labels, int n_frames, int Hf, int Wf, 
                              const float* gauss_points, float sigma, double* coords, void* workspace,
                              void* stream);
 
+/* ---- Segmentation masks (semi-supervised VOS, vanilla_tracker.py:663-830).  The propagation itself is fgvc_propagate_topk_f32
+ * with P = C channels; these are the two ends of the path and the hard-propagation step.
+ *
+ * Frame-0 labels: the padded index map (hp, wp) uint8 is sampled to the feature grid (Hf, Wf) by Pillow's NEAREST rule
+ * (pil_nearest_interpolate, common/utils.py:39: the source coordinate is a running double sum of in/out, truncated) and one-hot
+ * encoded.  fgvc_seg_max_label_u8 writes max(sampled map) to out[0] (int32; C = 1 + that, as F.one_hot infers it);
+ * fgvc_seg_onehot_labels_u8 writes out [Hf*Wf][C] f32 (an id >= C gives a zero row). */
+int fgvc_seg_max_label_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int32_t* out, void* stream);
+int fgvc_seg_onehot_labels_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int C, float* out, void* stream);
+
+/* Hard propagation: out[r] = one_hot(argmax_c in[r][c]) for rows r < rows; the first maximum wins.  `out` may be `in`. */
+int fgvc_seg_hard_onehot_f32(const float* in, int rows, int C, float* out, void* stream);
+
+/* Read-out of n frames: labels [n][Hf*Wf][C] f32 -> masks [n][h0][w0] uint8 =
+ *   argmax_C normalise( bilinear_{h0,w0}( crop_{top,left,h,w}( bilinear_{hp,wp}(labels) ) ) )       (align_corners=False)
+ * evaluated per output pixel from the feature grid (no (C, hp, wp) map); normalise (norm != 0) = per (frame, channel)
+ * (x - min) / (max - min + 1e-12) where max > 0, else x, min / max over the whole output frame; the first maximum wins.
+ * workspace: caller-owned device scratch of fgvc_seg_readout_workspace_bytes(n, C) bytes.  1 <= C <= 256. */
+size_t fgvc_seg_readout_workspace_bytes(int n, int C);
+int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
+                        int w0, int norm, uint8_t* masks, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 """Evaluation entry point with the steps of the reference's tools/test.py:71-198, on fgvc_amd.
 
     python tools/test.py CONFIG --task davis [--checkpoint CKPT] [--videos 4 --frames 8 --size 256 256]
+    python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -22,6 +23,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fgvc_amd.mmpt_api as api  # noqa: E402
 from fgvc_amd import apis, metrics  # noqa: E402
+from fgvc_amd.datasets import Davis2017, davis_evaluate  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
 
 DEFAULT_CFG = dict(
@@ -59,7 +61,11 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
         rank, world = dist.get_rank(), dist.get_world_size()
 
-    if a.task in ("jhmdb", "badja"):
+    if a.task == "vos":
+        if not a.data_root:
+            raise SystemExit("--task vos needs --data-root (DAVIS-2017 layout: ImageSets/2017/val.txt, JPEGImages/480p, Annotations/480p)")
+        dataset = None
+    elif a.task in ("jhmdb", "badja"):
         if not a.data_root:
             raise SystemExit("--task jhmdb needs --data-root (JHMDB frames + joint_positions + val_list.txt); --task badja the BADJA root "
                              "(joint_annotations/*.json, JPEGImages/, Annotations/)")
@@ -70,7 +76,7 @@ def main():
         dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev)
     loader = StridedLoader(dataset, rank, world) if dataset is not None else None          # :124-134
     key = "test_cfg_" + a.task                                                               # :135
-    if key not in cfg and a.task in ("jhmdb", "badja") and "test_cfg_davis" in cfg:
+    if key not in cfg and a.task in ("jhmdb", "badja", "vos") and "test_cfg_davis" in cfg:
         key = "test_cfg_davis"         # the pose task of DEFAULT_CFG (and of configs without a test_cfg_jhmdb) tracks with the TAP-Vid settings
     if key not in cfg:
         raise SystemExit(f"the config has no '{key}' (tasks it defines: {sorted(k[9:] for k in cfg if k.startswith('test_cfg_'))})")
@@ -85,7 +91,17 @@ def main():
         api.load_checkpoint(model, a.checkpoint)                                             # :158-159
     model = model.to(dev).eval()
 
-    if a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
+    if a.task == "vos":        # semi-supervised VOS: the first annotation is propagated (VanillaTracker.forward_test_seg), scored by J&F
+        if rank == 0:
+            jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev))
+            print(json.dumps({"J&F-Mean": round(jf["J&F-Mean"], 4), "J-Mean": round(jf["J-Mean"], 4), "F-Mean": round(jf["F-Mean"], 4)}))
+            for name, r in jf["sequences"].items():
+                print(json.dumps({"sequence": name, **{k: round(v, 4) for k, v in r.items()}}))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(jf, f, indent=1)
+        outputs = None
+    elif a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
             pck = badja_evaluate(model, BadjaPoses(a.data_root, size=(320, 512), device=dev))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
