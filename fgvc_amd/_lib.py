@@ -94,6 +94,10 @@ SIGNATURES = {
     "fgvc_seg_hard_onehot_f32": (_i, [_p, _i, _i, _p, _p]),
     "fgvc_seg_readout_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fgvc_seg_readout_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "fgvc_seg_soft_labels_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_soft_labels_f64": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_heatmap_coords_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fgvc_heatmap_coords_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

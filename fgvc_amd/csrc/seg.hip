@@ -283,6 +283,238 @@ __global__ __launch_bounds__(SEG_BLOCK) void seg_argmax_kernel(const float* __re
 
 size_t seg_readout_workspace_bytes(int n, int C) { return (size_t)n * SEG_NB * C * 2 * sizeof(float); }
 
+// ------------------------------------------------------------------------------------------
+// Soft first-frame labels (the JHMDB / BADJA heat-map form, vanilla_tracker.py:700-716 with a 4-D map) and their read-out to joint
+// coordinates (img2coord, :172-191, :814-818).  The map (K, hm, wm) is padded by its own pad_divide_by to (hp, wp) with the content at
+// (top, left); the padding is applied implicitly (zeros), no padded copy exists.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// bilinear (align_corners=False) of the zero-padded map at output pixel (oy, ox), in the map's dtype T as F.interpolate computes it
+// (area_pixel_compute_scale / _source_index in accscalar_t = T; the padded grid is the interpolation's input)
+template <typename T>
+__device__ __forceinline__ T padded_bilinear(const T* __restrict__ m, int hm, int wm, int top, int left, int hp, int wp, T sy, T sx,
+                                             int oy, int ox) {
+  T ry = sy * ((T)oy + (T)0.5) - (T)0.5, rx = sx * ((T)ox + (T)0.5) - (T)0.5;
+  ry = ry < (T)0 ? (T)0 : ry;
+  rx = rx < (T)0 ? (T)0 : rx;
+  const int y0 = imin((int)ry, hp - 1), x0 = imin((int)rx, wp - 1);
+  const int y1 = y0 + (y0 < hp - 1 ? 1 : 0), x1 = x0 + (x0 < wp - 1 ? 1 : 0);
+  const T ly = ry - (T)y0, lx = rx - (T)x0;
+  const T hy = (T)1 - ly, hx = (T)1 - lx;
+  auto at = [&](int y, int x) -> T {
+    const int yy = y - top, xx = x - left;
+    return (yy >= 0 && yy < hm && xx >= 0 && xx < wm) ? m[(size_t)yy * wm + xx] : (T)0;
+  };
+  return hy * (hx * at(y0, x0) + lx * at(y0, x1)) + ly * (hx * at(y1, x0) + lx * at(y1, x1));
+}
+
+// top-5 of a band: value descending, the higher flat index first among equal values (post.hip TopKHi, np.argsort's tail)
+constexpr int HM_K = 5;
+constexpr int HM_BLOCK = 256;
+constexpr int HM_BANDS = 8;
+
+struct Top5 {
+  double v[HM_K];
+  int ix[HM_K];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int j = 0; j < HM_K; ++j) {
+      v[j] = -INFINITY;
+      ix[j] = -1;
+    }
+  }
+  __device__ __forceinline__ bool accepts(double s, int id) const {
+    return s > v[HM_K - 1] || (s == v[HM_K - 1] && id > ix[HM_K - 1]);
+  }
+  __device__ __forceinline__ void insert(double s, int id) {
+#pragma unroll
+    for (int j = 0; j < HM_K; ++j) {
+      const bool b = s > v[j] || (s == v[j] && id > ix[j]);
+      const double tv = v[j];
+      const int ti = ix[j];
+      v[j] = b ? s : tv;
+      ix[j] = b ? id : ti;
+      s = b ? tv : s;
+      id = b ? ti : id;
+    }
+  }
+};
+
+struct HeatGeom {
+  int K, Hf, Wf, hm, wm, hp, wp, top, left, h0, w0, nbands;
+  float s1y, s1x, s2y, s2x;   // the composed taps' scales, as ReadoutGeom's
+};
+
+// the workgroup's candidates and partial sum -> slot (map, band) of the partials: a tree over the LDS lists, then thread 0 stores
+__device__ __forceinline__ void band_reduce_store(Top5& top, double sum, size_t o, double* __restrict__ part_v,
+                                                  int* __restrict__ part_i, double* __restrict__ part_sum) {
+  __shared__ double sv[HM_BLOCK * HM_K];
+  __shared__ int si[HM_BLOCK * HM_K];
+  __shared__ double ssum[HM_BLOCK];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < HM_K; ++j) {
+    sv[tid * HM_K + j] = top.v[j];
+    si[tid * HM_K + j] = top.ix[j];
+  }
+  ssum[tid] = sum;
+  __syncthreads();
+  for (int stride = HM_BLOCK / 2; stride >= 1; stride >>= 1) {
+    if (tid < stride) {
+#pragma unroll
+      for (int j = 0; j < HM_K; ++j) {
+        const double v = sv[(tid + stride) * HM_K + j];
+        const int id = si[(tid + stride) * HM_K + j];
+        if (id >= 0 && top.accepts(v, id)) top.insert(v, id);
+      }
+#pragma unroll
+      for (int j = 0; j < HM_K; ++j) {
+        sv[tid * HM_K + j] = top.v[j];
+        si[tid * HM_K + j] = top.ix[j];
+      }
+      ssum[tid] += ssum[tid + stride];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int j = 0; j < HM_K; ++j) {
+      part_v[o * HM_K + j] = top.v[j];
+      part_i[o * HM_K + j] = top.ix[j];
+    }
+    part_sum[o] = ssum[0];
+  }
+}
+
+}  // namespace
+
+// bank row 0: bilinear(padded map -> (Hf, Wf)) in the map's dtype, rounded once to f32; out [Hf*Wf][K], one thread per value
+template <typename T>
+__global__ __launch_bounds__(256) void seg_soft_labels_kernel(const T* __restrict__ map, int K, int hm, int wm, int hp, int wp, int top,
+                                                              int left, int Hf, int Wf, float* __restrict__ out) {
+  const T sy = (T)hp / (T)Hf, sx = (T)wp / (T)Wf;
+  const long long n = (long long)Hf * Wf * K;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const int pix = (int)(i / K), k = (int)(i - (long long)pix * K);
+    const int y = pix / Wf, x = pix - y * Wf;
+    out[i] = (float)padded_bilinear<T>(map + (size_t)k * hm * wm, hm, wm, top, left, hp, wp, sy, sx, y, x);
+  }
+}
+
+// Read-out stage 1, frames >= 1: one workgroup per (joint, frame, row band) scans the composed field (fgvc_seg_readout_u8's Taps /
+// field_value, unchanged) over its rows, one pixel per lane per step: a top-5 list and the band's sum (f64, lane-strided then a tree).
+template <bool COMPOSED>
+__global__ __launch_bounds__(HM_BLOCK) void heatmap_band_kernel(const float* __restrict__ bank, HeatGeom g, double* __restrict__ part_v,
+                                                                int* __restrict__ part_i, double* __restrict__ part_sum) {
+  const int k = blockIdx.x, f = blockIdx.y + 1, band = blockIdx.z;
+  const float* lab = bank + (size_t)f * g.Hf * g.Wf * g.K + k;
+  const int rows = cdiv(g.h0, g.nbands);
+  const int y_lo = band * rows, y_hi = imin(g.h0, y_lo + rows);
+  Top5 top;
+  top.init();
+  double sum = 0.0;
+  for (int y = y_lo; y < y_hi; ++y) {
+    Taps<COMPOSED> ty;
+    ty.make(y, g.s2y, g.hm, g.top, g.s1y, g.Hf);
+#pragma unroll
+    for (int i = 0; i < (COMPOSED ? 4 : 2); ++i) ty.t[i] *= g.Wf * g.K;
+    for (int x = threadIdx.x; x < g.w0; x += HM_BLOCK) {
+      Taps<COMPOSED> tx;
+      tx.make(x, g.s2x, g.wm, g.left, g.s1x, g.Wf);
+#pragma unroll
+      for (int i = 0; i < (COMPOSED ? 4 : 2); ++i) tx.t[i] *= g.K;
+      const double v = (double)field_value<COMPOSED>(lab, ty, tx);
+      const int id = y * g.w0 + x;
+      sum += v;
+      if (top.accepts(v, id)) top.insert(v, id);
+    }
+  }
+  band_reduce_store(top, sum, ((size_t)f * g.K + k) * g.nbands + band, part_v, part_i, part_sum);
+}
+
+// Read-out stage 1, frame 0: bilinear of the zero-padded input map straight to (h0, w0) in its own dtype -- no crop (:712-716)
+template <typename T>
+__global__ __launch_bounds__(HM_BLOCK) void heatmap_band0_kernel(const T* __restrict__ map, HeatGeom g, double* __restrict__ part_v,
+                                                                 int* __restrict__ part_i, double* __restrict__ part_sum) {
+  const int k = blockIdx.x, band = blockIdx.z;
+  const T* m = map + (size_t)k * g.hm * g.wm;
+  const T sy = (T)g.hp / (T)g.h0, sx = (T)g.wp / (T)g.w0;
+  const int rows = cdiv(g.h0, g.nbands);
+  const int y_lo = band * rows, y_hi = imin(g.h0, y_lo + rows);
+  Top5 top;
+  top.init();
+  double sum = 0.0;
+  for (int y = y_lo; y < y_hi; ++y)
+    for (int x = threadIdx.x; x < g.w0; x += HM_BLOCK) {
+      const double v = (double)padded_bilinear<T>(m, g.hm, g.wm, g.top, g.left, g.hp, g.wp, sy, sx, y, x);
+      const int id = y * g.w0 + x;
+      sum += v;
+      if (top.accepts(v, id)) top.insert(v, id);
+    }
+  band_reduce_store(top, sum, (size_t)k * g.nbands + band, part_v, part_i, part_sum);
+}
+
+// Read-out stage 2: one thread per (frame, joint) map merges its bands and writes x to coords[0][k][f], y to coords[1][k][f].
+// f64 != 0: img2coord on a float64 stack (the map was float64): top-5 normalisation in f64.  Else every value is an f32 and the
+// normalisation is f32, as post.hip's merge.  Sums in the ascending order of np.sum over argsort[-5:].
+__global__ __launch_bounds__(64) void heatmap_merge_kernel(const double* __restrict__ part_v, const int* __restrict__ part_i,
+                                                           const double* __restrict__ part_sum, int nbands, int K, int T, int w0, int f64,
+                                                           double* __restrict__ coords) {
+  const int m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= T * K) return;
+  const int f = m / K, k = m - f * K;
+  Top5 top;
+  top.init();
+  double sum = 0.0;
+  for (int b = 0; b < nbands; ++b) {
+    const size_t o = (size_t)m * nbands + b;
+    sum += part_sum[o];
+    for (int j = 0; j < HM_K; ++j) {
+      const int id = part_i[o * HM_K + j];
+      const double v = part_v[o * HM_K + j];
+      if (id >= 0 && top.accepts(v, id)) top.insert(v, id);
+    }
+  }
+  double* ox = coords + (size_t)k * T + f;
+  double* oy = ox + (size_t)K * T;
+  if (sum == 0.0) {   // np.sum(map) == 0 (:189)
+    *ox = -1.0;
+    *oy = -1.0;
+    return;
+  }
+  double ax = 0.0, ay = 0.0;
+  if (f64) {
+    double tot = 0.0;
+#pragma unroll
+    for (int j = HM_K - 1; j >= 0; --j) tot += top.v[j];
+    tot += 1e-9;
+#pragma unroll
+    for (int j = HM_K - 1; j >= 0; --j) {
+      const double wgt = top.v[j] / tot;
+      ax += (double)(top.ix[j] % w0) * wgt;
+      ay += (double)(top.ix[j] / w0) * wgt;
+    }
+  } else {
+    float tot = 0.f;
+#pragma unroll
+    for (int j = HM_K - 1; j >= 0; --j) tot += (float)top.v[j];
+    tot += 1e-9f;
+#pragma unroll
+    for (int j = HM_K - 1; j >= 0; --j) {
+      const float wgt = (float)top.v[j] / tot;
+      ax += (double)(top.ix[j] % w0) * (double)wgt;
+      ay += (double)(top.ix[j] / w0) * (double)wgt;
+    }
+  }
+  *ox = ax;
+  *oy = ay;
+}
+
+size_t heatmap_workspace_bytes(int T, int K) {
+  return (size_t)T * K * HM_BANDS * (HM_K * sizeof(double) + HM_K * sizeof(int) + sizeof(double));
+}
+
 }  // namespace fgvc
 
 using namespace fgvc;
@@ -351,6 +583,81 @@ int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int h
     seg_argmax_kernel<false><<<g2, SEG_BLOCK, 2 * C * sizeof(float), s>>>(labels, g, part, norm, masks);
   }
   FGVC_CHECK_LAUNCH("fgvc_seg_readout_u8");
+  return FGVC_OK;
+}
+
+static int soft_labels_check(const void* map, const float* out, int K, int hm, int wm, int hp, int wp, int top, int left, int Hf,
+                             int Wf, const char* name) {
+  FGVC_REQUIRE(map && out, FGVC_ERR_INVALID_ARG, "%s: null pointer", name);
+  FGVC_REQUIRE(K >= 1 && K <= 256 && hm > 0 && wm > 0 && Hf > 0 && Wf > 0, FGVC_ERR_INVALID_ARG, "%s: bad shape (1 <= K <= 256)", name);
+  FGVC_REQUIRE(top >= 0 && left >= 0 && top + hm <= hp && left + wm <= wp, FGVC_ERR_INVALID_ARG,
+               "%s: the map must lie inside the padded frame", name);
+  FGVC_REQUIRE((long long)Hf * Wf * K < (1ll << 40) && (long long)Hf * Wf < (1ll << 31), FGVC_ERR_UNSUPPORTED, "%s: too large", name);
+  return FGVC_OK;
+}
+
+int fgvc_seg_soft_labels_f32(const float* map, int K, int hm, int wm, int hp, int wp, int top, int left, int Hf, int Wf, float* out,
+                             void* stream) {
+  const int rc = soft_labels_check(map, out, K, hm, wm, hp, wp, top, left, Hf, Wf, "fgvc_seg_soft_labels_f32");
+  if (rc != FGVC_OK) return rc;
+  const long long n = (long long)Hf * Wf * K;
+  const int blocks = (int)(n < 256ll * 1024 ? (n + 255) / 256 : 1024);
+  seg_soft_labels_kernel<float><<<blocks, 256, 0, (hipStream_t)stream>>>(map, K, hm, wm, hp, wp, top, left, Hf, Wf, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_soft_labels_f32");
+  return FGVC_OK;
+}
+
+int fgvc_seg_soft_labels_f64(const double* map, int K, int hm, int wm, int hp, int wp, int top, int left, int Hf, int Wf, float* out,
+                             void* stream) {
+  const int rc = soft_labels_check(map, out, K, hm, wm, hp, wp, top, left, Hf, Wf, "fgvc_seg_soft_labels_f64");
+  if (rc != FGVC_OK) return rc;
+  const long long n = (long long)Hf * Wf * K;
+  const int blocks = (int)(n < 256ll * 1024 ? (n + 255) / 256 : 1024);
+  seg_soft_labels_kernel<double><<<blocks, 256, 0, (hipStream_t)stream>>>(map, K, hm, wm, hp, wp, top, left, Hf, Wf, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_soft_labels_f64");
+  return FGVC_OK;
+}
+
+size_t fgvc_heatmap_coords_workspace_bytes(int T, int K) {
+  if (T < 0 || K < 1) return 0;
+  return heatmap_workspace_bytes(T, K);
+}
+
+int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                            int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream) {
+  FGVC_REQUIRE(map0 && coords && (bank || T <= 1), FGVC_ERR_INVALID_ARG, "fgvc_heatmap_coords_f32: null pointer");
+  FGVC_REQUIRE(T >= 0 && T <= 65535 && Hf > 0 && Wf > 0 && K >= 1 && K <= 256 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_heatmap_coords_f32: bad shape (1 <= K <= 256, T <= 65535)");
+  FGVC_REQUIRE(hm > 0 && wm > 0 && top >= 0 && left >= 0 && top + hm <= hp && left + wm <= wp, FGVC_ERR_INVALID_ARG,
+               "fgvc_heatmap_coords_f32: the map must lie inside the padded frame");
+  FGVC_REQUIRE((long long)h0 * w0 >= HM_K && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_UNSUPPORTED,
+               "fgvc_heatmap_coords_f32: h0*w0 out of range (5 <= h0*w0 < 2^31)");
+  FGVC_REQUIRE(workspace != nullptr || T == 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_heatmap_coords_f32: workspace of fgvc_heatmap_coords_workspace_bytes() bytes required");
+  if (T == 0) return FGVC_OK;
+  HeatGeom g;
+  g.K = K; g.Hf = Hf; g.Wf = Wf; g.hm = hm; g.wm = wm; g.hp = hp; g.wp = wp; g.top = top; g.left = left; g.h0 = h0; g.w0 = w0;
+  g.nbands = HM_BANDS;
+  g.s1y = (float)Hf / (float)hp; g.s1x = (float)Wf / (float)wp;
+  g.s2y = (float)hm / (float)h0; g.s2x = (float)wm / (float)w0;
+  const size_t maps = (size_t)T * K;
+  double* part_v = static_cast<double*>(workspace);
+  double* part_sum = part_v + maps * HM_BANDS * HM_K;
+  int* part_i = reinterpret_cast<int*>(part_sum + maps * HM_BANDS);
+  hipStream_t s = (hipStream_t)stream;
+  if (map0_f64)
+    heatmap_band0_kernel<double><<<dim3(K, 1, HM_BANDS), HM_BLOCK, 0, s>>>(static_cast<const double*>(map0), g, part_v, part_i, part_sum);
+  else
+    heatmap_band0_kernel<float><<<dim3(K, 1, HM_BANDS), HM_BLOCK, 0, s>>>(static_cast<const float*>(map0), g, part_v, part_i, part_sum);
+  if (T > 1) {
+    const dim3 grid(K, T - 1, HM_BANDS);
+    if (hm == h0 && wm == w0)
+      heatmap_band_kernel<false><<<grid, HM_BLOCK, 0, s>>>(bank, g, part_v, part_i, part_sum);
+    else
+      heatmap_band_kernel<true><<<grid, HM_BLOCK, 0, s>>>(bank, g, part_v, part_i, part_sum);
+  }
+  heatmap_merge_kernel<<<cdiv((int)maps, 64), 64, 0, s>>>(part_v, part_i, part_sum, HM_BANDS, K, T, w0, f64_arith, coords);
+  FGVC_CHECK_LAUNCH("fgvc_heatmap_coords_f32");
   return FGVC_OK;
 }
 

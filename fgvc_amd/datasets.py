@@ -192,6 +192,74 @@ class TapVidPickles:
                     visibilities=vis.float().unsqueeze(0).to(d))
 
 
+# ---- heat-map form of the pose samples (jhmdb_dataset.py:101-141, badja_dataset.py:350-410, augmentation.py:790-807) ----------------
+def draw_label_map(img: np.ndarray, pt, sigma) -> np.ndarray:
+    """The pose datasets' draw_label_map (jhmdb_dataset.py:282-309; badja_dataset.py:298-325 is the same with pt = (y, x), so call it
+    with pt[::-1] there), restated: an unnormalised Gaussian patch of side 6 sigma + 1 (centre value 1) is ASSIGNED (not max-combined)
+    into img (h, w) in place around pt = (x, y).  The patch corners are int() of pt -/+ 3 sigma (+ 1): truncation toward zero, so
+    a point just left of / above the frame still draws a clipped patch; a patch entirely off the frame leaves img unchanged."""
+    h, w = img.shape
+    x_lo, y_lo = int(pt[0] - 3 * sigma), int(pt[1] - 3 * sigma)
+    x_hi, y_hi = int(pt[0] + 3 * sigma + 1), int(pt[1] + 3 * sigma + 1)
+    if x_lo >= w or y_lo >= h or x_hi < 0 or y_hi < 0:
+        return img
+    side = 6 * sigma + 1
+    r = np.arange(0, side, 1, float)
+    c = side // 2
+    patch = np.exp(-((r[None, :] - c) ** 2 + (r[:, None] - c) ** 2) / (2 * sigma ** 2))
+    px0, px1 = max(0, -x_lo), min(x_hi, w) - x_lo
+    py0, py1 = max(0, -y_lo), min(y_hi, h) - y_lo
+    img[max(0, y_lo):min(y_hi, h), max(0, x_lo):min(x_hi, w)] = patch[py0:py1, px0:px1]
+    return img
+
+
+def _cv2_linear_taps(n_in: int, n_out: int):
+    """Source indices and weights of OpenCV's INTER_LINEAR along one axis (resize.cpp, float / double images): the coordinate
+    (d + 0.5) * (n_in / n_out) - 0.5 is computed in double and rounded to float, its floor is the first tap and the float remainder the
+    second tap's weight; a coordinate below 0 snaps to (0, weight 0), one at or past n_in - 1 to (n_in - 1, weight 0).  The weights are
+    float, the interpolation is done in the image's depth (double for float64)."""
+    f = ((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = (f - s.astype(np.float32)).astype(np.float32)
+    lo, hi = s < 0, s >= n_in - 1
+    f[lo | hi] = 0.0
+    s[lo] = 0
+    s[hi] = n_in - 1
+    return s, np.minimum(s + 1, n_in - 1), (np.float32(1.0) - f).astype(np.float32), f
+
+
+def cv2_resize_linear(img: np.ndarray, size) -> np.ndarray:
+    """cv2.resize(img, (w, h), interpolation=cv2.INTER_LINEAR) of a float64 (h0, w0, K) image, restated (mmcv.imresize(...,
+    'bilinear', backend='cv2'), augmentation.py:798-802).  PARITY UNPINNED: cv2 is not installed.  What the restatement assumes of
+    OpenCV: the same size is a plain copy; otherwise a horizontal pass then a vertical pass, each a sum of two products in double with
+    float weights (_cv2_linear_taps), rows clamped to the image; the vertical weights keep their fraction where the row index is
+    clamped (row -1 and row 0 both read row 0).  Not covered: OpenCV's switch to INTER_AREA for an exact 2x downscale (the pose datasets
+    only upsample their maps) and any fused multiply-add OpenCV's build may use."""
+    h, w = size
+    img = np.asarray(img, dtype=np.float64)
+    if img.shape[:2] == (h, w):
+        return img.copy()
+    h0, w0 = img.shape[:2]
+    xs0, xs1, xw0, xw1 = _cv2_linear_taps(w0, w)
+    tmp = img[:, xs0] * xw0.astype(np.float64)[None, :, None] + img[:, xs1] * xw1.astype(np.float64)[None, :, None]
+    fy = ((np.arange(h, dtype=np.float64) + 0.5) * (h0 / h) - 0.5).astype(np.float32)
+    sy = np.floor(fy).astype(np.int64)
+    fy = (fy - sy.astype(np.float32)).astype(np.float32)
+    r0, r1 = np.clip(sy, 0, h0 - 1), np.clip(sy + 1, 0, h0 - 1)
+    b0, b1 = (np.float32(1.0) - fy).astype(np.float64), fy.astype(np.float64)
+    return tmp[r0] * b0[:, None, None] + tmp[r1] * b1[:, None, None]
+
+
+def pose_heatmaps(points_xy: np.ndarray, shape, sigma, size) -> np.ndarray:
+    """(K, 2) = (x, y) joints on a (h, w) = shape canvas -> (K, h', w') float64 heat maps at size = (h', w'): one draw_label_map per
+    joint on its own zero map, then cv2_resize_linear to the network size, channels first (the layout Resize leaves, augmentation.py:807)."""
+    h, w = shape
+    maps = np.zeros((h, w, len(points_xy)), dtype=np.float64)
+    for j, p in enumerate(points_xy):
+        draw_label_map(maps[:, :, j], p, sigma)
+    return np.ascontiguousarray(cv2_resize_linear(maps, size).transpose(2, 0, 1))
+
+
 # ---- JHMDB (mmpt/datasets/jhmdb_dataset.py:72-141) -> the tracker's sample format -------------------------------------------------
 class JhmdbPoses:
     """JHMDB pose videos in the sample format VanillaTracker.forward_test consumes.  The reference's JHMDB dataset yields
@@ -202,11 +270,19 @@ class JhmdbPoses:
     to `root`; frames `*.png`; the .mat holds `pos_img` (2, 15, T) = (x; y), 1-based (:125 "magic -1").  Frames are resized to
     `input_size` (test_pipeline_jhmdb: 320 x 320, keep_ratio=False) and go through the RGB->Lab contract; joints are scaled
     the same way.  `pose_prediction(sample, traj_pred)` maps a prediction back to the (2, 15, T) original-resolution array that
-    `metrics.jhmdb_pck` (jhmdb_dataset.py:174-256) scores against `sample["gt_poses"]`."""
-    NUM_KEYPOINTS = 15
+    `metrics.jhmdb_pck` (jhmdb_dataset.py:174-256) scores against `sample["gt_poses"]`.
 
-    def __init__(self, root: str, list_path: str = None, split: str = "val", input_size=(320, 320), device="cpu"):
-        self.root, self.input_size, self.device = root, tuple(input_size), device
+    form="heatmap": the reference's own first-frame label instead (jhmdb_dataset.py:119-141, Resize augmentation.py:790-807): data =
+    dict(imgs (1,1,3,T,h,w), ref_seg_map (1, 15, h, w) float64 = one draw_label_map Gaussian (sigma 4) per joint at the video's own
+    resolution, resized to the network size by cv2_resize_linear (parity unpinned), img_meta = [dict(original_shape=(h0, w0))]).
+    VanillaTracker.forward_test with test_cfg.coords=True returns the (2, 15, T) coordinates at (h0, w0) directly."""
+    NUM_KEYPOINTS = 15
+    SIGMA = 4
+
+    def __init__(self, root: str, list_path: str = None, split: str = "val", input_size=(320, 320), device="cpu", form: str = "points"):
+        if form not in ("points", "heatmap"):
+            raise ValueError(f"form={form!r}: 'points' or 'heatmap'")
+        self.root, self.input_size, self.device, self.form = root, tuple(input_size), device, form
         self.samples = []
         with open(os.path.join(list_path or root, f"{split}_list.txt")) as f:
             for line in f:
@@ -232,6 +308,12 @@ class JhmdbPoses:
         scale = np.array([w / w0, h / h0]).reshape(2, 1, 1)
         gts = gt * scale
         n = min(T, Tg)                                                                                           # :205
+        if self.form == "heatmap":
+            heat = pose_heatmaps(gt[:, :, 0].T, (h0, w0), self.SIGMA, (h, w))                                   # (15, h, w) f64
+            rgbs = preprocess_tapvid_frames(frames[:n].to(self.device), self.input_size)
+            imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()                                        # (1,1,3,T,h,w)
+            data = dict(imgs=imgs, ref_seg_map=torch.from_numpy(heat).unsqueeze(0).to(self.device), img_meta=[dict(original_shape=(h0, w0))])
+            return data, dict(gt_poses=gt[:, :, :n], original_shape=(h0, w0))
         traj = torch.from_numpy(gts[:, :, :n]).permute(2, 1, 0).float().contiguous()                             # (T,15,2)
         qp = torch.cat([torch.zeros(self.NUM_KEYPOINTS, 1), traj[0]], 1)                                        # (15,3) = (0,x,y)
         rgbs = preprocess_tapvid_frames(frames[:n].to(self.device), self.input_size)
@@ -261,6 +343,19 @@ def jhmdb_evaluate(model, dataset: "JhmdbPoses"):
     return metrics.jhmdb_pck(preds, gts)
 
 
+def jhmdb_evaluate_heatmap(model, dataset: "JhmdbPoses"):
+    """The heat-map form (JhmdbPoses(form='heatmap'), a model whose test_cfg has coords=True): the (2, 15, T) coordinates the tracker
+    returns at the video's own resolution go to metrics.jhmdb_pck as they are."""
+    from . import metrics
+    assert dataset.form == "heatmap", "jhmdb_evaluate_heatmap reads JhmdbPoses(form='heatmap')"
+    preds, gts = [], []
+    for i in range(len(dataset)):
+        data, meta = dataset[i]
+        preds.append(np.asarray(model(test_mode=True, **data)[0], dtype=np.float64))
+        gts.append(meta["gt_poses"])
+    return metrics.jhmdb_pck(preds, gts)
+
+
 # SMAL joints BADJA annotates (badja_dataset.py:71-82 `SMALJointInfo.annotated_classes`): 20 of the 37 per frame
 BADJA_ANNOTATED = (8, 9, 10, 12, 13, 14, 15, 18, 19, 20, 22, 23, 24, 25, 28, 31, 32, 33, 35, 36)
 
@@ -277,11 +372,18 @@ class BadjaPoses:
     are skipped (:177); the reference's IGNORE_ANIMALS list is ONE string by a missing comma (:38-41) and ignores nothing -- same here.
     Frames are resized to `size` = (320, 512) (:355-362; the released pipeline's Resize(-1, 320) then changes nothing) and go through
     the RGB->Lab contract; joints are scaled the same way (:364-366, :489-494).  Image resizing is PIL's here, OpenCV's there: the
-    adapter is restated from the file, "parity unpinned" (no BADJA data or mmcv offline)."""
+    adapter is restated from the file, "parity unpinned" (no BADJA data or mmcv offline).
 
-    def __init__(self, root: str, list_path: str = None, size=(320, 512), length: int = -1, device="cpu"):
+    form="heatmap": the reference's own first-frame label instead (badja_dataset.py:350-410): data = dict(imgs (1,1,3,T,h,w),
+    ref_seg_map (1, J, h, w) float64 = one draw_label_map Gaussian (sigma 3, point (y, x)) per joint on a (h // 2, w // 2) canvas at half
+    the joint coordinates, resized to `size` by cv2_resize_linear (Resize, parity unpinned), img_meta = [dict(original_shape=size)])."""
+    SIGMA, SCALE = 3, 2
+
+    def __init__(self, root: str, list_path: str = None, size=(320, 512), length: int = -1, device="cpu", form: str = "points"):
         import json
-        self.root, self.size, self.length, self.device = root, tuple(size), int(length), device
+        if form not in ("points", "heatmap"):
+            raise ValueError(f"form={form!r}: 'points' or 'heatmap'")
+        self.root, self.size, self.length, self.device, self.form = root, tuple(size), int(length), device, form
         self.videos = []
         adir = os.path.join(list_path or root, "joint_annotations")
         for name in sorted(os.listdir(adir)):
@@ -331,6 +433,13 @@ class BadjaPoses:
             if joints[t] is not None:
                 traj[t] = torch.from_numpy(joints[t][:, ::-1].copy()).float()                      # (x,y)
                 vis[t] = torch.from_numpy((np.asarray(visibles[t]) > 0).astype(np.float32))
+        meta = dict(joints=joints, visibles=visibles, segs=segs, original_shape=(h0, w0), name=v["name"])
+        if self.form == "heatmap":         # joints (y, x) at the network size, halved, drawn on the half-size canvas (:382-397)
+            heat = pose_heatmaps(joints[0][:, ::-1] / self.SCALE, (h // self.SCALE, w // self.SCALE), self.SIGMA, (h, w))
+            rgbs = preprocess_tapvid_frames(frames.to(self.device), self.size)
+            imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()
+            return (dict(imgs=imgs, ref_seg_map=torch.from_numpy(heat).unsqueeze(0).to(self.device), img_meta=[dict(original_shape=(h, w))]),
+                    meta)
         qp = torch.cat([torch.zeros(J, 1), traj[0]], 1)                                            # (J,3) = (0,x,y)
         rgbs = preprocess_tapvid_frames(frames.to(self.device), self.size)
         d = self.device
@@ -354,6 +463,19 @@ def badja_evaluate(model, dataset: "BadjaPoses"):
         out = model(test_mode=True, **sample)
         assert torch.equal(out[4], sample["query_points"])              # every query is at t = 0: one group, order kept
         preds.append(dataset.pose_prediction(out[2]))
+        js.append(meta["joints"]); vs.append(meta["visibles"]); ss.append(meta["segs"])
+    return metrics.badja_pck(preds, js, vs, ss)
+
+
+def badja_evaluate_heatmap(model, dataset: "BadjaPoses"):
+    """The heat-map form (BadjaPoses(form='heatmap'), a model whose test_cfg has coords=True): the (2, J, T) coordinates at the network
+    size go to metrics.badja_pck as they are."""
+    from . import metrics
+    assert dataset.form == "heatmap", "badja_evaluate_heatmap reads BadjaPoses(form='heatmap')"
+    preds, js, vs, ss = [], [], [], []
+    for i in range(len(dataset)):
+        data, meta = dataset[i]
+        preds.append(np.asarray(model(test_mode=True, **data)[0], dtype=np.float64))
         js.append(meta["joints"]); vs.append(meta["visibles"]); ss.append(meta["segs"])
     return metrics.badja_pck(preds, js, vs, ss)
 

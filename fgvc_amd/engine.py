@@ -442,3 +442,33 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
     rec("end")
     return masks
+
+
+def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                       out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
+                       stats_out: Optional[list] = None, events: Optional[dict] = None) -> torch.Tensor:
+    """Soft first-frame labels read out as joint coordinates for one clip (vanilla_tracker.py:663-830 with a 4-D map and
+    test_cfg.coords=True, VanillaTracker's affinity).  feats_hwc: the clip's bank as run_affinity takes it, encoded from the padded
+    frames; heat (K, hm, wm) f32 | f64 on the device, the map BEFORE its own padding map_pad = (left, right, top, bottom) (pad_divide_by of
+    the map's size, :672); out_shape = (h0, w0).  Returns (2, K, T) float64 on the device = img2coord of the stacked maps (:814-818).
+    K is the map's first dimension: no host read.  The propagation is the mask path's soft one with P = K (no min-max normalisation,
+    :785 applies to index maps only).  `events`: as propagate_masks."""
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    K = heat.shape[0]
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    rec("labels")
+    bank = torch.zeros((T, Hf * Wf, K), device=dev, dtype=torch.float32)
+    ops.seg_soft_labels(heat, map_pad, Hf, Wf, out=bank[0])
+    rec("affinity")
+    plan = plan_clip(T, [0], cfg)
+    tk = run_affinity(feats_hwc, Hf, Wf, plan, cfg, channels=channels)
+    if stats_out is not None and tk.refine_stats is not None:
+        stats_out.append(tk.refine_stats)
+    rec("propagation")
+    for f in range(1, T):
+        row = tk.row(plan.out_rows[(0, f)])
+        ops.propagate_topk(bank, tk.slot_frame[row], tk.idx[row], tk.weight[row], Hf, Wf, Hf, Wf, out=bank[f])
+    rec("readout")
+    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    rec("end")
+    return coords

@@ -250,11 +250,15 @@ class VanillaTracker(BaseTracker):
         g = self.test_cfg.get
         if ref_seg_map is None or imgs is None or img_meta is None:
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
-        if ref_seg_map.ndim == 4 or g("coords", False):
-            raise NotImplementedError("fgvc_amd: soft (4-D) first-frame labels and coords=True (the JHMDB / BADJA heat-map form) are not on "
-                                      "the mask path; track the joints as query points instead (forward_test(rgbs=, query_points=, ...))")
+        if (ref_seg_map.ndim == 4) != bool(g("coords", False)):
+            raise NotImplementedError("fgvc_amd: soft (4-D) first-frame labels go with coords=True only (the JHMDB / BADJA heat-map form: "
+                                      "joint coordinates), and coords=True with soft labels only (img2coord asserts on an index map); "
+                                      "full-resolution soft maps are not returned -- track the joints as query points instead "
+                                      "(forward_test(rgbs=, query_points=, ...)) or pass coords=True")
         if g("save_np", False):
             raise NotImplementedError("fgvc_amd: save_np=True is not supported; the masks are returned (save them with numpy.save)")
+        if ref_seg_map.ndim == 4:
+            return self._forward_test_heatmap(imgs, ref_seg_map, img_meta)
         if imgs.shape[0] != 1 or imgs.shape[1] != 1 or ref_seg_map.shape[0] != 1:     # (B, clips, 3, T, h, w): :676 folds clips into B
             raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
         if ref_seg_map.dtype != torch.uint8:
@@ -281,6 +285,40 @@ class VanillaTracker(BaseTracker):
         self._refine_stats = stats or None
         self._check_kernels()
         return [masks.cpu().numpy().astype("float64")]
+
+    def _forward_test_heatmap(self, imgs, heat, img_meta):
+        """forward_test_seg with soft first-frame labels and test_cfg.coords=True (the JHMDB / BADJA heat-map form): heat (1, K, hm, wm)
+        float32 | float64, padded by its OWN pad_divide_by (vanilla_tracker.py:672).  Returns a list over the batch of one ndarray
+        (2, K, T) float64 = img2coord of the propagated maps at img_meta[0]['original_shape'] (:814-818).  Frame 0 is the padded map
+        resized to that shape, NOT unpadded (:712-716): the reference's quirk, kept."""
+        if self.engine_config().hard_prop:
+            raise NotImplementedError("fgvc_amd: hard_prop=True with soft labels (the reference's F.one_hot without num_classes drops the last "
+                                      "channel when it never wins, and the next frame's cat then fails, vanilla_tracker.py:762-768)")
+        if imgs.shape[0] != 1 or imgs.shape[1] != 1 or heat.shape[0] != 1:
+            raise NotImplementedError("fgvc_amd: the heat-map path runs batch size 1; call it once per video")
+        if heat.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"ref_seg_map: soft labels must be float32 or float64, got {heat.dtype}")
+        K = heat.shape[1]
+        if not 1 <= K <= 256:
+            raise NotImplementedError(f"fgvc_amd: the heat-map path takes 1 to 256 joints (got {K})")
+        if not imgs.is_cuda:
+            raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
+        heat = heat[0].to(imgs.device).contiguous()
+        if not bool(torch.isfinite(heat).all()):
+            raise ValueError("ref_seg_map: the soft labels hold a non-finite value")
+        cfg = self.engine_config()
+        h, w = imgs.shape[-2:]
+        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
+        d = self.output_stride()
+        _, pad = engine.pad_divide_by(h, w, d)
+        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], d)
+        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
+        stats = []
+        coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats)
+        self._refine_stats = stats or None
+        self._check_kernels()
+        return [coords.cpu().numpy()]
 
     @torch.no_grad()
     def forward_test_main(self, rgbs, query_points, trajectories, visibilities):

@@ -1197,3 +1197,54 @@ def seg_readout(labels: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, in
     _lib.call("fgvc_seg_readout_u8", _ptr(labels), n, Hf, Wf, C, hp, wp, lh, lw, hp - lh - uh, wp - lw - uw, h0, w0, int(bool(norm)),
               _ptr(out), _ptr(ws), _stream(labels))
     return out
+
+
+# ---- soft first-frame labels read out as joint coordinates (JHMDB / BADJA heat maps, vanilla_tracker.py:663-830 with coords=True) ----
+
+def _heat(heat: torch.Tensor) -> torch.Tensor:
+    if not heat.is_cuda:
+        raise _lib.FgvcHipError("heat must be on the GPU (fgvc_amd has no CPU path)")
+    if heat.dtype not in (torch.float32, torch.float64) or heat.dim() != 3:
+        raise TypeError(f"heat: expected a (K, h, w) float32 or float64 map, got {tuple(heat.shape)} {heat.dtype}")
+    return heat.contiguous()
+
+
+def seg_soft_labels(heat: torch.Tensor, pad: Tuple[int, int, int, int], Hf: int, Wf: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """heat (K, hm, wm) f32 | f64, the map before its own padding pad = (left, right, top, bottom) -> (HfWf, K) f32 =
+    F.interpolate(F.pad(heat, pad), (Hf, Wf), bilinear).float() computed in heat's dtype (vanilla_tracker.py:706-711)."""
+    heat = _heat(heat)
+    K, hm, wm = heat.shape
+    lw, uw, lh, uh = pad
+    if out is None:
+        out = torch.empty((Hf * Wf, K), device=heat.device, dtype=torch.float32)
+    else:
+        assert out.is_contiguous() and out.shape == (Hf * Wf, K) and out.dtype == torch.float32
+    name = "fgvc_seg_soft_labels_f64" if heat.dtype == torch.float64 else "fgvc_seg_soft_labels_f32"
+    _lib.call(name, _ptr(heat), K, hm, wm, hm + lh + uh, wm + lw + uw, lh, lw, Hf, Wf, _ptr(out), _stream(heat))
+    return out
+
+
+def heatmap_coords(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, pad: Tuple[int, int, int, int],
+                   out_shape: Tuple[int, int], f64_arith: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """img2coord of the T frames the reference stacks (vanilla_tracker.py:712-716, :770-784, :803, :814-818) -> (2, K, T) f64.
+    Frame 0 = bilinear(F.pad(heat, pad) -> out_shape) in heat's dtype, not unpadded; frame f >= 1 = bilinear to the padded size, unpad,
+    bilinear to out_shape, in f32, from bank[f] (T, HfWf, K) f32 (bank[0] is not read).  The top-5 normalisation runs in f64 when
+    `f64_arith` (default: heat is float64, as np.stack makes it), else in f32.  No (K, h0, w0) map is built."""
+    heat = _heat(heat)
+    bank = _chk(bank, torch.float32, "bank")
+    K, hm, wm = heat.shape
+    T = bank.shape[0]
+    assert bank.shape[1:] == (Hf * Wf, K), (tuple(bank.shape), Hf, Wf, K)
+    lw, uw, lh, uh = pad
+    h0, w0 = out_shape
+    if f64_arith is None:
+        f64_arith = heat.dtype == torch.float64
+    if out is None:
+        out = torch.empty((2, K, T), device=heat.device, dtype=torch.float64)
+    else:
+        assert out.is_contiguous() and out.shape == (2, K, T) and out.dtype == torch.float64
+    ws = torch.empty((max(_lib.load().fgvc_heatmap_coords_workspace_bytes(T, K), 8) + 7) // 8, device=heat.device, dtype=torch.float64)
+    _lib.call("fgvc_heatmap_coords_f32", _ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm,
+              hm + lh + uh, wm + lw + uw, lh, lw, h0, w0, int(bool(f64_arith)), _ptr(out), _ptr(ws), _stream(heat))
+    return out

@@ -495,6 +495,29 @@ size_t fgvc_seg_readout_workspace_bytes(int n, int C);
 int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
                         int w0, int norm, uint8_t* masks, void* workspace, void* stream);
 
+/* ---- Soft first-frame labels read out as joint coordinates (the JHMDB / BADJA heat-map form: vanilla_tracker.py:700-716 with a 4-D
+ * map, :770-784, img2coord :172-191, :814-818).  The map (K, hm, wm) f32 or f64 lies at (top, left) of its zero padding to (hp, wp)
+ * (its own pad_divide_by, :672); the padding is implicit, no padded copy is made.  Propagation is fgvc_propagate_topk_f32 with P = K.
+ *
+ * Bank row 0 (:706-711): out [Hf*Wf][K] f32 = bilinear(padded map -> (Hf, Wf)) (align_corners=False) computed in the map's dtype,
+ * rounded once to f32. */
+int fgvc_seg_soft_labels_f32(const float* map, int K, int hm, int wm, int hp, int wp, int top, int left, int Hf, int Wf, float* out,
+                             void* stream);
+int fgvc_seg_soft_labels_f64(const double* map, int K, int hm, int wm, int hp, int wp, int top, int left, int Hf, int Wf, float* out,
+                             void* stream);
+
+/* Coordinates of T frames: coords [2][K][T] f64 (x row, then y row), the reference's img2coord of
+ *   frame 0:   bilinear_{h0,w0}(padded map) in the map's dtype, NOT unpadded (:712-716); map0 is f64 if map0_f64, else f32;
+ *   frame f>0: bilinear_{h0,w0}(crop_{top,left,hm,wm}(bilinear_{hp,wp}(bank[f]))) in f32 (fgvc_seg_readout_u8's composed taps);
+ * bank [T][Hf*Wf][K] f32 (row 0 is not read).  Per map: the top 5 values (descending, the higher flat index first among equals),
+ * v / (sum5 + 1e-9) in f64 if f64_arith (np.stack of a float64 frame 0) else in f32, x = sum (idx % w0) * v, y = sum (idx / w0) * v
+ * in f64; a map whose sum is 0 gives (-1, -1).  The sum is accumulated in f64, lane-strided per row band and then over a tree and
+ * the bands (for non-negative maps: sum == 0 <=> max == 0).  No full-resolution map is built.  workspace: caller-owned device
+ * scratch of fgvc_heatmap_coords_workspace_bytes(T, K) bytes; no atomics, nothing to clear.  1 <= K <= 256, 5 <= h0*w0. */
+size_t fgvc_heatmap_coords_workspace_bytes(int T, int K);
+int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                            int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ import fgvc_amd.mmpt_api as api  # noqa: E402
 from fgvc_amd import apis, metrics  # noqa: E402
 from fgvc_amd.datasets import Davis2017, davis_evaluate  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
+from fgvc_amd.datasets import badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
 
 DEFAULT_CFG = dict(
     model=dict(type="VanillaTracker",
@@ -46,6 +47,9 @@ def main():
     ap.add_argument("--points", type=int, default=8)
     ap.add_argument("--query-mode", default="first")
     ap.add_argument("--data-root", default=None, help="TAP-Vid pickles (directory of *.pkl or one .pkl); default: synthetic clips")
+    ap.add_argument("--pose-form", choices=["points", "heatmap"], default="points",
+                    help="jhmdb / badja: 'points' tracks the frame-0 joints as query points; 'heatmap' propagates the reference's first-frame "
+                         "Gaussian maps and reads joints out of them (test_cfg.coords=True)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -81,6 +85,9 @@ def main():
     if key not in cfg:
         raise SystemExit(f"the config has no '{key}' (tasks it defines: {sorted(k[9:] for k in cfg if k.startswith('test_cfg_'))})")
     test_cfg = cfg[key]
+    heatmap = a.task in ("jhmdb", "badja") and a.pose_form == "heatmap"
+    if heatmap:
+        test_cfg = dict(test_cfg, coords=True)       # the reference's pose configs: 4-D first-frame maps read out by img2coord
     model_cfg = dict(type=cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
@@ -103,15 +110,27 @@ def main():
         outputs = None
     elif a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
-            pck = badja_evaluate(model, BadjaPoses(a.data_root, size=(320, 512), device=dev))
+            if heatmap:        # --pose-form heatmap: the reference's own first-frame label (BadjaPoses(form='heatmap'))
+                pck = badja_evaluate_heatmap(model, BadjaPoses(a.data_root, size=(320, 512), device=dev, form="heatmap"))
+            else:
+                pck = badja_evaluate(model, BadjaPoses(a.data_root, size=(320, 512), device=dev))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(pck, f, indent=1)
         outputs = None
     elif a.task == "jhmdb":    # pose tracking: the 15 joints of frame 0 are the query points (fgvc_amd.datasets.JhmdbPoses)
         # PCK is a mean over ALL videos' joints (jhmdb_dataset.py:174-256), so the set is scored by one process: rank 0 runs it, the
         # other ranks of a `--launcher pytorch` job wait at the common teardown below
         if rank == 0:
-            pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev))
+            if heatmap:
+                pck = jhmdb_evaluate_heatmap(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev, form="heatmap"))
+            else:
+                pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(pck, f, indent=1)
         outputs = None
     else:
         outputs = apis.multi_gpu_test(model, loader) if distributed else apis.single_gpu_test(model, loader)   # :160-190
