@@ -82,6 +82,7 @@ SIGNATURES = {
     "fgvc_dense_propagate_f32": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "fgvc_local_corr_topk_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
     "fgvc_local_corr_topk_f16x3": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
+    "fgvc_local_merge_plan_f32": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "fgvc_topk_coord_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_c2f_refine_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "fgvc_c2f_refine_mode_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p]),

@@ -34,6 +34,8 @@ int split_bf16_launch(const float*, uint16_t*, long long, int, hipStream_t);
 int corr_volume_bf16_launch(const uint16_t*, const uint16_t*, int, int, int, float, float*, int, hipStream_t);
 int local_merge_launch(const int32_t*, const float*, int, int, int, int, int, float, int32_t*, float*, float*,
                        hipStream_t);
+int local_merge_plan_launch(const int32_t*, const float*, const int32_t*, int, int, int, int, int, int, int, float, int32_t*, float*,
+                            float*, hipStream_t);
 int topk_coord_launch(const int32_t*, const float*, int, int, int, int, int, float*, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
@@ -528,6 +530,23 @@ int fgvc_local_corr_topk_f16x3(const uint16_t* qsplit, const uint16_t* ksplit, c
   if (rc != FGVC_OK) return rc;
   return local_merge_launch(pair_idx_ws, pair_score_ws, n_slots, H, W, R, topk, temperature, idx_out, logit_out,
                             weight_out, (hipStream_t)stream);
+}
+
+int fgvc_local_merge_plan_f32(const int32_t* pair_idx, const float* pair_score, int n_pairs, const int32_t* slot_pair, int n_rows,
+                              int max_slots, int H, int W, int R, int topk, float temperature, int32_t* idx_out, float* logit_out,
+                              float* weight_out, void* stream) {
+  FGVC_REQUIRE(pair_idx && pair_score && slot_pair && idx_out && logit_out && weight_out, FGVC_ERR_INVALID_ARG,
+               "fgvc_local_merge_plan_f32: null pointer");
+  FGVC_REQUIRE(H > 0 && W > 0 && R >= 0 && n_pairs >= 1 && n_rows >= 0 && max_slots >= 1, FGVC_ERR_INVALID_ARG,
+               "fgvc_local_merge_plan_f32: bad shape H=%d W=%d R=%d n_pairs=%d n_rows=%d max_slots=%d", H, W, R, n_pairs, n_rows, max_slots);
+  FGVC_REQUIRE(topk >= 1 && topk <= 16, FGVC_ERR_UNSUPPORTED, "fgvc_local_merge_plan_f32: topk=%d outside 1..16", topk);
+  FGVC_REQUIRE(temperature > 0.f, FGVC_ERR_INVALID_ARG, "fgvc_local_merge_plan_f32: temperature must be > 0");
+  FGVC_REQUIRE(n_rows <= 65535, FGVC_ERR_UNSUPPORTED, "fgvc_local_merge_plan_f32: n_rows=%d > 65535 per call", n_rows);
+  FGVC_REQUIRE((long long)max_slots * (2 * R + 1) * (2 * R + 1) < (1ll << 31) && (long long)H * W < (1ll << 30), FGVC_ERR_UNSUPPORTED,
+               "fgvc_local_merge_plan_f32: index overflow");
+  if (n_rows == 0) return FGVC_OK;
+  return local_merge_plan_launch(pair_idx, pair_score, slot_pair, n_pairs, n_rows, max_slots, H, W, R, topk, temperature, idx_out,
+                                 logit_out, weight_out, (hipStream_t)stream);
 }
 
 int fgvc_topk_coord_f32(const int32_t* idx, const float* weight, int H, int W, int R, int topk, int scale, float* out,

@@ -10,6 +10,59 @@
 
 namespace fgvc {
 
+// One key slot of one query: its pair list (in-image taps of the square window, canonical order) then, on the border, the zero-padded taps
+// (score exactly 0, ascending tap order = canonical tie order).  Candidate id = gid0 + tap.
+template <int K>
+__device__ __forceinline__ void local_merge_slot(TopK<K>& top, const int32_t* __restrict__ li, const float* __restrict__ ls, int kout,
+                                                 int qy, int qx, int H, int W, int R, int gid0, bool border) {
+  const int L = 2 * R + 1;
+  for (int j = 0; j < kout; ++j) {
+    const int id = li[j];
+    if (id < 0) break;
+    const int ky = id / W, kx = id - ky * W;
+    const int gid = gid0 + (ky - qy + R) * L + (kx - qx + R);
+    const float s = ls[j];
+    if (!top.accepts(s, gid)) break;
+    top.insert(s, gid);
+  }
+  if (border) {
+    bool done = false;
+    for (int a = 0; a < L && !done; ++a) {
+      const int ky = qy + a - R;
+      for (int b = 0; b < L; ++b) {
+        const int kx = qx + b - R;
+        if (ky >= 0 && ky < H && kx >= 0 && kx < W) continue;
+        const int gid = gid0 + a * L + b;
+        if (!top.accepts(0.f, gid)) { done = true; break; }
+        top.insert(0.f, gid);
+      }
+    }
+  }
+}
+
+// temperature after the top-k (:563), softmax over the k survivors, one query's row of idx / logit / weight
+template <int K>
+__device__ __forceinline__ void local_merge_write(const TopK<K>& top, int kout, float temperature, int32_t* __restrict__ io,
+                                                  float* __restrict__ lo, float* __restrict__ wo) {
+  float lg[K], w[K];
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < K; ++j) lg[j] = top.v[j] / temperature;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    w[j] = (j < kout) ? expf(lg[j] - lg[0]) : 0.f;
+    sum += w[j];
+  }
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    if (j < kout) {
+      io[j] = top.ix[j] == IDX_EMPTY ? -1 : top.ix[j];
+      lo[j] = lg[j];
+      wo[j] = w[j] / sum;
+    }
+  }
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void local_merge_kernel(const int32_t* __restrict__ pair_idx,
                                                            const float* __restrict__ pair_score, int T, int H, int W,
@@ -26,47 +79,39 @@ __global__ __launch_bounds__(256) void local_merge_kernel(const int32_t* __restr
   top.init();
   for (int t = 0; t < T; ++t) {
     const size_t o = ((size_t)t * HW + q) * kout;
-    for (int j = 0; j < kout; ++j) {
-      const int id = pair_idx[o + j];
-      if (id < 0) break;
-      const int ky = id / W, kx = id - ky * W;
-      const int gid = t * L * L + (ky - qy + R) * L + (kx - qx + R);
-      const float s = pair_score[o + j];
-      if (!top.accepts(s, gid)) break;
-      top.insert(s, gid);
-    }
-    if (border) {  // zero-padded taps: score exactly 0, ascending tap order = canonical tie order
-      bool done = false;
-      for (int a = 0; a < L && !done; ++a) {
-        const int ky = qy + a - R;
-        for (int b = 0; b < L; ++b) {
-          const int kx = qx + b - R;
-          if (ky >= 0 && ky < H && kx >= 0 && kx < W) continue;
-          const int gid = t * L * L + a * L + b;
-          if (!top.accepts(0.f, gid)) { done = true; break; }
-          top.insert(0.f, gid);
-        }
-      }
-    }
-  }
-  float lg[K], w[K];
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < K; ++j) lg[j] = top.v[j] / temperature;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    w[j] = (j < kout) ? expf(lg[j] - lg[0]) : 0.f;
-    sum += w[j];
+    local_merge_slot<K>(top, pair_idx + o, pair_score + o, kout, qy, qx, H, W, R, t * L * L, border);
   }
   const size_t o = (size_t)q * kout;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    if (j < kout) {
-      idx_out[o + j] = top.ix[j] == IDX_EMPTY ? -1 : top.ix[j];
-      logit_out[o + j] = lg[j];
-      weight_out[o + j] = w[j] / sum;
-    }
+  local_merge_write<K>(top, kout, temperature, idx_out + o, logit_out + o, weight_out + o);
+}
+
+// The same merge for every output row of a planned clip in one launch (grid.y = row): row r's key slot j is fed by pair
+// slot_pair[r][j] of the pair lists (-1: no slot).  Candidate id = j*L^2 + tap, so a pair that fills two slot positions (frame 0 twice
+// while f <= precede_frames) gives two candidate sets, as in the reference.  A row whose slots are 0..T-1 is local_merge_kernel's
+// call on those T lists, bit for bit (the same insertions in the same order).  A pair id outside [0, n_pairs) counts as no slot.
+template <int K>
+__global__ __launch_bounds__(256) void local_merge_plan_kernel(const int32_t* __restrict__ pair_idx,
+                                                                const float* __restrict__ pair_score,
+                                                                const int32_t* __restrict__ slot_pair, int n_pairs,
+                                                                int max_slots, int H, int W, int R, int kout, float temperature,
+                                                                int32_t* __restrict__ idx_out, float* __restrict__ logit_out,
+                                                                float* __restrict__ weight_out) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  const int row = blockIdx.y;
+  const int HW = H * W, L = 2 * R + 1;
+  if (q >= HW) return;
+  const int qy = q / W, qx = q - qy * W;
+  const bool border = qy < R || qx < R || qy + R >= H || qx + R >= W;
+  TopK<K> top;
+  top.init();
+  for (int j = 0; j < max_slots; ++j) {
+    const int p = slot_pair[(size_t)row * max_slots + j];
+    if (p < 0 || p >= n_pairs) continue;
+    const size_t o = ((size_t)p * HW + q) * kout;
+    local_merge_slot<K>(top, pair_idx + o, pair_score + o, kout, qy, qx, H, W, R, j * L * L, border);
   }
+  const size_t o = ((size_t)row * HW + q) * kout;
+  local_merge_write<K>(top, kout, temperature, idx_out + o, logit_out + o, weight_out + o);
 }
 
 // A7 get_coord (vanilla_tracker.py:445-488): expected coordinate of each query under its top-k window weights.
@@ -109,6 +154,20 @@ int local_merge_launch(const int32_t* pi, const float* ps, int T, int H, int W, 
   else if (topk <= 10) local_merge_kernel<10><<<grid, 256, 0, s>>>(pi, ps, T, H, W, R, topk, temp, io, lo, wo);
   else local_merge_kernel<16><<<grid, 256, 0, s>>>(pi, ps, T, H, W, R, topk, temp, io, lo, wo);
   FGVC_CHECK_LAUNCH("fgvc_local_corr_topk_f32(merge)");
+  return FGVC_OK;
+}
+
+int local_merge_plan_launch(const int32_t* pi, const float* ps, const int32_t* slot_pair, int n_pairs, int n_rows, int max_slots, int H,
+                            int W, int R, int topk, float temp, int32_t* io, float* lo, float* wo, hipStream_t s) {
+  const dim3 grid(cdiv(H * W, 256), n_rows);
+#define FGVC_LMP(KK) \
+  local_merge_plan_kernel<KK><<<grid, 256, 0, s>>>(pi, ps, slot_pair, n_pairs, max_slots, H, W, R, topk, temp, io, lo, wo)
+  if (topk <= 1) FGVC_LMP(1);
+  else if (topk <= 5) FGVC_LMP(5);
+  else if (topk <= 10) FGVC_LMP(10);
+  else FGVC_LMP(16);
+#undef FGVC_LMP
+  FGVC_CHECK_LAUNCH("fgvc_local_merge_plan_f32");
   return FGVC_OK;
 }
 

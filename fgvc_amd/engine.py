@@ -472,3 +472,200 @@ def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Te
     coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
     rec("end")
     return coords
+
+
+# ---- HRVanillaTracker's label maps: the local-window affinity (vanilla_tracker.py:663-830, local_attention.py:883-1006) ----------------
+#
+# masked_attention_efficient_correlation scores every query pixel against the (2R+1)^2 window of each key slot (mmcv.ops.Correlation,
+# zero padded: a tap outside the frame scores 0 and carries label 0) and keeps the top k of K*(2R+1)^2 candidates.  Planned like the dense
+# path: the clip's unique (query frame, key frame) pairs run through the pair kernel under the square window, chunk by chunk, each chunk's
+# rows are merged in one launch (fgvc_local_merge_plan_f32 adds the zero taps per slot), then the frames are swept one by one.
+
+LOCAL_PAIR_BUDGET = 512 << 20     # bytes of pair lists (idx + score) held at once: 8.2 MB per pair at 480 x 854 (240 x 427 features, k = 10)
+
+
+@dataclass
+class LocalConfig:
+    """test_cfg keys of HRVanillaTracker.forward_test_backward_save_mem.  `temperature`, `topk` and `precede_frames` are read as
+    attributes there (:728, :754-755), with no defaults; R = neighbor_range // 2 (constructor, default 24); `with_norm` (:758, default True;
+    NOT the points path's `withnorm`); `with_first` (:742, default True).  hard_prop / norm_mask as the VanillaTracker mask path reads them.
+    pair_precision / pair_budget are not reference keys: "auto" | "f32" | "split" as TrackerConfig's, and the pair-list byte budget."""
+    temperature: float
+    topk: int
+    precede_frames: int
+    radius: int = 12
+    with_first: bool = True
+    with_norm: bool = True
+    hard_prop: bool = False
+    norm_mask: bool = True
+    pair_precision: str = "auto"
+    pair_budget: int = LOCAL_PAIR_BUDGET
+
+    @property
+    def mask(self) -> MaskSpec:
+        return MaskSpec(ry=self.radius, rx=self.radius)
+
+    @property
+    def window(self) -> int:
+        return 2 * self.radius + 1
+
+
+@dataclass
+class LocalPlan:
+    """Host-side schedule of one clip on the local window.  Row r = output frame r + 1."""
+    n_frames: int
+    pairs: List[Tuple[int, int]]                 # unique (query frame, key frame), grouped by row
+    slot_pair: List[List[int]]                   # row -> pair per key slot position (-1 pad)
+    slot_frame: List[List[int]]                  # row -> clip frame per key slot position (0 pad)
+    t_max: int
+    chunks: List[Tuple[int, int, int, int]]      # (row0, row1, pair0, pair1): rows and the pairs they own, one pair launch + one merge each
+    pair_bytes: int                              # bytes of one pair's lists
+    _dev: Dict[str, tuple] = field(default_factory=dict, repr=False)
+
+    def tables(self, dev):
+        """Per chunk (pairs int32 (n,4), slot_pair int32 (rows, t_max) relative to the chunk's first pair), and slot_frame (rows, t_max)."""
+        key = str(dev)
+        if key not in self._dev:
+            per = []
+            for r0, r1, p0, p1 in self.chunks:
+                rel = [[p - p0 if p >= 0 else -1 for p in row] for row in self.slot_pair[r0:r1]]
+                per.append((ops.make_pairs([(f, s, True) for f, s in self.pairs[p0:p1]], dev),
+                            torch.tensor(rel, dtype=torch.int32, device=dev).reshape(r1 - r0, self.t_max)))
+            sf = torch.tensor(self.slot_frame, dtype=torch.int32, device=dev).reshape(len(self.slot_frame), self.t_max)
+            self._dev[key] = (per, sf)
+        return self._dev[key]
+
+
+def plan_local_clip(n_frames: int, cfg: LocalConfig, HW: int) -> LocalPlan:
+    """Key slots of frame f (vanilla_tracker.py:728-745): frame 0 when with_first, then key_start .. f-1 with key_start =
+    max(0, f - precede_frames) -- duplicates kept (frame 1: [0, 0]), one pair for both.  Rows are chunked so that a chunk's pair lists
+    (HW * topk * 8 bytes per pair) stay within cfg.pair_budget."""
+    pre = int(cfg.precede_frames)
+    t_max = max(1, pre + (1 if cfg.with_first else 0))
+    pair_bytes = HW * int(cfg.topk) * 8
+    pairs: List[Tuple[int, int]] = []
+    slot_pair, slot_frame, row_pairs = [], [], []
+    for f in range(1, n_frames):
+        ks = key_slots(f, 0, pre, cfg.with_first)
+        own: Dict[int, int] = {}
+        for kf in ks:
+            if kf not in own:
+                own[kf] = len(pairs)
+                pairs.append((f, kf))
+        row_pairs.append(len(own))
+        slot_pair.append([own[kf] for kf in ks] + [-1] * (t_max - len(ks)))
+        slot_frame.append(list(ks) + [0] * (t_max - len(ks)))
+    chunks, r0, p0, n = [], 0, 0, 0
+    for r, m in enumerate(row_pairs):
+        if m * pair_bytes > cfg.pair_budget:
+            raise ValueError(f"pair_budget={cfg.pair_budget} bytes holds less than one frame's {m} pair lists ({m * pair_bytes} bytes)")
+        if (n + m) * pair_bytes > cfg.pair_budget:
+            chunks.append((r0, r, p0, p0 + n))
+            r0, p0, n = r, p0 + n, 0
+        n += m
+    if row_pairs:
+        chunks.append((r0, len(row_pairs), p0, p0 + n))
+    return LocalPlan(n_frames, pairs, slot_pair, slot_frame, t_max, chunks, pair_bytes)
+
+
+def local_route(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig) -> str:
+    """'f16x3' (fgvc_pair_topk_f16x3 on split_f16x2 rows) where ops.split_path_ok holds, else 'f32'; an int16 bank IS split_f16x2 rows."""
+    if cfg.pair_precision not in ("auto", "f32", "split"):
+        raise ValueError(f"pair_precision={cfg.pair_precision!r}")
+    ok = ops.split_path_ok(feats_hwc.shape[-1], Hf, Wf, cfg.topk, cfg.with_norm, None, cfg.mask, True)
+    if feats_hwc.dtype == torch.int16 or cfg.pair_precision == "split":
+        if not ok:
+            raise ValueError("the f16x3 local window needs normalised 256-channel rows, topk <= 10 and a window within the kernel's block list")
+        return "f16x3"
+    return "f16x3" if (ok and cfg.pair_precision == "auto") else "f32"
+
+
+def run_local_affinity(feats_hwc: torch.Tensor, Hf: int, Wf: int, plan: LocalPlan, cfg: LocalConfig,
+                       stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Every row's top-k over its slots' windows: idx (rows, HW, k) int32 = slot position * L^2 + tap, logit, weight.
+    feats_hwc (T, HW, C) f32 rows (L2-normalised iff cfg.with_norm), or their split_f16x2 form (T, HW, 2, 256) int16; a f32 bank on the
+    f16x3 route is split ONCE here.  `stats`: receives 'route', 'chunks' and 'workspace_bytes' (the largest chunk's pair lists)."""
+    dev, HW, k, R = feats_hwc.device, Hf * Wf, int(cfg.topk), int(cfg.radius)
+    rows = len(plan.slot_pair)
+    idx = torch.empty((rows, HW, k), device=dev, dtype=torch.int32)
+    logit = torch.empty((rows, HW, k), device=dev, dtype=torch.float32)
+    weight = torch.empty_like(logit)
+    route = local_route(feats_hwc, Hf, Wf, cfg)
+    if route == "f16x3":
+        bank = feats_hwc if feats_hwc.dtype == torch.int16 else ops.split_f16x2(feats_hwc)
+        pair_fn = lambda prs: ops.pair_topk_split(bank, bank, prs, Hf, Wf, Hf, Wf, cfg.mask, k, validate=False, all_masked=True, fmt="f16")
+    else:
+        pair_fn = lambda prs: ops.pair_topk(feats_hwc, feats_hwc, prs, Hf, Wf, Hf, Wf, cfg.mask, k, validate=False)
+    per, _ = plan.tables(dev)
+    for (r0, r1, p0, p1), (prs, sp) in zip(plan.chunks, per):
+        pidx, pscore = pair_fn(prs)
+        ops.local_merge_plan(pidx, pscore, sp, Hf, Wf, R, k, float(cfg.temperature), out=(idx[r0:r1], logit[r0:r1], weight[r0:r1]))
+        del pidx, pscore
+    if stats is not None:
+        stats.update(route=route, chunks=len(plan.chunks),
+                     workspace_bytes=max((p1 - p0) * plan.pair_bytes for _, _, p0, p1 in plan.chunks) if plan.chunks else 0)
+    return idx, logit, weight
+
+
+def _local_sweep(bank: torch.Tensor, soft: torch.Tensor, plan: LocalPlan, idx, weight, Hf: int, Wf: int, cfg: LocalConfig) -> None:
+    """Frames 1.. in order: soft[f] = top-k window weights x the label bank of the row's slot frames; bank[f] = one_hot(argmax) of it under
+    hard_prop (soft may be bank)."""
+    _, slot_frame = plan.tables(bank.device)
+    for f in range(1, plan.n_frames):
+        ops.propagate_topk(bank, slot_frame[f - 1], idx[f - 1], weight[f - 1], Hf, Wf, Hf, Wf, window_L=cfg.window, out=soft[f])
+        if cfg.hard_prop:
+            ops.seg_hard_onehot(soft[f], out=bank[f])
+
+
+def propagate_masks_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
+                          out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
+                          events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """propagate_masks (same arguments, outputs, one host read of C, `events`) on HRVanillaTracker's own affinity.  The feature grid is
+    whatever the encoder made of the padded frame: (Hf, Wf) need not divide (hp, wp).  `stats_out`: the dense path's refining-merge
+    counters have no counterpart here; nothing is appended.  `affinity_stats`: run_local_affinity's `stats`."""
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    hp, wp = seg_map.shape
+    lw, uw, lh, uh = pad
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    rec("labels")
+    C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
+    bank = torch.zeros((T, Hf * Wf, C), device=dev, dtype=torch.float32)
+    ops.seg_onehot_labels(seg_map, Hf, Wf, C, out=bank[0])
+    rec("affinity")
+    plan = plan_local_clip(T, cfg, Hf * Wf)
+    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
+    rec("propagation")
+    soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
+    _local_sweep(bank, soft, plan, idx, weight, Hf, Wf, cfg)
+    rec("readout")
+    masks = torch.empty((T, *out_shape), device=dev, dtype=torch.uint8)
+    if T > 1:
+        ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[1:])
+    ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]      # frame 0: the unpadded map, nearest-resized (:708-711)
+    masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
+    rec("end")
+    return masks
+
+
+def propagate_heatmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                             out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
+                             events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """propagate_heatmaps (same arguments and (2, K, T) f64 output; frame 0 = the padded map, not unpadded) on HRVanillaTracker's own
+    affinity.  `stats_out`, `affinity_stats`: as propagate_masks_local."""
+    if cfg.hard_prop:
+        raise NotImplementedError("propagate_heatmaps_local: hard_prop with soft labels")
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    K = heat.shape[0]
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    rec("labels")
+    bank = torch.zeros((T, Hf * Wf, K), device=dev, dtype=torch.float32)
+    ops.seg_soft_labels(heat, map_pad, Hf, Wf, out=bank[0])
+    rec("affinity")
+    plan = plan_local_clip(T, cfg, Hf * Wf)
+    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
+    rec("propagation")
+    _local_sweep(bank, bank, plan, idx, weight, Hf, Wf, cfg)
+    rec("readout")
+    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    rec("end")
+    return coords

@@ -15,7 +15,8 @@ from ..ops import MaskSpec
 
 __all__ = [
     "NeighborMask", "spatial_neighbor", "masked_attention_efficient", "masked_attention_efficient_v2",
-    "masked_attention", "masked_attention_efficient_c2f", "masked_attention_efficient_correlation_v2",
+    "masked_attention", "masked_attention_efficient_c2f", "masked_attention_efficient_correlation",
+    "masked_attention_efficient_correlation_v2",
     "compute_affinity", "propagate", "non_local_attention", "local_square_attention", "coords_grid", "cat", "video2images",
     "images2video", "bilinear_sample",
 ]
@@ -364,3 +365,13 @@ def masked_attention_efficient_correlation_v2(query_frame, key_frames, value, ra
     out = ops.propagate_topk(labels, torch.arange(K, dtype=torch.int32, device=query.device), idx, weight, H, W, H, W,
                              window_L=2 * radius + 1)
     return out.t().reshape(1, P, H, W).to(query.dtype)
+
+
+def masked_attention_efficient_correlation(query_frame, key_frames, value, radius, corr_infer, feat_extractor, temperature=1, topk=None,
+                                           normalize=True, sstep=32, tstep=5):
+    """local_attention.py:883-1006, the operator HRVanillaTracker.forward_test_backward_save_mem calls: mmcv.ops.Correlation over the
+    (2R+1)^2 window (zero padded: an outside tap scores 0 and carries value 0), top-k over K*(2R+1)^2, temperature after the top-k.  The
+    same operator as the _v2 form (whose part_unfold samples the keys at integer taps); `corr_infer`, `sstep`, `tstep` are accepted and
+    unused."""
+    return masked_attention_efficient_correlation_v2(query_frame, key_frames, value, radius, corr_infer, feat_extractor,
+                                                     temperature=temperature, topk=topk, normalize=normalize, sstep=sstep, tstep=tstep)

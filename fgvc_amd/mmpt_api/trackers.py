@@ -270,6 +270,10 @@ class VanillaTracker(BaseTracker):
                 raise ValueError(f"ref_seg_map: negative id {lo}")
         if not imgs.is_cuda:
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
+        return self._seg_index_maps(imgs, ref_seg_map, img_meta)
+
+    def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
+        """forward_test_seg past its refusals: index maps -> [ (T, h0, w0) float64 ]."""
         cfg = self.engine_config()
         h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
@@ -291,7 +295,7 @@ class VanillaTracker(BaseTracker):
         float32 | float64, padded by its OWN pad_divide_by (vanilla_tracker.py:672).  Returns a list over the batch of one ndarray
         (2, K, T) float64 = img2coord of the propagated maps at img_meta[0]['original_shape'] (:814-818).  Frame 0 is the padded map
         resized to that shape, NOT unpadded (:712-716): the reference's quirk, kept."""
-        if self.engine_config().hard_prop:
+        if self._label_config().hard_prop:
             raise NotImplementedError("fgvc_amd: hard_prop=True with soft labels (the reference's F.one_hot without num_classes drops the last "
                                       "channel when it never wins, and the next frame's cat then fails, vanilla_tracker.py:762-768)")
         if imgs.shape[0] != 1 or imgs.shape[1] != 1 or heat.shape[0] != 1:
@@ -306,6 +310,14 @@ class VanillaTracker(BaseTracker):
         heat = heat[0].to(imgs.device).contiguous()
         if not bool(torch.isfinite(heat).all()):
             raise ValueError("ref_seg_map: the soft labels hold a non-finite value")
+        return self._seg_heatmaps(imgs, heat, img_meta)
+
+    def _label_config(self):
+        """The configuration the label-map path propagates with (its `hard_prop` is read before the heat-map path's other checks)."""
+        return self.engine_config()
+
+    def _seg_heatmaps(self, imgs, heat, img_meta):
+        """_forward_test_heatmap past its refusals: heat (K, hm, wm) on the device -> [ (2, K, T) float64 ]."""
         cfg = self.engine_config()
         h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
@@ -440,8 +452,70 @@ class HRVanillaTracker(VanillaTracker):
             coords.append(coord)
         return list(torch.stack(coords, -1).cpu().numpy().astype(float))              # :642-660
 
+    # ---- label maps: forward_test_backward_save_mem (vanilla_tracker.py:663-830) on the local window ----------------------------------
+    def _label_config(self) -> engine.LocalConfig:
+        """The keys forward_test_backward_save_mem reads, as it reads them: `temperature`, `topk`, `precede_frames` as attributes with no
+        default (:728, :754-755: a config without one raises), `with_norm` (:758, default True; the points path's `withnorm` is not read),
+        `with_first` (:742, default True), R = neighbor_range // 2 (constructor).  `sstep` / `tstep` (:756-757), `step`, `mask_mode` and
+        `with_first_neighbor` are accepted and change nothing.  hard_prop / norm_mask as VanillaTracker's mask path reads them;
+        pair_precision ("auto" | "f32" | "split") and pair_budget (bytes of pair lists at once) are extension keys."""
+        tc = self.test_cfg if isinstance(self.test_cfg, ConfigDict) else ConfigDict(self.test_cfg)      # (a plain dict: the same keys)
+        g = tc.get
+        return engine.LocalConfig(temperature=float(tc.temperature), topk=int(tc.topk), precede_frames=int(tc.precede_frames),
+                                  radius=int(self.infer_radius), with_first=bool(g("with_first", True)), with_norm=bool(g("with_norm", True)),
+                                  hard_prop=bool(g("hard_prop", False)), norm_mask=bool(g("norm_mask", True)),
+                                  pair_precision=g("pair_precision", "auto"), pair_budget=int(g("pair_budget", engine.LOCAL_PAIR_BUDGET)))
+
+    def _label_feats(self, frames: torch.Tensor):
+        """frames (T,3,hp,wp) padded -> f32 rows (T, HfWf, C'), L2-normalised iff `with_norm`, Hf, Wf: every frame encoded once (the reference
+        re-encodes the key frames at every query frame, local_attention.py:918, :947: the same features)."""
+        if self.head is not None or self.stride_sample:
+            raise NotImplementedError("fgvc_amd: HRVanillaTracker's label maps are encoded by the backbone alone (feat_extractor=self.backbone, "
+                                      "vanilla_tracker.py:753); a head or stride_sample is not supported there")
+        return self.get_feats_hwc(frames, split=False)
+
+    def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
+        """Index maps: the pad unit is the tracker's own `stride` (vanilla_tracker.py:671-672), not the encoder's output stride; the feature
+        grid is whatever the encoder makes of the padded frame."""
+        cfg = self._label_config()
+        h, w = imgs.shape[-2:]
+        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
+        _, pad = engine.pad_divide_by(h, w, self.stride)
+        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
+        feats, Hf, Wf = self._label_feats(frames)
+        self.label_stats = {}                                        # the affinity's route, chunks and pair-list bytes of this call
+        masks = engine.propagate_masks_local(feats, Hf, Wf, seg, pad, (h0, w0), cfg, affinity_stats=self.label_stats)
+        self._refine_stats = None
+        self._check_kernels()
+        return [masks.cpu().numpy().astype("float64")]
+
+    def _seg_heatmaps(self, imgs, heat, img_meta):
+        """Heat maps (coords=True): frames and map each padded by pad_divide_by with the tracker's `stride` (:671-672)."""
+        cfg = self._label_config()
+        h, w = imgs.shape[-2:]
+        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
+        _, pad = engine.pad_divide_by(h, w, self.stride)
+        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], self.stride)
+        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)
+        feats, Hf, Wf = self._label_feats(frames)
+        self.label_stats = {}
+        coords = engine.propagate_heatmaps_local(feats, Hf, Wf, heat, map_pad, (h0, w0), cfg, affinity_stats=self.label_stats)
+        self._refine_stats = None
+        self._check_kernels()
+        return [coords.cpu().numpy()]
+
     @torch.no_grad()
-    def forward_test(self, rgbs, query_points, trajectories, visibilities, **kw):
+    def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,
+                     iteration=None, imgs=None, ref_seg_map=None, img_meta=None, **kw):
+        """Points: rgbs / query_points / trajectories / visibilities (below).  Label maps (imgs= / ref_seg_map= / img_meta=, what the
+        reference's mask and pose datasets pass): forward_test_seg, on this tracker's local-window affinity."""
+        if imgs is not None or ref_seg_map is not None or img_meta is not None:
+            if rgbs is not None or query_points is not None:
+                raise TypeError("HRVanillaTracker.forward_test: give either rgbs= / query_points= (points) or imgs= / ref_seg_map= / img_meta= (masks)")
+            return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        if rgbs is None or query_points is None:
+            raise TypeError("HRVanillaTracker.forward_test: missing rgbs / query_points")
         if not self.test_cfg.get("with_first", False):
             return self.forward_test_main(rgbs, query_points, trajectories, visibilities)
         # inherited regrouping (vanilla_tracker.py:246-299): one sweep per distinct query time over the tail of the clip; the

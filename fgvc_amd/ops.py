@@ -667,6 +667,26 @@ def local_corr_topk(qfeat: torch.Tensor, kfeat: torch.Tensor, H: int, W: int, R:
     return idx, logit, weight
 
 
+def local_merge_plan(pair_idx: torch.Tensor, pair_score: torch.Tensor, slot_pair: torch.Tensor, H: int, W: int, R: int, topk: int,
+                     temperature: float, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """The merge of local_corr_topk() for many output frames in one launch (fgvc_local_merge_plan_f32): pair_idx / pair_score
+    (n_pairs, HW, topk) from pair_topk() / pair_topk_split() under MaskSpec(ry=R, rx=R), slot_pair int32 (n_rows, max_slots) = pair of
+    key slot j of row r (-1: none).  Returns idx (n_rows, HW, topk) int32 = j*(2R+1)^2 + tap, logit, weight -- or writes `out`."""
+    pair_idx, pair_score = _chk(pair_idx, torch.int32, "pair_idx"), _chk(pair_score, torch.float32, "pair_score")
+    slot_pair = _chk(slot_pair, torch.int32, "slot_pair")
+    assert pair_idx.shape == pair_score.shape and pair_idx.shape[1:] == (H * W, topk) and slot_pair.dim() == 2
+    n_rows, max_slots = slot_pair.shape
+    if out is None:
+        idx = torch.empty((n_rows, H * W, topk), device=pair_idx.device, dtype=torch.int32)
+        logit = torch.empty((n_rows, H * W, topk), device=pair_idx.device, dtype=torch.float32)
+        out = (idx, logit, torch.empty_like(logit))
+    for t, dt in zip(out, (torch.int32, torch.float32, torch.float32)):
+        assert t.is_contiguous() and t.dtype == dt and t.shape == (n_rows, H * W, topk) and t.device == pair_idx.device
+    _lib.call("fgvc_local_merge_plan_f32", _ptr(pair_idx), _ptr(pair_score), pair_idx.shape[0], _ptr(slot_pair), n_rows, max_slots, H, W,
+              R, topk, float(temperature), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream(pair_idx))
+    return out
+
+
 def topk_coord(idx: torch.Tensor, weight: torch.Tensor, H: int, W: int, R: int, scale: int) -> torch.Tensor:
     """A7 get_coord: (HW,k) window lists of ONE key slot -> (HW,2) expected (x,y) image coordinates."""
     idx, weight = _chk(idx, torch.int32, "idx"), _chk(weight, torch.float32, "weight")

@@ -296,6 +296,17 @@ int fgvc_local_corr_topk_f16x3(const uint16_t* qsplit, const uint16_t* ksplit, c
                                int32_t* pair_idx_ws, float* pair_score_ws,
                                int32_t* idx_out, float* logit_out, float* weight_out, void* stream);
 
+/* The merge step of fgvc_local_corr_topk_* for every output frame of a planned clip in one launch (HRVanillaTracker's label maps,
+ * vanilla_tracker.py:663-830 with masked_attention_efficient_correlation, local_attention.py:883-1006).
+ *   pair_idx / pair_score [n_pairs][H*W][topk]: lists of fgvc_pair_topk_{f32,f16x3} with the square window |dy|,|dx| <= R;
+ *   slot_pair [n_rows][max_slots] int32 (device): pair feeding key slot j of row r, -1 = no slot (ids outside [0, n_pairs) too).
+ *   idx_out / logit_out / weight_out [n_rows][H*W][topk]: idx = j*(2R+1)^2 + (dy+R)*(2R+1) + (dx+R), zero-padded taps added per
+ *   slot, logit = score / temperature after the top-k, weight = softmax.  A row equals fgvc_local_corr_topk_* on the same lists bit
+ *   for bit; a pair that fills two slot positions gives two candidate sets.  No atomics, no workspace. */
+int fgvc_local_merge_plan_f32(const int32_t* pair_idx, const float* pair_score, int n_pairs, const int32_t* slot_pair, int n_rows,
+                              int max_slots, int H, int W, int R, int topk, float temperature, int32_t* idx_out, float* logit_out,
+                              float* weight_out, void* stream);
+
 /* ---- A7 get_coord (vanilla_tracker.py:445-488): expected image coordinate of every query pixel under the top-k
  * window weights of fgvc_local_corr_topk_f32 with ONE key slot (taps outside the grid contribute (0,0), like the
  * zero-padded F.unfold of the coordinate grid).  idx/weight [H*W][topk] -> out [H*W][2] = (x, y) in image pixels

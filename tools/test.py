@@ -3,6 +3,7 @@
 
     python tools/test.py CONFIG --task davis [--checkpoint CKPT] [--videos 4 --frames 8 --size 256 256]
     python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
+    python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -50,6 +51,8 @@ def main():
     ap.add_argument("--pose-form", choices=["points", "heatmap"], default="points",
                     help="jhmdb / badja: 'points' tracks the frame-0 joints as query points; 'heatmap' propagates the reference's first-frame "
                          "Gaussian maps and reads joints out of them (test_cfg.coords=True)")
+    ap.add_argument("--eval-arc", default=None, help="tracker class to build, overriding the config's eval_arc (e.g. HRVanillaTracker: the "
+                                                     "local-window affinity for masks, heat maps and points)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -88,7 +91,7 @@ def main():
     heatmap = a.task in ("jhmdb", "badja") and a.pose_form == "heatmap"
     if heatmap:
         test_cfg = dict(test_cfg, coords=True)       # the reference's pose configs: 4-D first-frame maps read out by img2coord
-    model_cfg = dict(type=cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
+    model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
             model_cfg["backbone"][k] = test_cfg[k]
