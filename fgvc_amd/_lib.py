@@ -99,6 +99,7 @@ SIGNATURES = {
     "fgvc_seg_soft_labels_f64": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_heatmap_coords_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fgvc_heatmap_coords_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "fgvc_softmap_readout_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

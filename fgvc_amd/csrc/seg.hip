@@ -290,12 +290,20 @@ size_t seg_readout_workspace_bytes(int n, int C) { return (size_t)n * SEG_NB * C
 // ------------------------------------------------------------------------------------------
 namespace {
 
+__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
 // bilinear (align_corners=False) of the zero-padded map at output pixel (oy, ox), in the map's dtype T as F.interpolate computes it
-// (area_pixel_compute_scale / _source_index in accscalar_t = T; the padded grid is the interpolation's input)
+// (area_pixel_compute_scale / _source_index in accscalar_t = T; the padded grid is the interpolation's input).
+// The rounding sequence is part of the source: every kernel that calls this (bank row 0, the coordinate read-out's frame 0, the map
+// read-out's frame 0) must produce the same bits for the same pixel, and with contraction left to the compiler each instance fused
+// a * b + c differently.  Contraction is off in this body and the fused operations are written out: the source coordinate and each
+// of the three interpolations are one multiply and one fma.
 template <typename T>
 __device__ __forceinline__ T padded_bilinear(const T* __restrict__ m, int hm, int wm, int top, int left, int hp, int wp, T sy, T sx,
                                              int oy, int ox) {
-  T ry = sy * ((T)oy + (T)0.5) - (T)0.5, rx = sx * ((T)ox + (T)0.5) - (T)0.5;
+#pragma clang fp contract(off)
+  T ry = fma_t(sy, (T)oy + (T)0.5, (T)-0.5), rx = fma_t(sx, (T)ox + (T)0.5, (T)-0.5);
   ry = ry < (T)0 ? (T)0 : ry;
   rx = rx < (T)0 ? (T)0 : rx;
   const int y0 = imin((int)ry, hp - 1), x0 = imin((int)rx, wp - 1);
@@ -306,7 +314,9 @@ __device__ __forceinline__ T padded_bilinear(const T* __restrict__ m, int hm, in
     const int yy = y - top, xx = x - left;
     return (yy >= 0 && yy < hm && xx >= 0 && xx < wm) ? m[(size_t)yy * wm + xx] : (T)0;
   };
-  return hy * (hx * at(y0, x0) + lx * at(y0, x1)) + ly * (hx * at(y1, x0) + lx * at(y1, x1));
+  const T r0 = fma_t(hx, at(y0, x0), lx * at(y0, x1));
+  const T r1 = fma_t(hx, at(y1, x0), lx * at(y1, x1));
+  return fma_t(hy, r0, ly * r1);
 }
 
 // top-5 of a band: value descending, the higher flat index first among equal values (post.hip TopKHi, np.argsort's tail)
@@ -515,6 +525,186 @@ size_t heatmap_workspace_bytes(int T, int K) {
   return (size_t)T * K * HM_BANDS * (HM_K * sizeof(double) + HM_K * sizeof(int) + sizeof(double));
 }
 
+// ------------------------------------------------------------------------------------------
+// The propagated soft maps themselves (coords=False with a 4-D map, :770-784, :803): the field the coordinate read-out scans, written
+// channel-first.  A transpose: the bank is channel-last, the output has w0 contiguous.  A workgroup owns SM_TY rows x SM_TX columns of
+// one frame for a group of up to SM_KG channels.  It stages the feature-grid footprint of that tile in LDS, one plane per channel
+// ([kg][rows][cols], plane stride odd), from channel-contiguous loads (16 B where K, the group and the pointer allow it); then lane
+// (q, cl) evaluates 4 consecutive x (quad q of the tile's 16) of one (row, channel) per step, cl-strided over the tile's rows x channels,
+// with field_value on its channel's plane: the same taps, weights and fmaf chain as heatmap_band_kernel.  16 lanes write one 256-byte
+// run of a row.  A footprint beyond SM_CAP floats (an output much smaller than the feature grid) is read from the bank directly.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int SM_BLOCK = 256;
+constexpr int SM_TX = 64;       // tile columns: 16 quads of 4
+constexpr int SM_TY = 8;        // tile rows
+constexpr int SM_KG = 16;       // channels per group
+constexpr int SM_CAP = 6144;    // floats of LDS for the footprint (24 KiB)
+
+// native vectors: one store instruction each (a struct of four floats is split into scalars and merged across the branches below)
+typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
+typedef float sm_f32x2 __attribute__((ext_vector_type(2)));
+typedef double sm_f64x2 __attribute__((ext_vector_type(2)));
+
+// 4 consecutive values at dst (n < 4 at the end of a row): the widest stores the address allows
+__device__ __forceinline__ void store_quad(float* __restrict__ dst, const float (&v)[4], int n) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
+  if (n == 4 && (a & 15) == 0) {
+    *reinterpret_cast<sm_f32x4*>(dst) = sm_f32x4{v[0], v[1], v[2], v[3]};
+  } else if (n == 4 && (a & 7) == 0) {
+    *reinterpret_cast<sm_f32x2*>(dst) = sm_f32x2{v[0], v[1]};
+    *reinterpret_cast<sm_f32x2*>(dst + 2) = sm_f32x2{v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < n) dst[j] = v[j];
+  }
+}
+__device__ __forceinline__ void store_quad(double* __restrict__ dst, const double (&v)[4], int n) {
+  if (n == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    *reinterpret_cast<sm_f64x2*>(dst) = sm_f64x2{v[0], v[1]};
+    *reinterpret_cast<sm_f64x2*>(dst + 2) = sm_f64x2{v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < n) dst[j] = v[j];
+  }
+}
+
+}  // namespace
+
+// frames >= 1.  grid (x tiles * y tiles, channel groups, frames); out points at the first of the frames written
+template <bool COMPOSED, typename OUT>
+__global__ __launch_bounds__(SM_BLOCK) void softmap_kernel(const float* __restrict__ bank, HeatGeom g, int f_first, int xtiles,
+                                                           OUT* __restrict__ out) {
+  constexpr int N = COMPOSED ? 4 : 2;
+  __shared__ __attribute__((aligned(16))) float foot[SM_CAP];
+  __shared__ Taps<COMPOSED> sty[SM_TY];
+  const int tid = threadIdx.x;
+  const int tile_y = blockIdx.x / xtiles, tile_x = blockIdx.x - tile_y * xtiles;
+  const int y0 = tile_y * SM_TY, x0 = tile_x * SM_TX;
+  const int ny = imin(SM_TY, g.h0 - y0), x_last = imin(x0 + SM_TX, g.w0) - 1;
+  const int k0 = blockIdx.y * SM_KG, kg = imin(SM_KG, g.K - k0);
+  const int f = f_first + blockIdx.z;
+  const float* lab = bank + (size_t)f * g.Hf * g.Wf * g.K + k0;
+  // the footprint: seg_src_index is monotone in its output coordinate, so the first tap of the first row / column and the last tap of
+  // the last bound every tap of the tile
+  Taps<COMPOSED> lo, hi;
+  lo.make(y0, g.s2y, g.hm, g.top, g.s1y, g.Hf);
+  hi.make(y0 + ny - 1, g.s2y, g.hm, g.top, g.s1y, g.Hf);
+  const int fy0 = lo.t[0], nrows = hi.t[N - 1] - fy0 + 1;
+  lo.make(x0, g.s2x, g.wm, g.left, g.s1x, g.Wf);
+  hi.make(x_last, g.s2x, g.wm, g.left, g.s1x, g.Wf);
+  const int fx0 = lo.t[0], ncols = hi.t[N - 1] - fx0 + 1;
+  const int plane = (nrows * ncols) | 1;
+  const bool staged = plane * kg <= SM_CAP;   // the same in every lane
+  if (staged) {
+    const int npix = nrows * ncols;
+    if ((g.K & 3) == 0 && (kg & 3) == 0 && (reinterpret_cast<uintptr_t>(bank) & 15) == 0) {
+      const int c4n = kg >> 2;
+      for (int e = tid; e < npix * c4n; e += SM_BLOCK) {
+        const int pix = e / c4n, c4 = e - pix * c4n;
+        const int r = pix / ncols, c = pix - r * ncols;
+        const float4 v = *reinterpret_cast<const float4*>(lab + ((size_t)(fy0 + r) * g.Wf + fx0 + c) * g.K + 4 * c4);
+        float* d = foot + (4 * c4) * plane + pix;
+        d[0] = v.x; d[plane] = v.y; d[2 * plane] = v.z; d[3 * plane] = v.w;
+      }
+    } else {
+      for (int e = tid; e < npix * kg; e += SM_BLOCK) {
+        const int pix = e / kg, c = e - pix * kg;
+        const int r = pix / ncols, cc = pix - r * ncols;
+        foot[c * plane + pix] = lab[((size_t)(fy0 + r) * g.Wf + fx0 + cc) * g.K + c];
+      }
+    }
+  }
+  // row taps of the tile, offsets as field_value wants them: LDS rows of ncols, or bank rows of Wf * K
+  if (tid < ny) {
+    Taps<COMPOSED> t;
+    t.make(y0 + tid, g.s2y, g.hm, g.top, g.s1y, g.Hf);
+#pragma unroll
+    for (int i = 0; i < N; ++i) t.t[i] = staged ? (t.t[i] - fy0) * ncols : t.t[i] * g.Wf * g.K;
+    sty[tid] = t;
+  }
+  const int q = tid & 15, cl = tid >> 4;
+  const int x = x0 + 4 * q;
+  Taps<COMPOSED> tx[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    tx[j].make(imin(x + j, g.w0 - 1), g.s2x, g.wm, g.left, g.s1x, g.Wf);
+#pragma unroll
+    for (int i = 0; i < N; ++i) tx[j].t[i] = staged ? tx[j].t[i] - fx0 : tx[j].t[i] * g.K;
+  }
+  __syncthreads();
+  const int n = imin(4, g.w0 - x);
+  if (n <= 0) return;
+  OUT* dst_f = out + ((size_t)blockIdx.z * g.K + k0) * g.h0 * g.w0 + x;
+  // one call per source so that the staged instance reads LDS with LDS instructions
+  auto run = [&](const float* __restrict__ base, int kstride) __attribute__((always_inline)) {
+    for (int c = cl; c < ny * kg; c += SM_BLOCK / 16) {
+      const int r = c / kg, k = c - r * kg;
+      const Taps<COMPOSED> ty = sty[r];
+      OUT v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = (OUT)field_value<COMPOSED>(base + k * kstride, ty, tx[j]);
+      store_quad(dst_f + ((size_t)k * g.h0 + y0 + r) * g.w0, v, n);
+    }
+  };
+  if (staged)
+    run(foot, plane);
+  else
+    run(lab, 1);
+}
+
+// frame 0: bilinear of the zero-padded input map straight to (h0, w0) in its own dtype, then rounded or widened to the output's.
+// The value is padded_bilinear's, whose rounding sequence is fixed in its source: the bits heatmap_band0_kernel scans.  The loop is that
+// kernel's (rows of a band, one pixel per lane, 256 consecutive x per step), the output dtype a run-time flag: one instance per map
+// dtype.  Frame 0 is 1 / T of the stack: dword stores.
+// grid (K, 1, nbands): one row per band up to 16384 rows, so that every lane has a few pixels only (the map is gathered through the caches)
+constexpr int SM_MAX_BANDS0 = 16384;
+template <typename T>
+__global__ __launch_bounds__(SM_BLOCK) void softmap0_kernel(const T* __restrict__ map, HeatGeom g, int out_f64, void* __restrict__ out) {
+  const int k = blockIdx.x, band = blockIdx.z;
+  const T* m = map + (size_t)k * g.hm * g.wm;
+  const T sy = (T)g.hp / (T)g.h0, sx = (T)g.wp / (T)g.w0;
+  const int rows = cdiv(g.h0, g.nbands);
+  const int y_lo = band * rows, y_hi = imin(g.h0, y_lo + rows);
+  const size_t base = (size_t)k * g.h0 * g.w0;
+  for (int y = y_lo; y < y_hi; ++y)
+    for (int x = threadIdx.x; x < g.w0; x += SM_BLOCK) {
+      const T v = padded_bilinear<T>(m, g.hm, g.wm, g.top, g.left, g.hp, g.wp, sy, sx, y, x);
+      const size_t o = base + (size_t)y * g.w0 + x;
+      if (out_f64)
+        static_cast<double*>(out)[o] = (double)v;
+      else
+        static_cast<float*>(out)[o] = (float)v;
+    }
+}
+
+template <typename OUT>
+static void softmap_launch(const float* bank, const void* map0, int map0_f64, const HeatGeom& g, int f_begin, int f_end, OUT* out,
+                           hipStream_t s) {
+  const size_t frame = (size_t)g.K * g.h0 * g.w0;
+  const int xtiles = cdiv(g.w0, SM_TX);
+  if (f_begin == 0) {
+    const dim3 grid0(g.K, 1, g.nbands);
+    const int f64 = sizeof(OUT) == 8;
+    if (map0_f64)
+      softmap0_kernel<double><<<grid0, SM_BLOCK, 0, s>>>(static_cast<const double*>(map0), g, f64, out);
+    else
+      softmap0_kernel<float><<<grid0, SM_BLOCK, 0, s>>>(static_cast<const float*>(map0), g, f64, out);
+  }
+  const int f_first = imax(f_begin, 1);
+  if (f_end > f_first) {
+    const dim3 grid(xtiles * cdiv(g.h0, SM_TY), cdiv(g.K, SM_KG), f_end - f_first);
+    OUT* dst = out + (size_t)(f_first - f_begin) * frame;
+    if (g.hm == g.h0 && g.wm == g.w0)
+      softmap_kernel<false, OUT><<<grid, SM_BLOCK, 0, s>>>(bank, g, f_first, xtiles, dst);
+    else
+      softmap_kernel<true, OUT><<<grid, SM_BLOCK, 0, s>>>(bank, g, f_first, xtiles, dst);
+  }
+}
+
 }  // namespace fgvc
 
 using namespace fgvc;
@@ -658,6 +848,31 @@ int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, i
   }
   heatmap_merge_kernel<<<cdiv((int)maps, 64), 64, 0, s>>>(part_v, part_i, part_sum, HM_BANDS, K, T, w0, f64_arith, coords);
   FGVC_CHECK_LAUNCH("fgvc_heatmap_coords_f32");
+  return FGVC_OK;
+}
+
+int fgvc_softmap_readout_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                             int wp, int top, int left, int h0, int w0, int f_begin, int f_end, int out_f64, void* out, void* stream) {
+  FGVC_REQUIRE(map0 && out && (bank || f_end <= 1), FGVC_ERR_INVALID_ARG, "fgvc_softmap_readout_f32: null pointer");
+  FGVC_REQUIRE(T >= 1 && T <= 65535 && Hf > 0 && Wf > 0 && K >= 1 && K <= 256 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_softmap_readout_f32: bad shape (1 <= K <= 256, 1 <= T <= 65535)");
+  FGVC_REQUIRE(0 <= f_begin && f_begin < f_end && f_end <= T, FGVC_ERR_INVALID_ARG,
+               "fgvc_softmap_readout_f32: bad frame range [%d, %d) of %d frames (0 <= f_begin < f_end <= T)", f_begin, f_end, T);
+  FGVC_REQUIRE(hm > 0 && wm > 0 && top >= 0 && left >= 0 && top + hm <= hp && left + wm <= wp, FGVC_ERR_INVALID_ARG,
+               "fgvc_softmap_readout_f32: the map must lie inside the padded frame");
+  FGVC_REQUIRE((long long)h0 * w0 < (1ll << 31) && (long long)Hf * Wf * K < (1ll << 31) &&
+                   (long long)cdiv(w0, SM_TX) * cdiv(h0, SM_TY) < (1ll << 31),
+               FGVC_ERR_UNSUPPORTED, "fgvc_softmap_readout_f32: h0*w0 or Hf*Wf*K out of range (< 2^31)");
+  HeatGeom g;
+  g.K = K; g.Hf = Hf; g.Wf = Wf; g.hm = hm; g.wm = wm; g.hp = hp; g.wp = wp; g.top = top; g.left = left; g.h0 = h0; g.w0 = w0;
+  g.nbands = imin(h0, SM_MAX_BANDS0);   // frame 0's row bands
+  g.s1y = (float)Hf / (float)hp; g.s1x = (float)Wf / (float)wp;
+  g.s2y = (float)hm / (float)h0; g.s2x = (float)wm / (float)w0;
+  if (out_f64)
+    softmap_launch<double>(bank, map0, map0_f64, g, f_begin, f_end, static_cast<double*>(out), (hipStream_t)stream);
+  else
+    softmap_launch<float>(bank, map0, map0_f64, g, f_begin, f_end, static_cast<float*>(out), (hipStream_t)stream);
+  FGVC_CHECK_LAUNCH("fgvc_softmap_readout_f32");
   return FGVC_OK;
 }
 

@@ -356,6 +356,40 @@ def jhmdb_evaluate_heatmap(model, dataset: "JhmdbPoses"):
     return metrics.jhmdb_pck(preds, gts)
 
 
+def img2coord_maps(maps: np.ndarray, topk: int = 5) -> np.ndarray:
+    """img2coord (vanilla_tracker.py:172-191) of a returned stack (T, K, h0, w0) -> (2, K, T) float64, with the read-out kernel's tie rule
+    (fgvc_heatmap_coords_f32): the top 5 by value, the higher flat index first among equals (a stable ascending argsort's tail; numpy's
+    default sort leaves that order open), normalised in the stack's dtype, coordinates summed in float64 in ascending order of value.
+    A map whose float64 sum is 0 gives (-1, -1) (the reference sums in the stack's dtype: the same test for non-negative maps)."""
+    maps = np.asarray(maps)
+    T, K, h, w = maps.shape
+    coords = np.zeros((2, K, T), dtype=np.float64)
+    for f in range(T):                                                    # per frame: the argsort's indices are 8 bytes per value
+        flat = maps[f].reshape(K, -1)
+        order = np.argsort(flat, axis=-1, kind="stable")[:, -topk:]
+        v = np.take_along_axis(flat, order, axis=-1)
+        v = v / (np.sum(v, keepdims=True, axis=-1) + maps.dtype.type(1e-9))
+        coords[0, :, f] = np.sum((order % w) * v, axis=-1)
+        coords[1, :, f] = np.sum((order // w) * v, axis=-1)
+        coords[:, flat.sum(axis=-1, dtype=np.float64) == 0, f] = -1
+    return coords
+
+
+class MapsAsCoords:
+    """A tracker whose test_cfg has return_maps=True, presented as one with coords=True: each call returns [img2coord_maps(maps)], so that
+    jhmdb_evaluate_heatmap / badja_evaluate_heatmap score it unchanged.  `on_maps(i, maps)` sees the i-th call's (T, K, h0, w0) array."""
+
+    def __init__(self, model, on_maps=None):
+        self.model, self.on_maps, self.calls = model, on_maps, 0
+
+    def __call__(self, **kw):
+        maps = self.model(**kw)[0]
+        if self.on_maps is not None:
+            self.on_maps(self.calls, maps)
+        self.calls += 1
+        return [img2coord_maps(maps)]
+
+
 # SMAL joints BADJA annotates (badja_dataset.py:71-82 `SMALJointInfo.annotated_classes`): 20 of the 37 per frame
 BADJA_ANNOTATED = (8, 9, 10, 12, 13, 14, 15, 18, 19, 20, 22, 23, 24, 25, 28, 31, 32, 33, 35, 36)
 

@@ -453,6 +453,19 @@ def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Te
     the map's size, :672); out_shape = (h0, w0).  Returns (2, K, T) float64 on the device = img2coord of the stacked maps (:814-818).
     K is the map's first dimension: no host read.  The propagation is the mask path's soft one with P = K (no min-max normalisation,
     :785 applies to index maps only).  `events`: as propagate_masks."""
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    bank = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels=channels, stats_out=stats_out, events=events)
+    rec("readout")
+    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    rec("end")
+    return coords
+
+
+def propagate_soft_bank(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                        cfg: TrackerConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
+                        events: Optional[dict] = None) -> torch.Tensor:
+    """The part propagate_heatmaps and propagate_softmaps share: first-frame labels, affinity and the sweep.  Returns the label bank
+    (T, HfWf, K) f32 both read-outs start from.  Records the events 'labels', 'affinity', 'propagation'."""
     T, dev = feats_hwc.shape[0], feats_hwc.device
     K = heat.shape[0]
     rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
@@ -468,10 +481,55 @@ def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Te
     for f in range(1, T):
         row = tk.row(plan.out_rows[(0, f)])
         ops.propagate_topk(bank, tk.slot_frame[row], tk.idx[row], tk.weight[row], Hf, Wf, Hf, Wf, out=bank[f])
+    return bank
+
+
+def propagate_softmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                       out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
+                       stats_out: Optional[list] = None, events: Optional[dict] = None,
+                       frames: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """propagate_heatmaps with the maps themselves as the result (the reference's return value without `coords`, :770-784, :800-803):
+    (T, K, h0, w0) on the device, or the rows `frames` = (f_begin, f_end) of it, float64 iff `heat` is float64 (np.stack of a float64
+    frame 0 with float32 later frames).  Same bank, same field as the coordinate read-out: ops.softmap_readout writes what
+    ops.heatmap_coords scans.  The whole stack is T K h0 w0 values: for a host-bound result see softmaps_to_host."""
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    bank = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels=channels, stats_out=stats_out, events=events)
     rec("readout")
-    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=frames)
     rec("end")
-    return coords
+    return maps
+
+
+MAPS_BUDGET = 512 << 20           # bytes of full-resolution maps held on the device at once by softmaps_to_host
+
+
+def plan_map_chunks(n_frames: int, K: int, out_shape: Tuple[int, int], itemsize: int, budget: int = MAPS_BUDGET) -> List[Tuple[int, int]]:
+    """Frame ranges [(f_begin, f_end), ...] covering 0 .. n_frames, each of at most `budget` bytes of (K, h0, w0) maps."""
+    frame_bytes = int(K) * int(out_shape[0]) * int(out_shape[1]) * int(itemsize)
+    per = int(budget) // frame_bytes
+    if per < 1:
+        raise ValueError(f"maps_budget={int(budget)} bytes holds less than one frame's {K} x {out_shape[0]} x {out_shape[1]} maps "
+                         f"({frame_bytes} bytes needed)")
+    return [(f, min(f + per, n_frames)) for f in range(0, n_frames, per)]
+
+
+def softmaps_to_host(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, map_pad: Tuple[int, int, int, int],
+                     out_shape: Tuple[int, int], budget: int = MAPS_BUDGET, events: Optional[dict] = None):
+    """The (T, K, h0, w0) stack of a propagated bank (propagate_soft_bank / propagate_soft_bank_local) as a numpy array, in heat's dtype.
+    The read-out runs over plan_map_chunks' frame ranges into ONE reused device buffer of at most `budget` bytes; each chunk is copied
+    into the host array before the buffer is written again (the copy is synchronous: no overlap with the next chunk's read-out).
+    `events`: 'readout' is recorded before the first chunk and 'end' after the last copy."""
+    T, K = bank.shape[0], heat.shape[0]
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    chunks = plan_map_chunks(T, K, out_shape, heat.element_size(), budget)
+    host = torch.empty((T, K, *out_shape), dtype=heat.dtype)
+    buf = torch.empty((chunks[0][1] - chunks[0][0], K, *out_shape), device=bank.device, dtype=heat.dtype)
+    rec("readout")
+    for f0, f1 in chunks:
+        ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=(f0, f1), out=buf[:f1 - f0])
+        host[f0:f1].copy_(buf[:f1 - f0])
+    rec("end")
+    return host.numpy()
 
 
 # ---- HRVanillaTracker's label maps: the local-window affinity (vanilla_tracker.py:663-830, local_attention.py:883-1006) ----------------
@@ -652,6 +710,17 @@ def propagate_heatmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: to
                              events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
     """propagate_heatmaps (same arguments and (2, K, T) f64 output; frame 0 = the padded map, not unpadded) on HRVanillaTracker's own
     affinity.  `stats_out`, `affinity_stats`: as propagate_masks_local."""
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    bank = propagate_soft_bank_local(feats_hwc, Hf, Wf, heat, map_pad, cfg, events=events, affinity_stats=affinity_stats)
+    rec("readout")
+    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    rec("end")
+    return coords
+
+
+def propagate_soft_bank_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                              cfg: LocalConfig, events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """propagate_soft_bank on HRVanillaTracker's own affinity: the part propagate_heatmaps_local and propagate_softmaps_local share."""
     if cfg.hard_prop:
         raise NotImplementedError("propagate_heatmaps_local: hard_prop with soft labels")
     T, dev = feats_hwc.shape[0], feats_hwc.device
@@ -665,7 +734,18 @@ def propagate_heatmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: to
     idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
     rec("propagation")
     _local_sweep(bank, bank, plan, idx, weight, Hf, Wf, cfg)
+    return bank
+
+
+def propagate_softmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                             out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
+                             events: Optional[dict] = None, affinity_stats: Optional[dict] = None,
+                             frames: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """propagate_softmaps (same arguments and (T, K, h0, w0) output) on HRVanillaTracker's own affinity.  `stats_out` is accepted for
+    the dense function's signature and ignored (nothing is appended, as in propagate_masks_local); `affinity_stats`: run_local_affinity's."""
+    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
+    bank = propagate_soft_bank_local(feats_hwc, Hf, Wf, heat, map_pad, cfg, events=events, affinity_stats=affinity_stats)
     rec("readout")
-    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=frames)
     rec("end")
-    return coords
+    return maps

@@ -250,7 +250,13 @@ class VanillaTracker(BaseTracker):
         g = self.test_cfg.get
         if ref_seg_map is None or imgs is None or img_meta is None:
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
-        if (ref_seg_map.ndim == 4) != bool(g("coords", False)):
+        return_maps = bool(g("return_maps", False))        # extension key: the propagated soft maps themselves (the reference's coords=False output)
+        if return_maps and g("coords", False):
+            raise ValueError("fgvc_amd: return_maps=True and coords=True ask for two read-outs of one call; set one of them")
+        if return_maps and ref_seg_map.ndim != 4:
+            raise NotImplementedError("fgvc_amd: return_maps=True takes soft (4-D) first-frame labels; for the per-object maps of an index map "
+                                      "pass its one-hot as float labels (1, C, h, w)")
+        if not return_maps and (ref_seg_map.ndim == 4) != bool(g("coords", False)):
             raise NotImplementedError("fgvc_amd: soft (4-D) first-frame labels go with coords=True only (the JHMDB / BADJA heat-map form: "
                                       "joint coordinates), and coords=True with soft labels only (img2coord asserts on an index map); "
                                       "full-resolution soft maps are not returned -- track the joints as query points instead "
@@ -258,7 +264,7 @@ class VanillaTracker(BaseTracker):
         if g("save_np", False):
             raise NotImplementedError("fgvc_amd: save_np=True is not supported; the masks are returned (save them with numpy.save)")
         if ref_seg_map.ndim == 4:
-            return self._forward_test_heatmap(imgs, ref_seg_map, img_meta)
+            return self._forward_test_heatmap(imgs, ref_seg_map, img_meta, return_maps=return_maps)
         if imgs.shape[0] != 1 or imgs.shape[1] != 1 or ref_seg_map.shape[0] != 1:     # (B, clips, 3, T, h, w): :676 folds clips into B
             raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
         if ref_seg_map.dtype != torch.uint8:
@@ -290,11 +296,13 @@ class VanillaTracker(BaseTracker):
         self._check_kernels()
         return [masks.cpu().numpy().astype("float64")]
 
-    def _forward_test_heatmap(self, imgs, heat, img_meta):
+    def _forward_test_heatmap(self, imgs, heat, img_meta, return_maps=False):
         """forward_test_seg with soft first-frame labels and test_cfg.coords=True (the JHMDB / BADJA heat-map form): heat (1, K, hm, wm)
         float32 | float64, padded by its OWN pad_divide_by (vanilla_tracker.py:672).  Returns a list over the batch of one ndarray
         (2, K, T) float64 = img2coord of the propagated maps at img_meta[0]['original_shape'] (:814-818).  Frame 0 is the padded map
-        resized to that shape, NOT unpadded (:712-716): the reference's quirk, kept."""
+        resized to that shape, NOT unpadded (:712-716): the reference's quirk, kept.
+        return_maps (test_cfg.return_maps=True instead of coords): the maps themselves, one ndarray (T, K, h0, w0) in heat's dtype
+        (:800-803, :826-831)."""
         if self._label_config().hard_prop:
             raise NotImplementedError("fgvc_amd: hard_prop=True with soft labels (the reference's F.one_hot without num_classes drops the last "
                                       "channel when it never wins, and the next frame's cat then fails, vanilla_tracker.py:762-768)")
@@ -310,27 +318,48 @@ class VanillaTracker(BaseTracker):
         heat = heat[0].to(imgs.device).contiguous()
         if not bool(torch.isfinite(heat).all()):
             raise ValueError("ref_seg_map: the soft labels hold a non-finite value")
-        return self._seg_heatmaps(imgs, heat, img_meta)
+        return self._seg_softmaps(imgs, heat, img_meta) if return_maps else self._seg_heatmaps(imgs, heat, img_meta)
 
     def _label_config(self):
         """The configuration the label-map path propagates with (its `hard_prop` is read before the heat-map path's other checks)."""
         return self.engine_config()
 
+    def _heat_inputs(self, imgs, heat, img_meta, unit):
+        """Frames and map each padded by its own pad_divide_by with `unit` (:671-672): the padded frames (T, 3, hp, wp), the map's pad, (h0, w0)."""
+        h, w = imgs.shape[-2:]
+        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
+        _, pad = engine.pad_divide_by(h, w, unit)
+        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], unit)
+        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        return frames, map_pad, (h0, w0)
+
     def _seg_heatmaps(self, imgs, heat, img_meta):
         """_forward_test_heatmap past its refusals: heat (K, hm, wm) on the device -> [ (2, K, T) float64 ]."""
         cfg = self.engine_config()
-        h, w = imgs.shape[-2:]
-        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        d = self.output_stride()
-        _, pad = engine.pad_divide_by(h, w, d)
-        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], d)
-        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.output_stride())
         feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
         stats = []
-        coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats)
+        coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, out_shape, cfg, channels=self.feat_channels, stats_out=stats)
         self._refine_stats = stats or None
         self._check_kernels()
         return [coords.cpu().numpy()]
+
+    def _maps_budget(self) -> int:
+        return int(self.test_cfg.get("maps_budget", engine.MAPS_BUDGET))
+
+    def _seg_softmaps(self, imgs, heat, img_meta):
+        """_forward_test_heatmap(return_maps=True) past its refusals -> [ (T, K, h0, w0) in heat's dtype ].  The bank is propagated once;
+        the read-out goes to the host in chunks of at most test_cfg.maps_budget bytes of device memory (engine.softmaps_to_host)."""
+        cfg = self.engine_config()
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.output_stride())
+        engine.plan_map_chunks(frames.shape[0], heat.shape[0], out_shape, heat.element_size(), self._maps_budget())   # refuse before any work
+        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
+        stats = []
+        bank = engine.propagate_soft_bank(feats, Hf, Wf, heat, map_pad, cfg, channels=self.feat_channels, stats_out=stats)
+        self._refine_stats = stats or None
+        maps = engine.softmaps_to_host(bank, heat, Hf, Wf, map_pad, out_shape, self._maps_budget())
+        self._check_kernels()
+        return [maps]
 
     @torch.no_grad()
     def forward_test_main(self, rgbs, query_points, trajectories, visibilities):
@@ -493,17 +522,26 @@ class HRVanillaTracker(VanillaTracker):
     def _seg_heatmaps(self, imgs, heat, img_meta):
         """Heat maps (coords=True): frames and map each padded by pad_divide_by with the tracker's `stride` (:671-672)."""
         cfg = self._label_config()
-        h, w = imgs.shape[-2:]
-        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        _, pad = engine.pad_divide_by(h, w, self.stride)
-        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], self.stride)
-        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.stride)
         feats, Hf, Wf = self._label_feats(frames)
         self.label_stats = {}
-        coords = engine.propagate_heatmaps_local(feats, Hf, Wf, heat, map_pad, (h0, w0), cfg, affinity_stats=self.label_stats)
+        coords = engine.propagate_heatmaps_local(feats, Hf, Wf, heat, map_pad, out_shape, cfg, affinity_stats=self.label_stats)
         self._refine_stats = None
         self._check_kernels()
         return [coords.cpu().numpy()]
+
+    def _seg_softmaps(self, imgs, heat, img_meta):
+        """The maps themselves (return_maps=True): as _seg_heatmaps up to the bank, then VanillaTracker._seg_softmaps' chunked read-out."""
+        cfg = self._label_config()
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.stride)
+        engine.plan_map_chunks(frames.shape[0], heat.shape[0], out_shape, heat.element_size(), self._maps_budget())
+        feats, Hf, Wf = self._label_feats(frames)
+        self.label_stats = {}
+        bank = engine.propagate_soft_bank_local(feats, Hf, Wf, heat, map_pad, cfg, affinity_stats=self.label_stats)
+        self._refine_stats = None
+        maps = engine.softmaps_to_host(bank, heat, Hf, Wf, map_pad, out_shape, self._maps_budget())
+        self._check_kernels()
+        return [maps]
 
     @torch.no_grad()
     def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,

@@ -1268,3 +1268,34 @@ def heatmap_coords(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, pad
     _lib.call("fgvc_heatmap_coords_f32", _ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm,
               hm + lh + uh, wm + lw + uw, lh, lw, h0, w0, int(bool(f64_arith)), _ptr(out), _ptr(ws), _stream(heat))
     return out
+
+
+def softmap_readout(bank: Optional[torch.Tensor], heat: torch.Tensor, Hf: int, Wf: int, pad: Tuple[int, int, int, int],
+                    out_shape: Tuple[int, int], frames: Optional[Tuple[int, int]] = None, out_dtype: Optional[torch.dtype] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frames [f_begin, f_end) of the stack the reference returns without `coords` (vanilla_tracker.py:770-784, :800-803) ->
+    (f_end - f_begin, K, h0, w0): the maps heatmap_coords reads its five values from, written out, bit for bit.  Arguments as
+    heatmap_coords'; `frames` defaults to all T of the bank; `out_dtype` float64 | float32 defaults to heat's dtype (np.stack's): frames
+    >= 1 are f32 values (widened for a float64 result), frame 0 is computed in heat's dtype and rounded once for a float32 result.
+    `bank` may be None when only frame 0 is asked for."""
+    heat = _heat(heat)
+    K, hm, wm = heat.shape
+    if bank is not None:
+        bank = _chk(bank, torch.float32, "bank")
+        assert bank.shape[1:] == (Hf * Wf, K), (tuple(bank.shape), Hf, Wf, K)
+    T = bank.shape[0] if bank is not None else 1
+    f_begin, f_end = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    lw, uw, lh, uh = pad
+    h0, w0 = out_shape
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else heat.dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"out_dtype: float32 or float64, got {out_dtype}")
+    shape = (max(f_end - f_begin, 0), K, h0, w0)
+    if out is None:
+        out = torch.empty(shape, device=heat.device, dtype=out_dtype)
+    else:
+        assert out.is_contiguous() and tuple(out.shape) == shape and out.dtype == out_dtype and out.device == heat.device
+    _lib.call("fgvc_softmap_readout_f32", _ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm,
+              hm + lh + uh, wm + lw + uw, lh, lw, h0, w0, f_begin, f_end, int(out_dtype == torch.float64), _ptr(out), _stream(heat))
+    return out

@@ -529,6 +529,18 @@ size_t fgvc_heatmap_coords_workspace_bytes(int T, int K);
 int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
                             int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream);
 
+/* The maps themselves, frames [f_begin, f_end) of the stack the reference returns without `coords` (:770-784, :800-803), channel-first:
+ *   out [f_end - f_begin][K][h0][w0], f32 or (out_f64 != 0) f64;
+ *   frame 0:   bilinear_{h0,w0}(padded map) in the map's dtype, NOT unpadded (:712-716);
+ *   frame f>0: bilinear_{h0,w0}(crop_{top,left,hm,wm}(bilinear_{hp,wp}(bank[f]))) in f32;
+ * every value is the one fgvc_heatmap_coords_f32 evaluates for that pixel, bit for bit (the same device functions).  out_f64: frames
+ * >= 1 are the f32 values widened, frame 0 keeps the map's precision (np.stack of a float64 frame 0 with float32 frames, :803);
+ * out_f64 == 0 with an f64 map rounds frame 0 once to f32.  bank [T][Hf*Wf][K] f32 (row 0 is not read; may be NULL when f_end <= 1),
+ * map0 as above.  A workgroup stages the feature-grid footprint of an 8 x 64 output tile in LDS and writes row-contiguous runs.
+ * No workspace, no atomics.  1 <= K <= 256, 0 <= f_begin < f_end <= T. */
+int fgvc_softmap_readout_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                             int wp, int top, int left, int h0, int w0, int f_begin, int f_end, int out_f64, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

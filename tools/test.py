@@ -26,7 +26,7 @@ import fgvc_amd.mmpt_api as api  # noqa: E402
 from fgvc_amd import apis, metrics  # noqa: E402
 from fgvc_amd.datasets import Davis2017, davis_evaluate  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
-from fgvc_amd.datasets import badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
+from fgvc_amd.datasets import MapsAsCoords, badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
 
 DEFAULT_CFG = dict(
     model=dict(type="VanillaTracker",
@@ -48,9 +48,11 @@ def main():
     ap.add_argument("--points", type=int, default=8)
     ap.add_argument("--query-mode", default="first")
     ap.add_argument("--data-root", default=None, help="TAP-Vid pickles (directory of *.pkl or one .pkl); default: synthetic clips")
-    ap.add_argument("--pose-form", choices=["points", "heatmap"], default="points",
+    ap.add_argument("--pose-form", choices=["points", "heatmap", "softmap"], default="points",
                     help="jhmdb / badja: 'points' tracks the frame-0 joints as query points; 'heatmap' propagates the reference's first-frame "
-                         "Gaussian maps and reads joints out of them (test_cfg.coords=True)")
+                         "Gaussian maps and reads joints out of them (test_cfg.coords=True); 'softmap' has the propagated maps themselves "
+                         "returned (test_cfg.return_maps=True) and reads the joints out of them on the host, by the same rule")
+    ap.add_argument("--dump-maps", default=None, metavar="DIR", help="--pose-form softmap: write each video's (T, K, h0, w0) array as DIR/<video>.npy")
     ap.add_argument("--eval-arc", default=None, help="tracker class to build, overriding the config's eval_arc (e.g. HRVanillaTracker: the "
                                                      "local-window affinity for masks, heat maps and points)")
     ap.add_argument("--out", default=None)
@@ -88,8 +90,13 @@ def main():
     if key not in cfg:
         raise SystemExit(f"the config has no '{key}' (tasks it defines: {sorted(k[9:] for k in cfg if k.startswith('test_cfg_'))})")
     test_cfg = cfg[key]
-    heatmap = a.task in ("jhmdb", "badja") and a.pose_form == "heatmap"
-    if heatmap:
+    heatmap = a.task in ("jhmdb", "badja") and a.pose_form in ("heatmap", "softmap")
+    softmap = heatmap and a.pose_form == "softmap"
+    if a.dump_maps and not softmap:
+        raise SystemExit("--dump-maps goes with --task jhmdb|badja --pose-form softmap")
+    if softmap:
+        test_cfg = dict(test_cfg, return_maps=True)  # the maps themselves (the reference's coords=False return value), decoded below
+    elif heatmap:
         test_cfg = dict(test_cfg, coords=True)       # the reference's pose configs: 4-D first-frame maps read out by img2coord
     model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
@@ -100,6 +107,16 @@ def main():
     if a.checkpoint:
         api.load_checkpoint(model, a.checkpoint)                                             # :158-159
     model = model.to(dev).eval()
+
+    def scored(names):
+        """The model the heat-map evaluators call: itself, or under --pose-form softmap its maps decoded on the host (and dumped)."""
+        if not softmap:
+            return model
+        if a.dump_maps:
+            os.makedirs(a.dump_maps, exist_ok=True)
+        import numpy as np
+        dump = (lambda i, maps: np.save(os.path.join(a.dump_maps, names(i) + ".npy"), maps)) if a.dump_maps else None
+        return MapsAsCoords(model, dump)
 
     if a.task == "vos":        # semi-supervised VOS: the first annotation is propagated (VanillaTracker.forward_test_seg), scored by J&F
         if rank == 0:
@@ -114,7 +131,8 @@ def main():
     elif a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
             if heatmap:        # --pose-form heatmap: the reference's own first-frame label (BadjaPoses(form='heatmap'))
-                pck = badja_evaluate_heatmap(model, BadjaPoses(a.data_root, size=(320, 512), device=dev, form="heatmap"))
+                ds = BadjaPoses(a.data_root, size=(320, 512), device=dev, form="heatmap")
+                pck = badja_evaluate_heatmap(scored(lambda i: str(ds.videos[i]["name"])), ds)
             else:
                 pck = badja_evaluate(model, BadjaPoses(a.data_root, size=(320, 512), device=dev))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
@@ -127,7 +145,9 @@ def main():
         # other ranks of a `--launcher pytorch` job wait at the common teardown below
         if rank == 0:
             if heatmap:
-                pck = jhmdb_evaluate_heatmap(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev, form="heatmap"))
+                ds = JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev, form="heatmap")
+                vname = lambda i: os.path.relpath(ds.samples[i]["video_path"], ds.root).replace(os.sep, "_")   # <action>_<video>
+                pck = jhmdb_evaluate_heatmap(scored(vname), ds)
             else:
                 pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
