@@ -37,6 +37,8 @@ int local_merge_launch(const int32_t*, const float*, int, int, int, int, int, fl
 int local_merge_plan_launch(const int32_t*, const float*, const int32_t*, int, int, int, int, int, int, int, float, int32_t*, float*,
                             float*, hipStream_t);
 int topk_coord_launch(const int32_t*, const float*, int, int, int, int, int, float*, hipStream_t);
+int topk_coord_rows_launch(const int32_t*, const float*, int, int, int, int, int, int, float*, hipStream_t);
+int cycle_chase_launch(const float*, const float*, const float*, int, int, int, int, int, float*, float*, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -554,6 +556,26 @@ int fgvc_topk_coord_f32(const int32_t* idx, const float* weight, int H, int W, i
   FGVC_REQUIRE(idx && weight && out, FGVC_ERR_INVALID_ARG, "fgvc_topk_coord_f32: null pointer");
   FGVC_REQUIRE(H > 0 && W > 0 && R >= 0 && topk >= 1 && scale >= 1, FGVC_ERR_INVALID_ARG, "fgvc_topk_coord_f32: bad shape");
   return topk_coord_launch(idx, weight, H, W, R, topk, scale, out, (hipStream_t)stream);
+}
+
+int fgvc_topk_coord_rows_f32(const int32_t* idx, const float* weight, int rows, int H, int W, int R, int topk, int scale, float* out,
+                             void* stream) {
+  FGVC_REQUIRE(idx && weight && out, FGVC_ERR_INVALID_ARG, "fgvc_topk_coord_rows_f32: null pointer");
+  FGVC_REQUIRE(rows >= 1 && rows <= 65535 && H > 0 && W > 0 && R >= 0 && topk >= 1 && scale >= 1 && (long long)H * W < (1ll << 30),
+               FGVC_ERR_INVALID_ARG, "fgvc_topk_coord_rows_f32: bad shape");
+  FGVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7u) == 0, FGVC_ERR_INVALID_ARG, "fgvc_topk_coord_rows_f32: out must be 8-byte aligned");
+  return topk_coord_rows_launch(idx, weight, rows, H, W, R, topk, scale, out, (hipStream_t)stream);
+}
+
+int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* start_xy, int n, int P, int H, int W, int scale,
+                         float* back_out, float* err_out, void* stream) {
+  FGVC_REQUIRE(fields && traj && start_xy && back_out && err_out, FGVC_ERR_INVALID_ARG, "fgvc_cycle_chase_f32: null pointer");
+  FGVC_REQUIRE(n >= 1 && P >= 1 && H > 0 && W > 0 && scale >= 1 && (long long)H * W < (1ll << 30) && (long long)n * P < (1ll << 30),
+               FGVC_ERR_INVALID_ARG, "fgvc_cycle_chase_f32: bad shape");
+  FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(traj) | reinterpret_cast<uintptr_t>(start_xy) |
+                 reinterpret_cast<uintptr_t>(back_out)) & 7u) == 0,
+               FGVC_ERR_INVALID_ARG, "fgvc_cycle_chase_f32: the (x, y) arrays must be 8-byte aligned");
+  return cycle_chase_launch(fields, traj, start_xy, n, P, H, W, scale, back_out, err_out, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

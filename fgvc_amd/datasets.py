@@ -17,11 +17,41 @@ import torch
 
 class SyntheticTapVid:
     """Moving-texture clips with known point tracks: every frame is the first frame shifted by an integer
-    (dx,dy) per frame, so ground-truth trajectories are exact and a tracker's accuracy is measurable."""
+    (dx,dy) per frame, so ground-truth trajectories are exact and a tracker's accuracy is measurable.
+    occluder=True: a STATIC textured rectangle (OCCLUDER_FRACTION of each side, seeded position and texture) is pasted over the frames
+    t >= T // 2 -- after every query time, so that query points stay visible -- and the points under it are marked invisible in
+    `visibilities`.  Everything else (the frames outside the rectangle, points, trajectories, queries) is the occluder=False sample."""
 
-    def __init__(self, n_videos=4, frames=8, size=(256, 256), points=8, query_mode="first", seed=0, device="cpu"):
+    OCCLUDER_FRACTION = 0.4
+
+    def __init__(self, n_videos=4, frames=8, size=(256, 256), points=8, query_mode="first", seed=0, device="cpu", occluder=False):
         self.n, self.T, self.h, self.w, self.P = n_videos, frames, size[0], size[1], points
         self.query_mode, self.seed, self.device = query_mode, seed, device
+        self.occluder = bool(occluder)
+
+    def occluder_box(self, i):
+        """(t_on, y0, y1, x0, x1) of video i's rectangle: present in frames t_on .. T-1, rows y0:y1, columns x0:x1 (None without one)."""
+        if not self.occluder:
+            return None
+        g = torch.Generator().manual_seed(self.seed * 1000 + i + 500009)             # its own stream: the sample's draws stay as they are
+        rh, rw = max(1, int(self.h * self.OCCLUDER_FRACTION)), max(1, int(self.w * self.OCCLUDER_FRACTION))
+        y0 = int(torch.randint(0, self.h - rh + 1, (1,), generator=g))
+        x0 = int(torch.randint(0, self.w - rw + 1, (1,), generator=g))
+        return self.T // 2, y0, y0 + rh, x0, x0 + rw
+
+    def _paste_occluder(self, i, rgbs, traj, vis):
+        t_on, y0, y1, x0, x1 = self.occluder_box(i)
+        g = torch.Generator().manual_seed(self.seed * 1000 + i + 700001)
+        rh, rw = y1 - y0, x1 - x0
+        tex = torch.nn.functional.interpolate(torch.randn(1, 3, rh // 4 + 2, rw // 4 + 2, generator=g), size=(rh, rw), mode="bilinear",
+                                              align_corners=False)[0]
+        tex = 1.5 * tex + 0.25 * torch.randn(tex.shape, generator=g)
+        rgbs = rgbs.clone()
+        rgbs[t_on:, :, y0:y1, x0:x1] = tex
+        x, y = traj[..., 0], traj[..., 1]
+        under = (x >= x0) & (x <= x1 - 1) & (y >= y0) & (y <= y1 - 1)
+        under[:t_on] = False
+        return rgbs, vis * (~under).float()
 
     def __len__(self):
         return self.n
@@ -44,6 +74,8 @@ class SyntheticTapVid:
         # express the query at its own time: position at t0 is (x0,y0)
         qp = torch.stack([t0, x0, y0], -1)
         vis = (ts >= t0.view(1, P)).float()
+        if self.occluder:
+            rgbs, vis = self._paste_occluder(i, rgbs, traj, vis)
         d = self.device
         return dict(rgbs=rgbs.unsqueeze(0).to(d), query_points=qp.unsqueeze(0).to(d),
                     trajectories=traj.unsqueeze(0).to(d), visibilities=vis.unsqueeze(0).to(d))

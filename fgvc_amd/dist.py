@@ -447,6 +447,9 @@ def track_points_sharded(backend, rgbs: torch.Tensor, query_points: torch.Tensor
     The device flags are process-wide words (read-and-clear): one consumer per process -- two trackers sharing a process also share them."""
     if halo not in ("exchange", "recompute", "auto"):
         raise ValueError(f"halo={halo!r}")
+    if getattr(getattr(backend, "model", None), "test_cfg", None) is not None and backend.model.test_cfg.get("occlusion", None) is not None:
+        raise NotImplementedError("fgvc_amd: test_cfg.occlusion (the forward-backward visibility read-out) is not computed on the sharded "
+                                  "path; call the model itself (model(test_mode=True, rgbs=..., query_points=...)) or remove the key")
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     T, h, w = rgbs.shape[0], rgbs.shape[-2], rgbs.shape[-1]

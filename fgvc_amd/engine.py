@@ -749,3 +749,97 @@ def propagate_softmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: to
     maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=frames)
     rec("end")
     return maps
+
+
+# ---- predicted visibility: the forward-backward cycle check -------------------------------------------------------
+#
+# HRVanillaTracker.forward_test_forward (vanilla_tracker.py:591-645) with precede_frames = 1 pushes points through the chain of
+# frame-to-frame coordinate fields.  Run on the reversed sub-clip [f, f-1, ..., s] from the PREDICTED position x_f it walks the prediction
+# back to the query frame; how far it lands from the query point is the forward-backward tracking error.  The field of query frame g and
+# key frame g - 1 does not depend on s, f or the point: the T - 1 fields are computed once per clip and every (group, frame, point) chases
+# through them.
+
+@dataclass
+class OcclusionConfig:
+    """test_cfg.occlusion = dict(type='cycle', cycle_thresh=1.0, radius=None), parsed.  `cycle_thresh` is in FEATURE CELLS (the fields live
+    on the feature grid: an error below its pitch cannot be told from their own quantisation); `radius` = the local window of the fields."""
+    cycle_thresh: float = 1.0
+    radius: int = 12
+
+
+def parse_occlusion(spec, default_radius: int) -> Optional[OcclusionConfig]:
+    """None -> None (the option is off: the trackers return zeros, as the reference does).  A mapping with type='cycle' -> OcclusionConfig;
+    any other `type` (or none), an unknown key or a value out of range raises ValueError, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.occlusion: a dict such as dict(type='cycle', cycle_thresh=1.0, radius=None), got {type(spec).__name__}")
+    spec = dict(spec)
+    typ = spec.pop("type", None)
+    if typ != "cycle":
+        raise ValueError(f"test_cfg.occlusion: type={typ!r} (only 'cycle', the forward-backward cycle check)")
+    thresh, radius = spec.pop("cycle_thresh", 1.0), spec.pop("radius", None)
+    if spec:
+        raise ValueError(f"test_cfg.occlusion: unknown key(s) {sorted(spec)} (type, cycle_thresh, radius)")
+    thresh = float(thresh)
+    if not (math.isfinite(thresh) and thresh >= 0):
+        raise ValueError(f"test_cfg.occlusion: cycle_thresh={thresh} (a finite number of feature cells >= 0)")
+    radius = int(default_radius) if radius is None else int(radius)
+    if radius < 0:
+        raise ValueError(f"test_cfg.occlusion: radius={radius}")
+    return OcclusionConfig(thresh, radius)
+
+
+def backward_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, stats: Optional[dict] = None) -> torch.Tensor:
+    """The clip's T - 1 backward coordinate fields (T-1, HW, 2) f32, (x, y) image pixels interleaved: fields[g - 1] = get_coord(query =
+    frame g, key = frame g - 1) (vanilla_tracker.py:445-488), the expected position in frame g - 1 of every feature cell of frame g.
+    feats_hwc: f32 rows (T, HW, C) (L2-normalised iff cfg.with_norm) or their split_f16x2 form, as run_local_affinity takes them.
+    `cfg`: a LocalConfig with precede_frames = 1 and with_first = False -- plan_local_clip then yields exactly the pairs (g, g - 1), run in
+    chunked launches within cfg.pair_budget -- then ONE fgvc_topk_coord_rows_f32 launch.  `stats`: run_local_affinity's."""
+    if cfg.precede_frames != 1 or cfg.with_first:
+        raise ValueError("backward_fields: a LocalConfig with precede_frames=1 and with_first=False (one key slot per frame: the one before)")
+    T = feats_hwc.shape[0]
+    if T < 2:
+        return torch.empty((0, Hf * Wf, 2), device=feats_hwc.device, dtype=torch.float32)
+    plan = plan_local_clip(T, cfg, Hf * Wf)
+    assert plan.pairs == [(g, g - 1) for g in range(1, T)]
+    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, stats)
+    return ops.topk_coord_rows(idx, weight, Hf, Wf, int(cfg.radius), int(scale))
+
+
+def cycle_check(fields: torch.Tensor, traj: torch.Tensor, start: int, query_xy: torch.Tensor, scale: int, thresh: float,
+                Hf: int, Wf: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One query-time group.  fields (T-1, HW, 2) = backward_fields of the clip; traj (T-start, P, 2) = the group's predicted (x, y) from
+    its query frame `start` on (row 0 = the query frame itself); query_xy (P, 2) = x_s; thresh in feature cells.
+    Returns visible (T-start, P) bool = err <= thresh * scale, err (T-start, P) f32 and back (T-start, P, 2) f32 = the back-tracked points.
+    Row 0 (the query frame) is visible with err 0 and back = the query point."""
+    n, P = traj.shape[0] - 1, traj.shape[1]
+    assert n >= 0 and fields.shape[0] >= start + n
+    dev = traj.device
+    q = query_xy.to(dev, torch.float32)
+    err = torch.zeros((n + 1, P), device=dev, dtype=torch.float32)
+    back = torch.empty((n + 1, P, 2), device=dev, dtype=torch.float32)
+    back[0] = q
+    if n and P:
+        b, e = ops.cycle_chase(fields[start:start + n], traj[1:], q, scale, Hf, Wf)
+        back[1:], err[1:] = b, e
+    return err <= float(thresh) * float(scale), err, back
+
+
+def cycle_check_groups(fields: torch.Tensor, traj: torch.Tensor, times: torch.Tensor, query_xy: torch.Tensor, scale: int, thresh: float,
+                       Hf: int, Wf: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cycle_check for every query-time group of a regrouped clip: the fields are shared, the chase runs per group with its own start.
+    traj (T, P, 2) and times (P,) int64 (host) / query_xy (P, 2) in the SAME point order (track_points' `order`: ascending query time).
+    Returns visible (T, P) bool and err (T, P) f32; frames before a point's query time are not scored: visible 0, err +inf."""
+    T, P = traj.shape[0], traj.shape[1]
+    dev = traj.device
+    vis = torch.zeros((T, P), device=dev, dtype=torch.bool)
+    err = torch.full((T, P), float("inf"), device=dev, dtype=torch.float32)
+    times = times.to("cpu", torch.int64)
+    for s in sorted(set(times.tolist())):
+        cols = (times == s).nonzero().flatten()
+        q = query_xy[cols.to(query_xy.device)]
+        cols = cols.to(dev)
+        v, e, _ = cycle_check(fields, traj[s:, cols], s, q, scale, thresh, Hf, Wf)
+        vis[s:, cols], err[s:, cols] = v, e
+    return vis, err

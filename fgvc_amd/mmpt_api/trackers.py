@@ -91,6 +91,7 @@ class VanillaTracker(BaseTracker):
         g = self.test_cfg.get
         self.stride_sample = g("stride_sample", False)
         self.feat_channels = None          # the encoder's (un-padded) channel count, known after the first get_feats_hwc()
+        self.last_cycle_error = None       # (1, T, P) f32 forward-backward errors of the last points call with test_cfg.occlusion set, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -183,6 +184,66 @@ class VanillaTracker(BaseTracker):
                                "this video's results are invalid -- the scales were dropped and the next call re-calibrates on its own "
                                "frames (or call backbone.calibrate(frames), or backbone.set_arith('bf16x3'))")
 
+    # ---- predicted visibility: the forward-backward cycle check (test_cfg.occlusion, an extension key) ----------
+    _default_neighbor_range = None         # (TrackerConfig.from_test_cfg reads neighbor_range without a default; HRVanillaTracker's is 24)
+
+    def _occlusion(self) -> Optional[engine.OcclusionConfig]:
+        """test_cfg.occlusion parsed (None: the option is off).  The default window of the fields is this tracker's own: neighbor_range // 2."""
+        spec = self.test_cfg.get("occlusion", None)
+        if spec is None:
+            return None
+        nr = self.test_cfg.get("neighbor_range", self._default_neighbor_range)
+        if nr is None and dict(spec).get("radius") is None:
+            raise ValueError("test_cfg.occlusion: neighbor_range is None (no window to derive the fields' from); give occlusion.radius")
+        return engine.parse_occlusion(spec, 0 if nr is None else int(nr) // 2)
+
+    def _refuse_occlusion(self, what: str):
+        if self.test_cfg.get("occlusion", None) is not None:
+            raise NotImplementedError(f"fgvc_amd: test_cfg.occlusion is read by the points call only (rgbs= / query_points=); {what} "
+                                      "has no visibility output -- remove the key for this call")
+
+    def _cycle_fields(self, feats, Hf, Wf, w, occ: engine.OcclusionConfig):
+        """The clip's backward coordinate fields from the bank get_feats_hwc(split=True) returned, on this tracker's own topk, temperature
+        and normalisation key.  The f16 + FP6 bank gives its exact f32 channels (a view), a split_f16x2 bank goes in as it is where the
+        16-bit pair kernel takes the window, any other bank as f32 rows.  Returns (fields (T-1, HW, 2), scale)."""
+        cfg = self.engine_config()
+        fmt = ops.bank_format(feats, cfg.bank_fmt)
+        if fmt == "f16f6x":
+            rows = ops.f32_of_f16f6x(feats)
+        elif fmt == "f16f6":
+            raise NotImplementedError("fgvc_amd: test_cfg.occlusion needs f32-grade rows; a split_f16f6p() bank (pair_split_fmt='f16f6' with "
+                                      "pair_refine=False) holds 11-bit ones -- set pair_refine=True (the default) or pair_split_fmt='f16'")
+        elif fmt == "f16" and not ops.split_path_ok(feats.shape[-1], Hf, Wf, cfg.topk, cfg.with_norm, None,
+                                                    ops.MaskSpec(ry=occ.radius, rx=occ.radius), True):
+            rows = ops.unsplit_f16x2(feats)
+        else:
+            rows = feats
+        lc = engine.LocalConfig(temperature=cfg.softmax_temperature(self.feat_channels or rows.shape[-1]), topk=int(cfg.topk),
+                                precede_frames=1, radius=occ.radius, with_first=False, with_norm=bool(cfg.with_norm),
+                                pair_precision="f32" if cfg.pair_precision == "f32" else "auto",
+                                pair_budget=int(self.test_cfg.get("pair_budget", engine.LOCAL_PAIR_BUDGET)))
+        scale = w // Wf                                                               # vanilla_tracker.py:609
+        self.cycle_stats = {}
+        return engine.backward_fields(rows, Hf, Wf, lc, scale, self.cycle_stats), scale
+
+    def _visibility_from_frame0(self, feats, Hf, Wf, w, coords, qp, visibilities, occ):
+        """The fourth return element of the un-regrouped call: every point is tracked from frame 0, whatever its query time
+        (vanilla_tracker.py:302-303), so the cycle closes there; frames before a point's own query time are reported invisible.
+        qp (P, 3) = (t, x, y), coords (T, P, 2).  Zeros when the option is off."""
+        if occ is None:
+            return torch.zeros_like(visibilities)
+        T, dev = coords.shape[0], coords.device
+        fields, scale = self._cycle_fields(feats, Hf, Wf, w, occ)
+        v, e, _ = engine.cycle_check(fields, coords, 0, qp[:, 1:], scale, occ.cycle_thresh, Hf, Wf)
+        v = v & (torch.arange(T, device=dev).view(T, 1) >= qp[:, 0].to(dev).view(1, -1))
+        return self._visibility_like(visibilities, v, e)
+
+    def _visibility_like(self, visibilities, vis_bool, err):
+        """(T, P) bool / f32 -> the fourth return element (visibilities' dtype, shape and device; float32 without one) and last_cycle_error."""
+        self.last_cycle_error = err.unsqueeze(0)
+        v = vis_bool.unsqueeze(0)
+        return v.to(visibilities.dtype).to(visibilities.device) if visibilities is not None else v.to(torch.float32)
+
     # ---- A10: regrouping by query time ----------------------------------------------------------
     @torch.no_grad()
     def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,
@@ -200,6 +261,8 @@ class VanillaTracker(BaseTracker):
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
         assert rgbs.shape[0] == 1, "batch size must be 1 (vanilla_tracker.py:134)"
         cfg = self.engine_config()
+        occ = self._occlusion()
+        self.last_cycle_error = None
         T, h, w = rgbs.shape[1], rgbs.shape[-2], rgbs.shape[-1]
         dev = rgbs.device
         qp = query_points[0]
@@ -211,8 +274,9 @@ class VanillaTracker(BaseTracker):
             self._refine_stats = [tk.refine_stats] if tk.refine_stats is not None else None
             _, coords = engine.run_propagation(tk, 0, qp[:, 1:].to(dev, torch.float32), Hf, Wf, h, w, cfg)
             traj_pred = coords.unsqueeze(0)                                   # float64, like torch.from_numpy(...)
+            vis_pred = self._visibility_from_frame0(feats, Hf, Wf, w, coords, qp, visibilities, occ)
             self._check_kernels()
-            return trajectories, visibilities, traj_pred, torch.zeros_like(visibilities), query_points
+            return trajectories, visibilities, traj_pred, vis_pred, query_points
         t_min = int(qp[:, 0].min().item())
         # frames before the earliest query time are never used by any group
         feats, Hf, Wf = self.get_feats_hwc(rgbs[0, t_min:], split=True)
@@ -224,9 +288,17 @@ class VanillaTracker(BaseTracker):
         order = order.to(dev)
         traj_pred = torch.zeros_like(trajectories)
         traj_pred[0, t_min:] = traj.to(traj_pred.dtype)
+        vis_pred = torch.zeros_like(visibilities)
+        if occ is not None:
+            fields, scale = self._cycle_fields(feats, Hf, Wf, w, occ)                # once per clip, shared by every query-time group
+            qo = qp_rel.detach().cpu()[order.cpu()]                                   # (one host read for every group's columns)
+            v, e = engine.cycle_check_groups(fields, traj, qo[:, 0], qo[:, 1:], scale, occ.cycle_thresh, Hf, Wf)
+            vis = torch.zeros((T, qp.shape[0]), device=dev, dtype=torch.bool)
+            err = torch.full((T, qp.shape[0]), float("inf"), device=dev, dtype=torch.float32)
+            vis[t_min:], err[t_min:] = v, e
+            vis_pred = self._visibility_like(visibilities, vis, err)
         self._check_kernels()
-        return (trajectories[:, :, order], visibilities[:, :, order], traj_pred,
-                torch.zeros_like(visibilities), query_points[:, order])
+        return (trajectories[:, :, order], visibilities[:, :, order], traj_pred, vis_pred, query_points[:, order])
 
     def output_stride(self) -> int:
         """The encoder's output stride d (frame size / feature size): the mask path pads the frames to a multiple of it
@@ -250,6 +322,7 @@ class VanillaTracker(BaseTracker):
         g = self.test_cfg.get
         if ref_seg_map is None or imgs is None or img_meta is None:
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
+        self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
         return_maps = bool(g("return_maps", False))        # extension key: the propagated soft maps themselves (the reference's coords=False output)
         if return_maps and g("coords", False):
             raise ValueError("fgvc_amd: return_maps=True and coords=True ask for two read-outs of one call; set one of them")
@@ -365,6 +438,8 @@ class VanillaTracker(BaseTracker):
     def forward_test_main(self, rgbs, query_points, trajectories, visibilities):
         """vanilla_tracker.py:305-412: all points are propagated from frame 0 of `rgbs`."""
         cfg = self.engine_config()
+        occ = self._occlusion()
+        self.last_cycle_error = None
         T, h, w = rgbs.shape[1], rgbs.shape[-2], rgbs.shape[-1]
         feats, Hf, Wf = self.get_feats_hwc(rgbs[0], split=True)
         plan = engine.plan_clip(T, [0], cfg)
@@ -372,8 +447,9 @@ class VanillaTracker(BaseTracker):
         self._refine_stats = [tk.refine_stats] if tk.refine_stats is not None else None
         pts = query_points[0, :, 1:].to(rgbs.device, torch.float32)
         _, coords = engine.run_propagation(tk, 0, pts, Hf, Wf, h, w, cfg)
+        vis_pred = self._visibility_from_frame0(feats, Hf, Wf, w, coords, query_points[0], visibilities, occ)
         self._check_kernels()
-        return trajectories, visibilities, coords.unsqueeze(0), torch.zeros_like(visibilities), query_points
+        return trajectories, visibilities, coords.unsqueeze(0), vis_pred, query_points
 
 
 @MODELS.register_module()
@@ -396,6 +472,7 @@ class HRVanillaTracker(VanillaTracker):
         self.infer_radius = g("neighbor_range", 24) // 2
         self.infer_dilations = g("dilations", 1)
         self.grid_size_hr = 2 * self.infer_radius + 1
+        self._default_neighbor_range = 24                                # (the occlusion fields' default window = infer_radius)
         self.save_mem = bool(g("save_mem", False))                      # :432
         if self.save_mem and int(g("precede_frames", 5)) != 1:
             raise NotImplementedError("fgvc_amd: HRVanillaTracker save_mem=True needs precede_frames = 1: the reference's branch pairs ONE key "
@@ -437,11 +514,30 @@ class HRVanillaTracker(VanillaTracker):
     def forward_test_main(self, rgbs, query_points, trajectories, visibilities):
         """"backward warping" (:492-585): labels of frame f = top-k softmax over the (2R+1)^2 windows of its key slots."""
         h, w = rgbs.shape[-2], rgbs.shape[-1]
+        occ = self._occlusion()
+        self.last_cycle_error = None
         feats, Hf, Wf, norm = self._feats_hwc(rgbs[0])
-        coords = self._sweep(feats, Hf, Wf, norm, h, w, query_points[0, :, 1:].to(rgbs.device, torch.float32))
-        self._check_kernels()
+        pts = query_points[0, :, 1:].to(rgbs.device, torch.float32)
+        coords = self._sweep(feats, Hf, Wf, norm, h, w, pts)
         vis = torch.zeros_like(visibilities) if visibilities is not None else None
+        if occ is not None:
+            fields, scale = self._cycle_fields(feats, Hf, Wf, w, occ, norm)
+            v, e, _ = engine.cycle_check(fields, coords, 0, pts, scale, occ.cycle_thresh, Hf, Wf)
+            vis = self._visibility_like(visibilities, v, e)
+        self._check_kernels()
         return trajectories, visibilities, coords.unsqueeze(0), vis, query_points
+
+    def _cycle_fields(self, feats, Hf, Wf, w, occ: engine.OcclusionConfig, norm: bool = True):
+        """The clip's backward coordinate fields from _feats_hwc's f32 rows, with the keys get_coord reads (`topk`, `temperature`, `withnorm`):
+        fields[g - 1] is _coord_field(frame g, frame g - 1) for every g in chunked launches.  Returns (fields (T-1, HW, 2), scale)."""
+        g = self.test_cfg.get
+        pp = g("pair_precision", "auto")
+        lc = engine.LocalConfig(temperature=float(g("temperature", 1)), topk=int(g("topk", 10)), precede_frames=1, radius=occ.radius,
+                                with_first=False, with_norm=bool(norm), pair_precision="f32" if pp == "f32" else "auto",
+                                pair_budget=int(g("pair_budget", engine.LOCAL_PAIR_BUDGET)))
+        scale = w // Wf                                                                # :609
+        self.cycle_stats = {}
+        return engine.backward_fields(feats, Hf, Wf, lc, scale, self.cycle_stats), scale
 
     def _coord_field(self, qrow, krow, H, W, scale, norm):
         idx, _, weight = ops.local_corr_topk(qrow, krow, H, W, self.infer_radius, int(self.test_cfg.get("topk", 10)),
@@ -465,6 +561,7 @@ class HRVanillaTracker(VanillaTracker):
         frame-to-frame coordinate fields (query = frame max(0, f - precede_frames), key = frame f).  imgs (B,1,3,T,h,w).
         Returns what the reference returns: a list over the batch of float64 numpy arrays (2,P,T), rows (x,y)."""
         from .common import bilinear_sample
+        self._refuse_occlusion("forward_test_forward (forward warping)")
         h, w = imgs.shape[-2:]
         imgs = imgs.reshape((-1,) + imgs.shape[2:])                                    # :599
         assert imgs.shape[0] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"
@@ -559,19 +656,29 @@ class HRVanillaTracker(VanillaTracker):
         # inherited regrouping (vanilla_tracker.py:246-299): one sweep per distinct query time over the tail of the clip; the
         # frames are encoded ONCE (the reference re-encodes rgbs[:, t:] per group, :284 -- same features)
         h, w = rgbs.shape[-2], rgbs.shape[-1]
+        occ = self._occlusion()
+        self.last_cycle_error = None
         times = query_points[0, :, 0].to(torch.int64)
         t_min = int(times.min())
         feats, Hf, Wf, norm = self._feats_hwc(rgbs[0, t_min:])
         order, col = [], 0
         traj_pred = torch.zeros_like(trajectories)
+        T, P = rgbs.shape[1], query_points.shape[1]
+        if occ is not None:
+            fields, scale = self._cycle_fields(feats, Hf, Wf, w, occ, norm)            # once per clip, shared by every query-time group
+            vis = torch.zeros((T, P), device=rgbs.device, dtype=torch.bool)
+            err = torch.full((T, P), float("inf"), device=rgbs.device, dtype=torch.float32)
         for t in sorted(set(times.tolist())):
             sel = (times == t).nonzero().flatten()
             pts = query_points[0, sel, 1:].to(rgbs.device, torch.float32)
             coords = self._sweep(feats[t - t_min:], Hf, Wf, norm, h, w, pts)
             traj_pred[0, t:, col:col + sel.numel()] = coords.to(traj_pred.dtype)
+            if occ is not None:
+                v, e, _ = engine.cycle_check(fields, coords, t - t_min, pts, scale, occ.cycle_thresh, Hf, Wf)
+                vis[t:, col:col + sel.numel()], err[t:, col:col + sel.numel()] = v, e
             order.extend(sel.tolist())
             col += sel.numel()
         order = torch.tensor(order, device=rgbs.device)
+        vis_pred = self._visibility_like(visibilities, vis, err) if occ is not None else torch.zeros_like(visibilities)
         self._check_kernels()
-        return (trajectories[:, :, order], visibilities[:, :, order], traj_pred, torch.zeros_like(visibilities),
-                query_points[:, order])
+        return (trajectories[:, :, order], visibilities[:, :, order], traj_pred, vis_pred, query_points[:, order])

@@ -696,6 +696,35 @@ def topk_coord(idx: torch.Tensor, weight: torch.Tensor, H: int, W: int, R: int, 
     return out
 
 
+def topk_coord_rows(idx: torch.Tensor, weight: torch.Tensor, H: int, W: int, R: int, scale: int) -> torch.Tensor:
+    """topk_coord() for many single-slot rows in one launch: (rows, HW, k) lists -> (rows, HW, 2) fields, (x, y) interleaved."""
+    idx, weight = _chk(idx, torch.int32, "idx"), _chk(weight, torch.float32, "weight")
+    assert idx.dim() == 3 and idx.shape == weight.shape and idx.shape[1] == H * W
+    out = torch.empty((idx.shape[0], H * W, 2), device=idx.device, dtype=torch.float32)
+    if idx.shape[0]:
+        _lib.call("fgvc_topk_coord_rows_f32", _ptr(idx), _ptr(weight), idx.shape[0], H, W, R, idx.shape[2], int(scale), _ptr(out), _stream(idx))
+    return out
+
+
+def cycle_chase(fields: torch.Tensor, traj: torch.Tensor, start_xy: torch.Tensor, scale: int, H: int, W: int):
+    """Walk predicted positions back to their query frame through a chain of coordinate fields (fgvc_cycle_chase_f32).
+    fields (n, HW, 2) f32: fields[j] maps a position in frame s + 1 + j to frame s + j (topk_coord_rows); traj (n, P, 2) = the predicted
+    (x, y) of frames s + 1 .. s + n (any float dtype: chased in f32, as the reference's forward warping does); start_xy (P, 2) = the query
+    points.  Returns back (n, P, 2) f32 = where each position lands in frame s, err (n, P) f32 = its distance from the query point;
+    a non-finite position at any hop, or the (-1, -1) of an all-zero map, gives back = NaN and err = +inf."""
+    fields = _chk(fields, torch.float32, "fields")
+    traj = _chk(traj.to(torch.float32), torch.float32, "traj")
+    start_xy = _chk(start_xy.to(torch.float32), torch.float32, "start_xy")
+    n, P = traj.shape[0], traj.shape[1]
+    assert fields.shape == (n, H * W, 2) and traj.shape == (n, P, 2) and start_xy.shape == (P, 2)
+    back = torch.empty((n, P, 2), device=traj.device, dtype=torch.float32)
+    err = torch.empty((n, P), device=traj.device, dtype=torch.float32)
+    if n and P:
+        _lib.call("fgvc_cycle_chase_f32", _ptr(fields), _ptr(traj), _ptr(start_xy), n, P, H, W, int(scale), _ptr(back), _ptr(err),
+                  _stream(traj))
+    return back, err
+
+
 def c2f_refine(coarse_arg: torch.Tensor, qfine: torch.Tensor, kfine: torch.Tensor, vfine: torch.Tensor, H: int,
                W: int, scale: int, Rf: int, topk: int, temperature: float, mode: str = "softmax"):
     """A6 fine stage. coarse_arg int32 (T, HW); qfine (sHsW, Cf); kfine (T, sHsW, Cf); vfine (T, sHsW, P); mode "softmax" or

@@ -313,6 +313,20 @@ int fgvc_local_merge_plan_f32(const int32_t* pair_idx, const float* pair_score, 
  * (feature coordinate * scale). */
 int fgvc_topk_coord_f32(const int32_t* idx, const float* weight, int H, int W, int R, int topk, int scale,
                         float* out, void* stream);
+/* ... for `rows` single-slot lists in one launch: idx / weight [rows][H*W][topk] -> out [rows][H*W][2] = (x, y) interleaved (8-byte
+ * aligned: one bilinear tap of fgvc_cycle_chase_f32 is one 8-byte load).  Row r equals fgvc_topk_coord_f32 on its lists bit for bit. */
+int fgvc_topk_coord_rows_f32(const int32_t* idx, const float* weight, int rows, int H, int W, int R, int topk, int scale,
+                             float* out, void* stream);
+
+/* ---- forward-backward cycle check of predicted tracks: HRVanillaTracker.forward_test_forward's step
+ * (vanilla_tracker.py:639: bilinear_sample, align_corners=True, zero padding, corr_lookup.py:31-65) run backwards in time.
+ *   fields [n][H*W][2]: fields[j] maps a position (image pixels) in frame s+1+j to frame s+j (fgvc_topk_coord_rows_f32);
+ *   traj [n][P][2] = predicted (x, y) of frames s+1 .. s+n, start_xy [P][2] = the query points at frame s.
+ * One thread per (i, p): y = traj[i][p]; for j = i .. 0: y = sample(fields[j], y / scale).  back_out [n][P][2] = y,
+ * err_out [n][P] = |y - start_xy[p]|.  A non-finite position at any hop, or traj = (-1, -1) (the read-out of an all-zero map), gives
+ * back = NaN and err = +inf.  No atomics, no workspace. */
+int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* start_xy, int n, int P, int H, int W, int scale,
+                         float* back_out, float* err_out, void* stream);
 
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage

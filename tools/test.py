@@ -4,6 +4,7 @@
     python tools/test.py CONFIG --task davis [--checkpoint CKPT] [--videos 4 --frames 8 --size 256 256]
     python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
     python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
+    python tools/test.py CONFIG --task davis --occlusion [--cycle-thresh 1.0] [--occluder]   # predicted visibility: DESIGN.md section 13
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -55,6 +56,12 @@ def main():
     ap.add_argument("--dump-maps", default=None, metavar="DIR", help="--pose-form softmap: write each video's (T, K, h0, w0) array as DIR/<video>.npy")
     ap.add_argument("--eval-arc", default=None, help="tracker class to build, overriding the config's eval_arc (e.g. HRVanillaTracker: the "
                                                      "local-window affinity for masks, heat maps and points)")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="predict visibility by the forward-backward cycle check (test_cfg.occlusion = dict(type='cycle', ...)): "
+                         "average_jaccard and occlusion_accuracy then score a prediction instead of all-occluded zeros")
+    ap.add_argument("--cycle-thresh", type=float, default=None, metavar="CELLS",
+                    help="with --occlusion: a point is visible while its cycle error is <= this many feature cells (default 1.0)")
+    ap.add_argument("--occluder", action="store_true", help="synthetic clips: paste a static rectangle over the later frames (SyntheticTapVid(occluder=True))")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -82,7 +89,7 @@ def main():
     elif a.data_root:
         dataset = TapVidPickles(a.data_root, a.query_mode, tuple(a.size), device=dev)                   # :121-122
     else:
-        dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev)
+        dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev, occluder=a.occluder)
     loader = StridedLoader(dataset, rank, world) if dataset is not None else None          # :124-134
     key = "test_cfg_" + a.task                                                               # :135
     if key not in cfg and a.task in ("jhmdb", "badja", "vos") and "test_cfg_davis" in cfg:
@@ -98,6 +105,14 @@ def main():
         test_cfg = dict(test_cfg, return_maps=True)  # the maps themselves (the reference's coords=False return value), decoded below
     elif heatmap:
         test_cfg = dict(test_cfg, coords=True)       # the reference's pose configs: 4-D first-frame maps read out by img2coord
+    if a.cycle_thresh is not None and not a.occlusion:
+        raise SystemExit("--cycle-thresh goes with --occlusion")
+    if a.occlusion:
+        if dataset is None:
+            raise SystemExit("--occlusion is a read-out of the points call: TAP-Vid tasks only (not vos / jhmdb / badja)")
+        if distributed:
+            raise SystemExit("--occlusion runs on one GPU (--launcher none)")
+        test_cfg = dict(test_cfg, occlusion=dict(type="cycle", cycle_thresh=1.0 if a.cycle_thresh is None else a.cycle_thresh, radius=None))
     model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
