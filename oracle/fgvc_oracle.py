@@ -853,31 +853,64 @@ def f16f6_cosines(qrows: np.ndarray, krows: np.ndarray) -> np.ndarray:
 # ----------------------------------------------------------------------------
 # tolerance-aware comparison of a top-k result against a dense score slab
 # ----------------------------------------------------------------------------
+def _ranked(dense: torch.Tensor, k: int):
+    """Canonical ranks 1..min(k+1, M) of every column of `dense` (M,S): values dv (S,kk), candidate ids di (S,kk), `finite` (S,k) and the
+    adjacent gaps (S,kk-1) with non-finite differences counted as +inf."""
+    kk = min(k + 1, dense.shape[0])
+    dv, di = topk_canonical(dense, kk)
+    dv, di = dv.t(), di.t()
+    finite = torch.isfinite(dv[:, :k])
+    gaps = (dv[:, :-1] - dv[:, 1:]).abs()
+    gaps = torch.where(torch.isfinite(gaps), gaps, torch.full_like(gaps, float("inf")))
+    return dv, di, finite, gaps
+
+
+def _clear_columns(di: torch.Tensor, finite: torch.Tensor, gaps: torch.Tensor, gap: float, structural: Optional[torch.Tensor]) -> torch.Tensor:
+    """The ONE rule for 'this column is held to the exact canonical list' (check_topk and checkable_queries both use it): every adjacent gap
+    among ranks 1..k+1 is above `gap`, or -- with `structural` -- exactly 0 between two candidates of the same non-zero tie class."""
+    ok = gaps > gap
+    if structural is not None:
+        cls = structural.to(torch.int64).t().gather(1, di)            # (S,kk) tie class of every ranked candidate
+        ok = ok | ((gaps == 0) & (cls[:, :-1] != 0) & (cls[:, :-1] == cls[:, 1:]))
+    return ok.all(1) & finite.all(1)
+
+
+def checkable_queries(dense: torch.Tensor, k: int, gap: float = 1e-5, structural: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(S,) bool: the queries of the slab `dense` (M,S) on which check_topk demands the canonical list exactly -- every adjacent
+    gap among ranks 1..k+1 is above `gap`, or (with `structural`) exactly 0 between two candidates that tie BY CONSTRUCTION.
+    `structural` (M,S): bool marks the out-of-image taps of a zero-padded window (score exactly 0 in the reference); an integer
+    tensor gives tie classes -- two candidates tie by construction when they carry the same non-zero class (e.g. the same tap of one
+    key frame held in two slots).  Needs nothing but the reference, so the share of checkable queries is a CPU-side fact."""
+    dv, di, finite, gaps = _ranked(dense, k)
+    return _clear_columns(di, finite, gaps, gap, structural)
+
+
 def check_topk(dense: torch.Tensor, idx: torch.Tensor, score: torch.Tensor, k: int,
-               tol: float = 1e-3, gap: float = 1e-5) -> dict:
+               tol: float = 1e-3, gap: float = 1e-5, structural: Optional[torch.Tensor] = None) -> dict:
     """Validate (idx, score) (S,k) against the dense slab `dense` (M,S) (ideally float64).
 
     * every reported score is within `tol` of dense[idx]                       (score parity)
     * every selected index is a legitimate top-k member: dense[idx] >= kth_dense - tol
     * on columns whose ranks 1..k+1 are separated by more than `gap` in `dense`,
       idx must equal the canonical dense top-k EXACTLY (bit-exact index parity)
-    Returns counts; raises AssertionError on violation.
+    * `structural` (optional, see checkable_queries): an exact tie between two candidates that tie by construction does not exempt
+      the column -- the list must then show them in canonical order (score desc, candidate id asc), the order TopK::accepts and
+      the butterfly arg-max document.  Without it the behaviour is unchanged.
+    Returns counts (`clear` = `checkable` = the columns held to the exact list); raises AssertionError on violation.
     """
     M, S = dense.shape
-    kk = min(k + 1, M)
-    dv, di = topk_canonical(dense, kk)
-    dv, di = dv.t(), di.t()                                       # (S,kk)
+    dv, di, finite, gaps = _ranked(dense, k)                      # (S,kk), (S,kk), (S,k), (S,kk-1)
     got = dense.t().gather(1, idx.clamp_min(0).long())            # (S,k)
-    finite = torch.isfinite(dv[:, :k])
     err = (got - score.to(dense.dtype)).abs()
     err = torch.where(finite & torch.isfinite(got), err, torch.zeros_like(err))
     assert float(err.max()) <= tol, f"score error {float(err.max())} > {tol}"
     kth = dv[:, k - 1:k]
     legit = (got >= kth - tol) | ~finite
     assert bool(legit.all()), "an index outside the tolerance top-k set was selected"
-    gaps = (dv[:, :-1] - dv[:, 1:]).abs()
-    gaps = torch.where(torch.isfinite(gaps), gaps, torch.full_like(gaps, float("inf")))
-    clear = (gaps.min(dim=1).values > gap) & finite.all(1)
+    clear = _clear_columns(di, finite, gaps, gap, structural)     # structural None: every gap above `gap`, as ever
     exact = (idx.long() == di[:, :k]).all(1)
     assert bool(exact[clear].all()), f"{int((~exact[clear]).sum())} clear-gap queries differ in index"
-    return dict(queries=S, clear=int(clear.sum()), exact=int(exact.sum()), max_score_err=float(err.max()))
+    stats = dict(queries=S, clear=int(clear.sum()), exact=int(exact.sum()), max_score_err=float(err.max()))
+    if structural is not None:
+        stats.update(checkable=int(clear.sum()), checkable_mask=clear)
+    return stats

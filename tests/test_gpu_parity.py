@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import fgvc_oracle as O
+from tests import window_cases as WC
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -279,7 +280,11 @@ def test_local_corr_golden(dev, golden):
     idx, logit, weight = ops.local_corr_topk(qf, kf, H, W, R, topk, 0.07)
     o_out, o_idx, o_logit = O.local_corr_topk(q, key.transpose(0, 1), v.transpose(0, 1), R, topk, 0.07)
     assert torch.allclose(logit.cpu(), o_logit, atol=TOL)
-    assert (idx.cpu().long() == o_idx).all(1).float().mean() > 0.98
+    # the exact canonical list on every query whose float64 ranks are clear or tie by construction (zero-padded taps): no share of
+    # queries may differ "for any reason"
+    dense, cls = WC.local_slab(q, key.transpose(0, 1).contiguous(), R, 0.07)
+    st = O.check_topk(dense, idx.cpu().long(), logit.cpu(), topk, tol=TOL, structural=cls)
+    assert st["checkable"] >= 0.98 * H * W, st["checkable"]
     labels = v.permute(1, 2, 3, 0).reshape(K, H * W, -1).contiguous().to(dev)
     out = ops.propagate_topk(labels, torch.arange(K, dtype=torch.int32, device=dev), idx, weight, H, W, H, W,
                              window_L=2 * R + 1)
@@ -309,7 +314,9 @@ def test_c2f_golden(dev, golden):
     vf = v.permute(1, 2, 3, 0).reshape(Tn, -1, v.shape[0]).contiguous().to(dev)
     out, idx, logit = ops.c2f_refine(o_arg.to(dev, torch.int32), qf, kf, vf, H, W, scale, Rf, topk, 0.07)
     assert torch.allclose(logit.cpu(), o_logit, atol=TOL)
-    assert (idx.cpu().long() == o_idx).all(1).float().mean() > 0.98
+    dense, cls, _ = WC.c2f_slab(O.l2_normalize(qfine.double(), 0), O.l2_normalize(kfine.double(), 0), o_arg, H, W, scale, Rf, 0.07)
+    st = O.check_topk(dense, idx.cpu().long(), logit.cpu(), topk, tol=TOL, structural=cls)      # the exact canonical list, padded taps included
+    assert st["checkable"] >= 0.98 * H * W, st["checkable"]
     assert torch.allclose(out.cpu(), T(g["out"])[0].flatten(1).t(), atol=TOL)
 
 
