@@ -404,100 +404,11 @@ def pad_divide_by(h: int, w: int, d: int) -> Tuple[Tuple[int, int], Tuple[int, i
     return (hp, wp), (lw, wp - w - lw, lh, hp - h - lh)
 
 
-def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
-                    out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
-                    stats_out: Optional[list] = None, events: Optional[dict] = None) -> torch.Tensor:
-    """Semi-supervised VOS for one clip (vanilla_tracker.py:663-830 with VanillaTracker's affinity, :366-378).
-    feats_hwc: the clip's bank as run_affinity takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame
-    index map; pad = (left, right, top, bottom) as pad_divide_by gives it; out_shape = (h0, w0).
-    Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
-    resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output).
-    `events`: torch.cuda.Events keyed 'labels', 'affinity', 'propagation', 'readout', 'end', recorded before each phase."""
-    T, dev = feats_hwc.shape[0], feats_hwc.device
-    hp, wp = seg_map.shape
-    lw, uw, lh, uh = pad
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    rec("labels")
-    C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
-    bank = torch.zeros((T, Hf * Wf, C), device=dev, dtype=torch.float32)
-    ops.seg_onehot_labels(seg_map, Hf, Wf, C, out=bank[0])
-    rec("affinity")
-    plan = plan_clip(T, [0], cfg)
-    tk = run_affinity(feats_hwc, Hf, Wf, plan, cfg, channels=channels)
-    if stats_out is not None and tk.refine_stats is not None:
-        stats_out.append(tk.refine_stats)
-    rec("propagation")
-    soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
-    for f in range(1, T):
-        row = tk.row(plan.out_rows[(0, f)])
-        ops.propagate_topk(bank, tk.slot_frame[row], tk.idx[row], tk.weight[row], Hf, Wf, Hf, Wf, out=soft[f])
-        if cfg.hard_prop:
-            ops.seg_hard_onehot(soft[f], out=bank[f])
-    rec("readout")
-    masks = torch.empty((T, *out_shape), device=dev, dtype=torch.uint8)
-    if T > 1:
-        ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[1:])
-    # frame 0: the unpadded input map, nearest-resized to the output size (:708-711)
-    ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]
-    masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
-    rec("end")
-    return masks
-
-
-def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                       out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
-                       stats_out: Optional[list] = None, events: Optional[dict] = None) -> torch.Tensor:
-    """Soft first-frame labels read out as joint coordinates for one clip (vanilla_tracker.py:663-830 with a 4-D map and
-    test_cfg.coords=True, VanillaTracker's affinity).  feats_hwc: the clip's bank as run_affinity takes it, encoded from the padded
-    frames; heat (K, hm, wm) f32 | f64 on the device, the map BEFORE its own padding map_pad = (left, right, top, bottom) (pad_divide_by of
-    the map's size, :672); out_shape = (h0, w0).  Returns (2, K, T) float64 on the device = img2coord of the stacked maps (:814-818).
-    K is the map's first dimension: no host read.  The propagation is the mask path's soft one with P = K (no min-max normalisation,
-    :785 applies to index maps only).  `events`: as propagate_masks."""
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    bank = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels=channels, stats_out=stats_out, events=events)
-    rec("readout")
-    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
-    rec("end")
-    return coords
-
-
-def propagate_soft_bank(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                        cfg: TrackerConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
-                        events: Optional[dict] = None) -> torch.Tensor:
-    """The part propagate_heatmaps and propagate_softmaps share: first-frame labels, affinity and the sweep.  Returns the label bank
-    (T, HfWf, K) f32 both read-outs start from.  Records the events 'labels', 'affinity', 'propagation'."""
-    T, dev = feats_hwc.shape[0], feats_hwc.device
-    K = heat.shape[0]
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    rec("labels")
-    bank = torch.zeros((T, Hf * Wf, K), device=dev, dtype=torch.float32)
-    ops.seg_soft_labels(heat, map_pad, Hf, Wf, out=bank[0])
-    rec("affinity")
-    plan = plan_clip(T, [0], cfg)
-    tk = run_affinity(feats_hwc, Hf, Wf, plan, cfg, channels=channels)
-    if stats_out is not None and tk.refine_stats is not None:
-        stats_out.append(tk.refine_stats)
-    rec("propagation")
-    for f in range(1, T):
-        row = tk.row(plan.out_rows[(0, f)])
-        ops.propagate_topk(bank, tk.slot_frame[row], tk.idx[row], tk.weight[row], Hf, Wf, Hf, Wf, out=bank[f])
-    return bank
-
-
-def propagate_softmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                       out_shape: Tuple[int, int], cfg: TrackerConfig, channels: Optional[int] = None,
-                       stats_out: Optional[list] = None, events: Optional[dict] = None,
-                       frames: Optional[Tuple[int, int]] = None) -> torch.Tensor:
-    """propagate_heatmaps with the maps themselves as the result (the reference's return value without `coords`, :770-784, :800-803):
-    (T, K, h0, w0) on the device, or the rows `frames` = (f_begin, f_end) of it, float64 iff `heat` is float64 (np.stack of a float64
-    frame 0 with float32 later frames).  Same bank, same field as the coordinate read-out: ops.softmap_readout writes what
-    ops.heatmap_coords scans.  The whole stack is T K h0 w0 values: for a host-bound result see softmaps_to_host."""
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    bank = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels=channels, stats_out=stats_out, events=events)
-    rec("readout")
-    maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=frames)
-    rec("end")
-    return maps
+def _record(events: Optional[dict], key: str) -> None:
+    """The label-map functions' `events`: torch.cuda.Events keyed 'labels', 'affinity', 'propagation', 'readout', 'end', each recorded
+    immediately before its phase ('end' after the last one).  None: nothing is recorded."""
+    if events is not None:
+        events[key].record()
 
 
 MAPS_BUDGET = 512 << 20           # bytes of full-resolution maps held on the device at once by softmaps_to_host
@@ -515,20 +426,19 @@ def plan_map_chunks(n_frames: int, K: int, out_shape: Tuple[int, int], itemsize:
 
 def softmaps_to_host(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, map_pad: Tuple[int, int, int, int],
                      out_shape: Tuple[int, int], budget: int = MAPS_BUDGET, events: Optional[dict] = None):
-    """The (T, K, h0, w0) stack of a propagated bank (propagate_soft_bank / propagate_soft_bank_local) as a numpy array, in heat's dtype.
+    """The (T, K, h0, w0) stack of a propagated bank (propagate_soft_bank) as a numpy array, in heat's dtype.
     The read-out runs over plan_map_chunks' frame ranges into ONE reused device buffer of at most `budget` bytes; each chunk is copied
     into the host array before the buffer is written again (the copy is synchronous: no overlap with the next chunk's read-out).
     `events`: 'readout' is recorded before the first chunk and 'end' after the last copy."""
     T, K = bank.shape[0], heat.shape[0]
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
     chunks = plan_map_chunks(T, K, out_shape, heat.element_size(), budget)
     host = torch.empty((T, K, *out_shape), dtype=heat.dtype)
     buf = torch.empty((chunks[0][1] - chunks[0][0], K, *out_shape), device=bank.device, dtype=heat.dtype)
-    rec("readout")
+    _record(events, "readout")
     for f0, f1 in chunks:
         ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=(f0, f1), out=buf[:f1 - f0])
         host[f0:f1].copy_(buf[:f1 - f0])
-    rec("end")
+    _record(events, "end")
     return host.numpy()
 
 
@@ -665,91 +575,136 @@ def run_local_affinity(feats_hwc: torch.Tensor, Hf: int, Wf: int, plan: LocalPla
     return idx, logit, weight
 
 
-def _local_sweep(bank: torch.Tensor, soft: torch.Tensor, plan: LocalPlan, idx, weight, Hf: int, Wf: int, cfg: LocalConfig) -> None:
-    """Frames 1.. in order: soft[f] = top-k window weights x the label bank of the row's slot frames; bank[f] = one_hot(argmax) of it under
-    hard_prop (soft may be bank)."""
-    _, slot_frame = plan.tables(bank.device)
-    for f in range(1, plan.n_frames):
-        ops.propagate_topk(bank, slot_frame[f - 1], idx[f - 1], weight[f - 1], Hf, Wf, Hf, Wf, window_L=cfg.window, out=soft[f])
-        if cfg.hard_prop:
+# ---- label maps: one sweep, two affinities (vanilla_tracker.py:663-830) -------------------------------------------------------------------
+#
+# Masks, heat maps and soft maps are one algorithm: seed frame 0's labels, compute the affinity, sweep frames 1 .. T-1, read out.  The
+# configuration's type picks the affinity: a TrackerConfig VanillaTracker's dense (disc-masked) one (:366-378), a LocalConfig
+# HRVanillaTracker's local window.  Keywords every entry point takes:
+#   channels, stats_out   dense only: the encoder's un-padded channel count (run_pairs), and a list that receives the refining merge's
+#                         counters (DeviceTopk.refine_stats).  The local window reads neither and appends nothing;
+#   affinity_stats        local only: run_local_affinity's `stats` dict.  The dense affinity leaves it alone;
+#   events                _record's.
+
+@dataclass
+class LabelSweep:
+    """What the sweep reads: output frame f takes row f - 1 of each tensor."""
+    slot_frame: torch.Tensor   # (T-1, t_max) int32  clip frame per key slot
+    idx: torch.Tensor          # (T-1, HW, k) int32  slot*HW + pixel (dense), slot * L^2 + tap (local window)
+    weight: torch.Tensor       # (T-1, HW, k)
+    window_L: int              # 0 = dense candidates, else the window's side L = cfg.window
+
+
+def label_affinity(feats_hwc: torch.Tensor, Hf: int, Wf: int, T: int, cfg, channels: Optional[int] = None,
+                   stats_out: Optional[list] = None, affinity_stats: Optional[dict] = None) -> LabelSweep:
+    """The affinity of a clip whose labels all start at frame 0, on the route `cfg`'s type names."""
+    if isinstance(cfg, LocalConfig):
+        plan = plan_local_clip(T, cfg, Hf * Wf)
+        idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
+        return LabelSweep(plan.tables(feats_hwc.device)[1], idx, weight, cfg.window)
+    plan = plan_clip(T, [0], cfg)
+    tk = run_affinity(feats_hwc, Hf, Wf, plan, cfg, channels=channels)
+    if stats_out is not None and tk.refine_stats is not None:
+        stats_out.append(tk.refine_stats)
+    assert [tk.row(plan.out_rows[(0, f)]) for f in range(1, T)] == list(range(T - 1))     # one group from frame 0: row f - 1 is frame f
+    return LabelSweep(tk.slot_frame, tk.idx, tk.weight, 0)
+
+
+def _sweep_labels(bank: torch.Tensor, soft: torch.Tensor, sw: LabelSweep, Hf: int, Wf: int, hard_prop: bool = False) -> None:
+    """Frames 1.. in order: soft[f] = top-k weights x the label bank of the row's slot frames; under hard_prop bank[f] = one_hot(argmax) of
+    it (vanilla_tracker.py:81, :763-769), else `soft` is `bank`."""
+    for f in range(1, bank.shape[0]):
+        ops.propagate_topk(bank, sw.slot_frame[f - 1], sw.idx[f - 1], sw.weight[f - 1], Hf, Wf, Hf, Wf, window_L=sw.window_L, out=soft[f])
+        if hard_prop:
             ops.seg_hard_onehot(soft[f], out=bank[f])
 
 
-def propagate_masks_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
-                          out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
-                          events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
-    """propagate_masks (same arguments, outputs, one host read of C, `events`) on HRVanillaTracker's own affinity.  The feature grid is
-    whatever the encoder made of the padded frame: (Hf, Wf) need not divide (hp, wp).  `stats_out`: the dense path's refining-merge
-    counters have no counterpart here; nothing is appended.  `affinity_stats`: run_local_affinity's `stats`."""
-    T, dev = feats_hwc.shape[0], feats_hwc.device
+def _mask_readout(soft: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
+                  out_shape: Tuple[int, int], norm_mask: bool) -> torch.Tensor:
+    """(T, h0, w0) uint8: the argmax of the soft logits for frames 1.. (:772-802); frame 0 is the unpadded input map, nearest-resized to
+    the output size (:708-711)."""
+    T = soft.shape[0]
     hp, wp = seg_map.shape
     lw, uw, lh, uh = pad
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    rec("labels")
-    C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
-    bank = torch.zeros((T, Hf * Wf, C), device=dev, dtype=torch.float32)
-    ops.seg_onehot_labels(seg_map, Hf, Wf, C, out=bank[0])
-    rec("affinity")
-    plan = plan_local_clip(T, cfg, Hf * Wf)
-    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
-    rec("propagation")
-    soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
-    _local_sweep(bank, soft, plan, idx, weight, Hf, Wf, cfg)
-    rec("readout")
-    masks = torch.empty((T, *out_shape), device=dev, dtype=torch.uint8)
+    masks = torch.empty((T, *out_shape), device=soft.device, dtype=torch.uint8)
     if T > 1:
-        ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[1:])
-    ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]      # frame 0: the unpadded map, nearest-resized (:708-711)
+        ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, norm_mask, out=masks[1:])
+    ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]
     masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
-    rec("end")
     return masks
 
 
-def propagate_heatmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                             out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
-                             events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
-    """propagate_heatmaps (same arguments and (2, K, T) f64 output; frame 0 = the padded map, not unpadded) on HRVanillaTracker's own
-    affinity.  `stats_out`, `affinity_stats`: as propagate_masks_local."""
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    bank = propagate_soft_bank_local(feats_hwc, Hf, Wf, heat, map_pad, cfg, events=events, affinity_stats=affinity_stats)
-    rec("readout")
+def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
+                    out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
+                    events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """Semi-supervised VOS for one clip.  feats_hwc: the clip's bank as run_affinity (TrackerConfig) or run_local_affinity (LocalConfig)
+    takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame index map; pad = (left, right, top, bottom) as
+    pad_divide_by gives it; out_shape = (h0, w0).  On the local window the feature grid is whatever the encoder made of the padded
+    frame: (Hf, Wf) need not divide (hp, wp).
+    Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
+    resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output)."""
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    _record(events, "labels")
+    C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
+    bank = torch.zeros((T, Hf * Wf, C), device=dev, dtype=torch.float32)
+    ops.seg_onehot_labels(seg_map, Hf, Wf, C, out=bank[0])
+    _record(events, "affinity")
+    sw = label_affinity(feats_hwc, Hf, Wf, T, cfg, channels, stats_out, affinity_stats)
+    _record(events, "propagation")
+    soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
+    _sweep_labels(bank, soft, sw, Hf, Wf, cfg.hard_prop)
+    _record(events, "readout")
+    masks = _mask_readout(soft, Hf, Wf, seg_map, pad, out_shape, cfg.norm_mask)
+    _record(events, "end")
+    return masks
+
+
+def propagate_soft_bank(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int], cfg,
+                        channels: Optional[int] = None, stats_out: Optional[list] = None, events: Optional[dict] = None,
+                        affinity_stats: Optional[dict] = None) -> Tuple[torch.Tensor, LabelSweep]:
+    """The part propagate_heatmaps and propagate_softmaps share: first-frame labels, affinity and the sweep.  heat (K, hm, wm) f32 | f64 on
+    the device, the map BEFORE its own padding map_pad = (left, right, top, bottom) (pad_divide_by of the map's size, :672).  Returns the
+    label bank (T, HfWf, K) f32 both read-outs start from, and the LabelSweep it was swept with.  K is the map's first dimension: no
+    host read; no min-max normalisation (:785 applies to index maps only).  Records the events 'labels', 'affinity', 'propagation'.
+    hard_prop is refused on either route: the reference's F.one_hot without num_classes fails on soft labels (:762-768)."""
+    if cfg.hard_prop:
+        raise NotImplementedError("propagate_soft_bank: hard_prop with soft labels")
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    _record(events, "labels")
+    bank = torch.zeros((T, Hf * Wf, heat.shape[0]), device=dev, dtype=torch.float32)
+    ops.seg_soft_labels(heat, map_pad, Hf, Wf, out=bank[0])
+    _record(events, "affinity")
+    sw = label_affinity(feats_hwc, Hf, Wf, T, cfg, channels, stats_out, affinity_stats)
+    _record(events, "propagation")
+    _sweep_labels(bank, bank, sw, Hf, Wf)
+    return bank, sw
+
+
+def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                       out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
+                       events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """Soft first-frame labels read out as joint coordinates for one clip (test_cfg.coords=True): propagate_soft_bank's arguments and
+    out_shape = (h0, w0).  Returns (2, K, T) float64 on the device = img2coord of the stacked maps (:814-818); frame 0 is the padded map,
+    not unpadded (:712-716)."""
+    bank, _ = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels, stats_out, events, affinity_stats)
+    _record(events, "readout")
     coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
-    rec("end")
+    _record(events, "end")
     return coords
 
 
-def propagate_soft_bank_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                              cfg: LocalConfig, events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
-    """propagate_soft_bank on HRVanillaTracker's own affinity: the part propagate_heatmaps_local and propagate_softmaps_local share."""
-    if cfg.hard_prop:
-        raise NotImplementedError("propagate_heatmaps_local: hard_prop with soft labels")
-    T, dev = feats_hwc.shape[0], feats_hwc.device
-    K = heat.shape[0]
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    rec("labels")
-    bank = torch.zeros((T, Hf * Wf, K), device=dev, dtype=torch.float32)
-    ops.seg_soft_labels(heat, map_pad, Hf, Wf, out=bank[0])
-    rec("affinity")
-    plan = plan_local_clip(T, cfg, Hf * Wf)
-    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, affinity_stats)
-    rec("propagation")
-    _local_sweep(bank, bank, plan, idx, weight, Hf, Wf, cfg)
-    return bank
-
-
-def propagate_softmaps_local(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
-                             out_shape: Tuple[int, int], cfg: LocalConfig, stats_out: Optional[list] = None,
-                             events: Optional[dict] = None, affinity_stats: Optional[dict] = None,
-                             frames: Optional[Tuple[int, int]] = None) -> torch.Tensor:
-    """propagate_softmaps (same arguments and (T, K, h0, w0) output) on HRVanillaTracker's own affinity.  `stats_out` is accepted for
-    the dense function's signature and ignored (nothing is appended, as in propagate_masks_local); `affinity_stats`: run_local_affinity's."""
-    rec = (lambda k: events[k].record()) if events is not None else (lambda k: None)
-    bank = propagate_soft_bank_local(feats_hwc, Hf, Wf, heat, map_pad, cfg, events=events, affinity_stats=affinity_stats)
-    rec("readout")
+def propagate_softmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
+                       out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
+                       events: Optional[dict] = None, frames: Optional[Tuple[int, int]] = None,
+                       affinity_stats: Optional[dict] = None) -> torch.Tensor:
+    """propagate_heatmaps with the maps themselves as the result (the reference's return value without `coords`, :770-784, :800-803):
+    (T, K, h0, w0) on the device, or the rows `frames` = (f_begin, f_end) of it, float64 iff `heat` is float64 (np.stack of a float64
+    frame 0 with float32 later frames).  Same bank, same field as the coordinate read-out: ops.softmap_readout writes what
+    ops.heatmap_coords scans.  The whole stack is T K h0 w0 values: for a host-bound result see softmaps_to_host."""
+    bank, _ = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels, stats_out, events, affinity_stats)
+    _record(events, "readout")
     maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape, frames=frames)
-    rec("end")
+    _record(events, "end")
     return maps
-
 
 # ---- predicted visibility: the forward-backward cycle check (DESIGN.md section 13) -------------------------------------------------------
 #

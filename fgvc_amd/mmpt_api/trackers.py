@@ -251,32 +251,20 @@ class VanillaTracker(BaseTracker):
         """rgbs (1,T,3,h,w), query_points (1,P,3)=(t,x,y), trajectories (1,T,P,2), visibilities (1,T,P).
         Called with imgs= / ref_seg_map= / img_meta= (what BaseModel.forward(test_mode=True, **data) passes for the reference's mask
         datasets) it propagates segmentation masks instead: forward_test_seg."""
-        if imgs is not None or ref_seg_map is not None or img_meta is not None:
-            if rgbs is not None or query_points is not None:
-                raise TypeError("VanillaTracker.forward_test: give either rgbs= / query_points= (points) or imgs= / ref_seg_map= / img_meta= (masks)")
+        if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
-        if rgbs is None or query_points is None:
-            raise TypeError("VanillaTracker.forward_test: missing rgbs / query_points")
         if not rgbs.is_cuda:
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
         assert rgbs.shape[0] == 1, "batch size must be 1 (vanilla_tracker.py:134)"
         cfg = self.engine_config()
+        if not cfg.regroup:
+            # single group that starts at frame 0 regardless of the query times (vanilla_tracker.py:302-303)
+            return self.forward_test_main(rgbs, query_points, trajectories, visibilities)
         occ = self._occlusion()
         self.last_cycle_error = None
         T, h, w = rgbs.shape[1], rgbs.shape[-2], rgbs.shape[-1]
         dev = rgbs.device
         qp = query_points[0]
-        if not cfg.regroup:
-            # single group that starts at frame 0 regardless of the query times (vanilla_tracker.py:302-303)
-            feats, Hf, Wf = self.get_feats_hwc(rgbs[0], split=True)
-            plan = engine.plan_clip(T, [0], cfg)
-            tk = engine.run_affinity(feats, Hf, Wf, plan, cfg, channels=self.feat_channels)
-            self._refine_stats = [tk.refine_stats] if tk.refine_stats is not None else None
-            _, coords = engine.run_propagation(tk, 0, qp[:, 1:].to(dev, torch.float32), Hf, Wf, h, w, cfg)
-            traj_pred = coords.unsqueeze(0)                                   # float64, like torch.from_numpy(...)
-            vis_pred = self._visibility_from_frame0(feats, Hf, Wf, w, coords, qp, visibilities, occ)
-            self._check_kernels()
-            return trajectories, visibilities, traj_pred, vis_pred, query_points
         t_min = int(qp[:, 0].min().item())
         # frames before the earliest query time are never used by any group
         feats, Hf, Wf = self.get_feats_hwc(rgbs[0, t_min:], split=True)
@@ -299,6 +287,18 @@ class VanillaTracker(BaseTracker):
             vis_pred = self._visibility_like(visibilities, vis, err)
         self._check_kernels()
         return (trajectories[:, :, order], visibilities[:, :, order], traj_pred, vis_pred, query_points[:, order])
+
+    def _label_call(self, rgbs, query_points, imgs, ref_seg_map, img_meta) -> bool:
+        """forward_test's two call forms: True for the label-map one (imgs= / ref_seg_map= / img_meta=), False for points; TypeError for a
+        mixture of the two or a points call without its tensors."""
+        name = type(self).__name__
+        if imgs is not None or ref_seg_map is not None or img_meta is not None:
+            if rgbs is not None or query_points is not None:
+                raise TypeError(f"{name}.forward_test: give either rgbs= / query_points= (points) or imgs= / ref_seg_map= / img_meta= (masks)")
+            return True
+        if rgbs is None or query_points is None:
+            raise TypeError(f"{name}.forward_test: missing rgbs / query_points")
+        return False
 
     def output_stride(self) -> int:
         """The encoder's output stride d (frame size / feature size): the mask path pads the frames to a multiple of it
@@ -353,18 +353,16 @@ class VanillaTracker(BaseTracker):
 
     def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
         """forward_test_seg past its refusals: index maps -> [ (T, h0, w0) float64 ]."""
-        cfg = self.engine_config()
+        cfg = self._label_config()
         h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        d = self.output_stride()
-        (hp, wp), pad = engine.pad_divide_by(h, w, d)
+        _, pad = engine.pad_divide_by(h, w, self._pad_unit())
         frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
         seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
-        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
-        if (Hf * d, Wf * d) != (hp, wp):
-            raise RuntimeError(f"fgvc_amd: features {Hf}x{Wf} are not the padded frame {hp}x{wp} / {d}")
-        stats = []
-        masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats)
+        feats, Hf, Wf = self._label_feats(frames, index_map=True)
+        stats, self.label_stats = [], {}
+        masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats,
+                                       affinity_stats=self.label_stats)
         self._refine_stats = stats or None
         self._check_kernels()
         return [masks.cpu().numpy().astype("float64")]
@@ -393,12 +391,33 @@ class VanillaTracker(BaseTracker):
             raise ValueError("ref_seg_map: the soft labels hold a non-finite value")
         return self._seg_softmaps(imgs, heat, img_meta) if return_maps else self._seg_heatmaps(imgs, heat, img_meta)
 
+    # The label-map methods below are shared with HRVanillaTracker, which overrides these three hooks only.  After a call `label_stats` holds
+    # what the affinity reported (the local window's route, chunks and workspace_bytes; nothing on the dense one) and `_refine_stats` the
+    # refining merge's counters (dense only) until _check_kernels reads them.
     def _label_config(self):
-        """The configuration the label-map path propagates with (its `hard_prop` is read before the heat-map path's other checks)."""
+        """The configuration the label-map path propagates with (its `hard_prop` is read before the heat-map path's other checks); its type
+        names the engine's affinity."""
         return self.engine_config()
 
-    def _heat_inputs(self, imgs, heat, img_meta, unit):
-        """Frames and map each padded by its own pad_divide_by with `unit` (:671-672): the padded frames (T, 3, hp, wp), the map's pad, (h0, w0)."""
+    def _pad_unit(self) -> int:
+        """What frames and maps are padded to a multiple of (pad_divide_by): here the encoder's output stride, so that the feature grid is
+        exactly the padded size / d."""
+        return self.output_stride()
+
+    def _label_feats(self, frames: torch.Tensor, index_map: bool = False):
+        """frames (T,3,hp,wp) padded -> the bank engine.run_affinity takes, Hf, Wf.  index_map: the index-map read-out needs the feature
+        grid to be the padded frame / d."""
+        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
+        if index_map:
+            d, (hp, wp) = self._pad_unit(), frames.shape[-2:]
+            if (Hf * d, Wf * d) != (hp, wp):
+                raise RuntimeError(f"fgvc_amd: features {Hf}x{Wf} are not the padded frame {hp}x{wp} / {d}")
+        return feats, Hf, Wf
+
+    def _heat_inputs(self, imgs, heat, img_meta):
+        """Frames and map each padded by its own pad_divide_by with _pad_unit() (:671-672): the padded frames (T, 3, hp, wp), the map's pad,
+        (h0, w0)."""
+        unit = self._pad_unit()
         h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
         _, pad = engine.pad_divide_by(h, w, unit)
@@ -408,11 +427,12 @@ class VanillaTracker(BaseTracker):
 
     def _seg_heatmaps(self, imgs, heat, img_meta):
         """_forward_test_heatmap past its refusals: heat (K, hm, wm) on the device -> [ (2, K, T) float64 ]."""
-        cfg = self.engine_config()
-        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.output_stride())
-        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
-        stats = []
-        coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, out_shape, cfg, channels=self.feat_channels, stats_out=stats)
+        cfg = self._label_config()
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta)
+        feats, Hf, Wf = self._label_feats(frames)
+        stats, self.label_stats = [], {}
+        coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, out_shape, cfg, channels=self.feat_channels, stats_out=stats,
+                                           affinity_stats=self.label_stats)
         self._refine_stats = stats or None
         self._check_kernels()
         return [coords.cpu().numpy()]
@@ -423,12 +443,13 @@ class VanillaTracker(BaseTracker):
     def _seg_softmaps(self, imgs, heat, img_meta):
         """_forward_test_heatmap(return_maps=True) past its refusals -> [ (T, K, h0, w0) in heat's dtype ].  The bank is propagated once;
         the read-out goes to the host in chunks of at most test_cfg.maps_budget bytes of device memory (engine.softmaps_to_host)."""
-        cfg = self.engine_config()
-        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.output_stride())
+        cfg = self._label_config()
+        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta)
         engine.plan_map_chunks(frames.shape[0], heat.shape[0], out_shape, heat.element_size(), self._maps_budget())   # refuse before any work
-        feats, Hf, Wf = self.get_feats_hwc(frames, split=True)
-        stats = []
-        bank = engine.propagate_soft_bank(feats, Hf, Wf, heat, map_pad, cfg, channels=self.feat_channels, stats_out=stats)
+        feats, Hf, Wf = self._label_feats(frames)
+        stats, self.label_stats = [], {}
+        bank, _ = engine.propagate_soft_bank(feats, Hf, Wf, heat, map_pad, cfg, channels=self.feat_channels, stats_out=stats,
+                                             affinity_stats=self.label_stats)
         self._refine_stats = stats or None
         maps = engine.softmaps_to_host(bank, heat, Hf, Wf, map_pad, out_shape, self._maps_budget())
         self._check_kernels()
@@ -592,7 +613,7 @@ class HRVanillaTracker(VanillaTracker):
                                   hard_prop=bool(g("hard_prop", False)), norm_mask=bool(g("norm_mask", True)),
                                   pair_precision=g("pair_precision", "auto"), pair_budget=int(g("pair_budget", engine.LOCAL_PAIR_BUDGET)))
 
-    def _label_feats(self, frames: torch.Tensor):
+    def _label_feats(self, frames: torch.Tensor, index_map: bool = False):
         """frames (T,3,hp,wp) padded -> f32 rows (T, HfWf, C'), L2-normalised iff `with_norm`, Hf, Wf: every frame encoded once (the reference
         re-encodes the key frames at every query frame, local_attention.py:918, :947: the same features)."""
         if self.head is not None or self.stride_sample:
@@ -600,57 +621,18 @@ class HRVanillaTracker(VanillaTracker):
                                       "vanilla_tracker.py:753); a head or stride_sample is not supported there")
         return self.get_feats_hwc(frames, split=False)
 
-    def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
-        """Index maps: the pad unit is the tracker's own `stride` (vanilla_tracker.py:671-672), not the encoder's output stride; the feature
-        grid is whatever the encoder makes of the padded frame."""
-        cfg = self._label_config()
-        h, w = imgs.shape[-2:]
-        h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        _, pad = engine.pad_divide_by(h, w, self.stride)
-        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
-        seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
-        feats, Hf, Wf = self._label_feats(frames)
-        self.label_stats = {}                                        # the affinity's route, chunks and pair-list bytes of this call
-        masks = engine.propagate_masks_local(feats, Hf, Wf, seg, pad, (h0, w0), cfg, affinity_stats=self.label_stats)
-        self._refine_stats = None
-        self._check_kernels()
-        return [masks.cpu().numpy().astype("float64")]
-
-    def _seg_heatmaps(self, imgs, heat, img_meta):
-        """Heat maps (coords=True): frames and map each padded by pad_divide_by with the tracker's `stride` (:671-672)."""
-        cfg = self._label_config()
-        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.stride)
-        feats, Hf, Wf = self._label_feats(frames)
-        self.label_stats = {}
-        coords = engine.propagate_heatmaps_local(feats, Hf, Wf, heat, map_pad, out_shape, cfg, affinity_stats=self.label_stats)
-        self._refine_stats = None
-        self._check_kernels()
-        return [coords.cpu().numpy()]
-
-    def _seg_softmaps(self, imgs, heat, img_meta):
-        """The maps themselves (return_maps=True): as _seg_heatmaps up to the bank, then VanillaTracker._seg_softmaps' chunked read-out."""
-        cfg = self._label_config()
-        frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta, self.stride)
-        engine.plan_map_chunks(frames.shape[0], heat.shape[0], out_shape, heat.element_size(), self._maps_budget())
-        feats, Hf, Wf = self._label_feats(frames)
-        self.label_stats = {}
-        bank = engine.propagate_soft_bank_local(feats, Hf, Wf, heat, map_pad, cfg, affinity_stats=self.label_stats)
-        self._refine_stats = None
-        maps = engine.softmaps_to_host(bank, heat, Hf, Wf, map_pad, out_shape, self._maps_budget())
-        self._check_kernels()
-        return [maps]
+    def _pad_unit(self) -> int:
+        """The tracker's own `stride` (vanilla_tracker.py:671-672), not the encoder's output stride; the feature grid is whatever the encoder
+        makes of the padded frame."""
+        return self.stride
 
     @torch.no_grad()
     def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,
                      iteration=None, imgs=None, ref_seg_map=None, img_meta=None, **kw):
         """Points: rgbs / query_points / trajectories / visibilities (below).  Label maps (imgs= / ref_seg_map= / img_meta=, what the
         reference's mask and pose datasets pass): forward_test_seg, on this tracker's local-window affinity."""
-        if imgs is not None or ref_seg_map is not None or img_meta is not None:
-            if rgbs is not None or query_points is not None:
-                raise TypeError("HRVanillaTracker.forward_test: give either rgbs= / query_points= (points) or imgs= / ref_seg_map= / img_meta= (masks)")
+        if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
-        if rgbs is None or query_points is None:
-            raise TypeError("HRVanillaTracker.forward_test: missing rgbs / query_points")
         if not self.test_cfg.get("with_first", False):
             return self.forward_test_main(rgbs, query_points, trajectories, visibilities)
         # inherited regrouping (vanilla_tracker.py:246-299): one sweep per distinct query time over the tail of the clip; the

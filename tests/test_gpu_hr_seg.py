@@ -158,8 +158,8 @@ def test_chunking_is_invisible(dev):
         assert torch.equal(a, b)
     seg = torch.zeros(H * 2, W * 2, dtype=torch.uint8, device=dev)
     seg[10:40, 20:70], seg[50:80, 60:110] = 1, 2
-    m1 = engine.propagate_masks_local(feats, H, W, seg, (0, 0, 0, 0), (H * 2, W * 2), cfg)
-    m2 = engine.propagate_masks_local(feats, H, W, seg, (0, 0, 0, 0), (H * 2, W * 2), cfgs)
+    m1 = engine.propagate_masks(feats, H, W, seg, (0, 0, 0, 0), (H * 2, W * 2), cfg)
+    m2 = engine.propagate_masks(feats, H, W, seg, (0, 0, 0, 0), (H * 2, W * 2), cfgs)
     assert torch.equal(m1, m2)
 
 
@@ -266,7 +266,7 @@ def test_masks_match_float64_restatement_480p(dev):
     assert (Hf, Wf) == (240, 427) and feats.dtype == torch.float32 and cfg.radius == R
     seg = torch.from_numpy(seg0).to(dev)
     stats = {}
-    masks = engine.propagate_masks_local(feats, Hf, Wf, seg, (0, 0, 0, 0), (480, 854), cfg, affinity_stats=stats)
+    masks = engine.propagate_masks(feats, Hf, Wf, seg, (0, 0, 0, 0), (480, 854), cfg, affinity_stats=stats)
     assert stats["route"] == "f16x3"
     C = int(ops.seg_max_label(seg, Hf, Wf).item()) + 1
     lab0 = ops.seg_onehot_labels(seg, Hf, Wf, C).double()

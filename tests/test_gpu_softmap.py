@@ -333,7 +333,7 @@ def test_propagate_softmaps_local_matches_restatement(dev, dtype):
     cfg = engine.LocalConfig(temperature=0.07, topk=10, precede_frames=3, radius=R)
     out_shape = (h, w)
     stats = {}
-    got = engine.propagate_softmaps_local(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg, affinity_stats=stats)
+    got = engine.propagate_softmaps(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg, affinity_stats=stats)
     assert stats["route"] in ("f16x3", "f32")
     plan = engine.plan_local_clip(T, cfg, Hf * Wf)
     idx_all, _, weight_all = engine.run_local_affinity(feats, Hf, Wf, plan, cfg)
@@ -351,9 +351,9 @@ def test_propagate_softmaps_local_matches_restatement(dev, dtype):
         val = bank[sf[slot], (ky.clamp(0, Hf - 1) * Wf + kx.clamp(0, Wf - 1))] * inside[..., None]
         bank[f] = (wt[..., None] * val).sum(1)
     _check_clip("propagate_softmaps_local", got, bank, heat, Hf, Wf, map_pad, out_shape, cfg.topk, dev)
-    part = engine.propagate_softmaps_local(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg, frames=(0, 3))
+    part = engine.propagate_softmaps(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg, frames=(0, 3))
     assert torch.equal(part, got[:3])
-    coords = engine.propagate_heatmaps_local(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg).cpu().numpy()
+    coords = engine.propagate_heatmaps(feats, Hf, Wf, heat.to(dev), map_pad, out_shape, cfg).cpu().numpy()
     dec, gap = decode(got)
     clear = gap.T > CLEAR
     assert clear.any() and float(np.abs(dec - coords).max(0)[clear].max()) <= _tol_decode(dtype == torch.float64, out_shape)

@@ -101,7 +101,7 @@ def bench_vos(dev, iters, warmup):
     (hp, wp), pad = engine.pad_divide_by(h, w, model.stride)
     seg = F.pad(seg.to(dev), pad).contiguous()
     frames = F.pad(imgs[0, 0], pad).transpose(0, 1).contiguous()
-    run = lambda feats, Hf, Wf, ev, st: engine.propagate_masks_local(feats, Hf, Wf, seg, pad, (h, w), cfg, events=ev, affinity_stats=st)
+    run = lambda feats, Hf, Wf, ev, st: engine.propagate_masks(feats, Hf, Wf, seg, pad, (h, w), cfg, events=ev, affinity_stats=st)
     feats, Hf, Wf, masks, split, stats = _run(model, frames, run, iters, warmup)
     return {"config": {"frames": T, "size": [h, w], "objects": objects, "feature_grid": [Hf, Wf], "R": cfg.radius, "taps": cfg.window ** 2,
                        "key_slots": cfg.precede_frames + 1, "topk": cfg.topk},
@@ -122,7 +122,7 @@ def bench_jhmdb(dev, iters, warmup):
     _, pad = engine.pad_divide_by(h, w, model.stride)
     _, map_pad = engine.pad_divide_by(h, w, model.stride)
     frames = F.pad(imgs[0, 0], pad).transpose(0, 1).contiguous()
-    run = lambda feats, Hf, Wf, ev, st: engine.propagate_heatmaps_local(feats, Hf, Wf, heat, map_pad, (h, w), cfg, events=ev, affinity_stats=st)
+    run = lambda feats, Hf, Wf, ev, st: engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, (h, w), cfg, events=ev, affinity_stats=st)
     feats, Hf, Wf, coords, split, stats = _run(model, frames, run, iters, warmup)
     return {"config": {"frames": T, "size": [h, w], "joints": K, "feature_grid": [Hf, Wf], "R": cfg.radius, "topk": cfg.topk},
             "route": stats["route"], "chunks": stats["chunks"], "pair_list_mb": round(stats["workspace_bytes"] / 1e6, 1),

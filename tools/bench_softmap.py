@@ -44,7 +44,7 @@ def run(model, dev, T, size, K, out_shape, iters, warmup):
             ev = {k: torch.cuda.Event(enable_timing=True) for k in ("start",) + names}
             ev["start"].record()
             feats, Hf, Wf = model.get_feats_hwc(frames, split=True)
-            bank = engine.propagate_soft_bank(feats, Hf, Wf, heat, map_pad, cfg, channels=model.feat_channels, events=ev)
+            bank, _ = engine.propagate_soft_bank(feats, Hf, Wf, heat, map_pad, cfg, channels=model.feat_channels, events=ev)
             ev["readout"].record()
             maps = ops.softmap_readout(bank, heat, Hf, Wf, map_pad, out_shape)
             ev["end"].record()
