@@ -318,8 +318,10 @@ __global__ __launch_bounds__(256) void softargmax_band_kernel(const float* __res
 //   3. evaluate the pixels of the listed cells, keep those >= tau;
 //   4. rank the survivors (value desc, higher index first among equals): ranks 0-4 are the map's top 5, identical to a full
 //      scan because every pixel >= tau lies in a listed cell.
-// For non-negative maps "sum == 0" <=> M == 0.  Whatever does not fit (negative labels, flat maps whose lists overflow,
-// fewer than 5 evaluated pixels) sets need_scan[map] and is redone by softargmax_band_kernel: slower, never different.
+// For non-negative maps "sum == 0" <=> M == 0, as long as every coarse cell reaches an output pixel with a positive weight: true up to
+// a ratio of 2 (source coordinates are at most 2 apart, each cell's support is 2 wide), not beyond (24 rows -> 8 reads rows 3d + 1 only).
+// Whatever does not fit (negative labels, flat maps whose lists overflow, fewer than 5 evaluated pixels, Hf > 2h or Wf > 2w) sets
+// need_scan[map] and is redone by softargmax_band_kernel: slower, never different.
 // The first frame's analytic Gaussians decrease with distance from the centre: their top 5 are inside a 13 x 13 window.
 // ------------------------------------------------------------------------------------------
 constexpr int RO_CELLS = 1024, RO_CAND = 2048, RO_NEIGH = 1024, RO_BLOCK = 1024;
@@ -366,6 +368,10 @@ __global__ __launch_bounds__(RO_BLOCK) void softargmax_pruned_kernel(const float
   }
   for (int j = tid; j < nbands; j += RO_BLOCK) part_sum[o + j] = 0.f;
   __syncthreads();
+  if (!analytic && (Hf > 2 * h || Wf > 2 * w)) {       // a ratio above 2 skips coarse rows or columns: M > 0 no longer means a non-zero sum
+    if (tid == 0) need_scan[map] = 1;
+    return;
+  }
   float map_max;
   if (analytic) {
     const float cx = gauss_points[2 * pl], cy = gauss_points[2 * pl + 1];
