@@ -39,6 +39,8 @@ int local_merge_plan_launch(const int32_t*, const float*, const int32_t*, int, i
 int topk_coord_launch(const int32_t*, const float*, int, int, int, int, int, float*, hipStream_t);
 int topk_coord_rows_launch(const int32_t*, const float*, int, int, int, int, int, int, float*, hipStream_t);
 int cycle_chase_launch(const float*, const float*, const float*, int, int, int, int, int, float*, float*, hipStream_t);
+int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
+                              hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -576,6 +578,22 @@ int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* st
                  reinterpret_cast<uintptr_t>(back_out)) & 7u) == 0,
                FGVC_ERR_INVALID_ARG, "fgvc_cycle_chase_f32: the (x, y) arrays must be 8-byte aligned");
   return cycle_chase_launch(fields, traj, start_xy, n, P, H, W, scale, back_out, err_out, (hipStream_t)stream);
+}
+
+int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                                int64_t stride_c, int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out,
+                                void* stream) {
+  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_frames_rgb8_to_lab_f32: null pointer");
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_lab_f32: non-positive size (T=%d, %d x %d -> %d x %d)", T, h0, w0, h, w);
+  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_lab_f32: negative pad (%d, %d, %d, %d)", pad_left, pad_right, pad_top, pad_bottom);
+  const long long hp = (long long)pad_top + h + pad_bottom, wp = (long long)pad_left + w + pad_right;
+  // grid.z = T and grid.y = ceil(hp / 4) are 16-bit; a lane's column index 4 * (blockIdx.x * 256 + lane) and hp * wp stay inside an int
+  FGVC_REQUIRE(T <= 65535 && hp <= 4 * 65535ll && wp < (1ll << 30) && hp * wp < (1ll << 31), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels)");
+  return frames_rgb8_to_lab_launch(frames, T, h0, w0, stride_t, stride_y, stride_x, stride_c, h, w, pad_left, pad_right, pad_top, pad_bottom,
+                                   out, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

@@ -20,14 +20,18 @@ class SyntheticTapVid:
     (dx,dy) per frame, so ground-truth trajectories are exact and a tracker's accuracy is measurable.
     occluder=True: a STATIC textured rectangle (OCCLUDER_FRACTION of each side, seeded position and texture) is pasted over the frames
     t >= T // 2 -- after every query time, so that query points stay visible -- and the points under it are marked invisible in
-    `visibilities`.  Everything else (the frames outside the rectangle, points, trajectories, queries) is the occluder=False sample."""
+    `visibilities`.  Everything else (the frames outside the rectangle, points, trajectories, queries) is the occluder=False sample.
+    raw=True: the frames as a decoder would hand them over, `rgbs` (1, T, h, w, 3) uint8 = the same texture quantised to
+    round(128 + 48 x) clamped to 0..255 -- for a tracker whose test_cfg.input = dict(type='rgb8'); the rest as before."""
 
     OCCLUDER_FRACTION = 0.4
 
-    def __init__(self, n_videos=4, frames=8, size=(256, 256), points=8, query_mode="first", seed=0, device="cpu", occluder=False):
+    def __init__(self, n_videos=4, frames=8, size=(256, 256), points=8, query_mode="first", seed=0, device="cpu", occluder=False,
+                 raw=False):
         self.n, self.T, self.h, self.w, self.P = n_videos, frames, size[0], size[1], points
         self.query_mode, self.seed, self.device = query_mode, seed, device
         self.occluder = bool(occluder)
+        self.raw = bool(raw)
 
     def occluder_box(self, i):
         """(t_on, y0, y1, x0, x1) of video i's rectangle: present in frames t_on .. T-1, rows y0:y1, columns x0:x1 (None without one)."""
@@ -77,6 +81,8 @@ class SyntheticTapVid:
         if self.occluder:
             rgbs, vis = self._paste_occluder(i, rgbs, traj, vis)
         d = self.device
+        if self.raw:
+            rgbs = (128.0 + 48.0 * rgbs).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()     # (T,h,w,3)
         return dict(rgbs=rgbs.unsqueeze(0).to(d), query_points=qp.unsqueeze(0).to(d),
                     trajectories=traj.unsqueeze(0).to(d), visibilities=vis.unsqueeze(0).to(d))
 
@@ -128,6 +134,15 @@ def preprocess_tapvid_frames(frames_uint8: torch.Tensor, size=(256, 256)) -> tor
     return ((lab - mean) / std).unsqueeze(0)
 
 
+def _label_imgs(frames_uint8: torch.Tensor, size, device, raw: bool = False) -> torch.Tensor:
+    """(T, h0, w0, 3) uint8 -> the `imgs` of a label-map sample on `device`: (1, 1, 3, T, h, w) float32 through the input contract, or with
+    raw=True the frames themselves, (1, 1, T, h0, w0, 3) uint8 (for test_cfg.input = dict(type='rgb8', size=size))."""
+    if raw:
+        return frames_uint8.to(device).unsqueeze(0).unsqueeze(0)
+    rgbs = preprocess_tapvid_frames(frames_uint8.to(device), size)
+    return rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()
+
+
 # ---- TAP-Vid files (mmpt/datasets/tapvid.py:36-174, tapvid_evaluation_datasets.py:284-395) ---------------------------------
 def _queries_first(occluded: np.ndarray, points: np.ndarray):
     """One query per track at its first visible frame; tracks that are never visible are dropped
@@ -159,9 +174,12 @@ class TapVidPickles:
     {name: video} or [video, ...] (the published tapvid_davis.pkl).  A video = dict(video (T,H,W,3) uint8 frames -- or an
     array of encoded JPEG byte strings, tapvid.py:91-99 --, points (P,T,2) = (x,y) in [0,1], occluded (P,T) bool).
     Frames go through the TAP-Vid input contract (`preprocess_tapvid_frames`: resize to `input_size`, RGB->Lab, normalise),
-    points are scaled to `input_size` pixels (tapvid.py:106-108), queries are sampled by `query_mode` 'first' | 'strided'."""
+    points are scaled to `input_size` pixels (tapvid.py:106-108), queries are sampled by `query_mode` 'first' | 'strided'.
+    raw=True: `rgbs` is the decoded video itself, (1, T, H, W, 3) uint8 on `device` at its own size, for a tracker whose
+    test_cfg.input = dict(type='rgb8', size=input_size) resizes and converts it; everything else as before."""
 
-    def __init__(self, root: str, query_mode: str = "first", input_size=(256, 256), device="cpu"):
+    def __init__(self, root: str, query_mode: str = "first", input_size=(256, 256), device="cpu", raw=False):
+        self.raw = bool(raw)
         if query_mode not in ("first", "strided"):
             raise ValueError(f"Unknown query mode {query_mode}.")                                   # tapvid.py:115
         self.query_mode, self.input_size, self.device = query_mode, tuple(input_size), device
@@ -218,7 +236,10 @@ class TapVidPickles:
                     vis[qt[p], p] = True
         assert bool(vis[qt, torch.arange(P)].all()), "Query points must be visible"                # tapvid.py:160-161
         assert torch.allclose(query_points[:, 1:], traj[qt, torch.arange(P)], atol=1.0)             # tapvid.py:164-168
-        rgbs = preprocess_tapvid_frames(frames.to(self.device), self.input_size)                    # (1,T,3,h,w)
+        if self.raw:
+            rgbs = frames.to(self.device).unsqueeze(0)                                              # (1,T,H,W,3) uint8
+        else:
+            rgbs = preprocess_tapvid_frames(frames.to(self.device), self.input_size)                # (1,T,3,h,w)
         d = self.device
         return dict(rgbs=rgbs, query_points=query_points.unsqueeze(0).to(d), trajectories=traj.unsqueeze(0).to(d),
                     visibilities=vis.float().unsqueeze(0).to(d))
@@ -307,14 +328,19 @@ class JhmdbPoses:
     form="heatmap": the reference's own first-frame label instead (jhmdb_dataset.py:119-141, Resize augmentation.py:790-807): data =
     dict(imgs (1,1,3,T,h,w), ref_seg_map (1, 15, h, w) float64 = one draw_label_map Gaussian (sigma 4) per joint at the video's own
     resolution, resized to the network size by cv2_resize_linear (parity unpinned), img_meta = [dict(original_shape=(h0, w0))]).
-    VanillaTracker.forward_test with test_cfg.coords=True returns the (2, 15, T) coordinates at (h0, w0) directly."""
+    VanillaTracker.forward_test with test_cfg.coords=True returns the (2, 15, T) coordinates at (h0, w0) directly.
+
+    raw=True: the frames stay uint8 at the video's own size on `device` -- rgbs (1, T, h0, w0, 3), imgs (1, 1, T, h0, w0, 3) -- for a
+    tracker whose test_cfg.input = dict(type='rgb8', size=input_size); joints, maps and meta as before."""
     NUM_KEYPOINTS = 15
     SIGMA = 4
 
-    def __init__(self, root: str, list_path: str = None, split: str = "val", input_size=(320, 320), device="cpu", form: str = "points"):
+    def __init__(self, root: str, list_path: str = None, split: str = "val", input_size=(320, 320), device="cpu", form: str = "points",
+                 raw=False):
         if form not in ("points", "heatmap"):
             raise ValueError(f"form={form!r}: 'points' or 'heatmap'")
         self.root, self.input_size, self.device, self.form = root, tuple(input_size), device, form
+        self.raw = bool(raw)
         self.samples = []
         with open(os.path.join(list_path or root, f"{split}_list.txt")) as f:
             for line in f:
@@ -342,13 +368,12 @@ class JhmdbPoses:
         n = min(T, Tg)                                                                                           # :205
         if self.form == "heatmap":
             heat = pose_heatmaps(gt[:, :, 0].T, (h0, w0), self.SIGMA, (h, w))                                   # (15, h, w) f64
-            rgbs = preprocess_tapvid_frames(frames[:n].to(self.device), self.input_size)
-            imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()                                        # (1,1,3,T,h,w)
+            imgs = _label_imgs(frames[:n], self.input_size, self.device, self.raw)                              # (1,1,3,T,h,w)
             data = dict(imgs=imgs, ref_seg_map=torch.from_numpy(heat).unsqueeze(0).to(self.device), img_meta=[dict(original_shape=(h0, w0))])
             return data, dict(gt_poses=gt[:, :, :n], original_shape=(h0, w0))
         traj = torch.from_numpy(gts[:, :, :n]).permute(2, 1, 0).float().contiguous()                             # (T,15,2)
         qp = torch.cat([torch.zeros(self.NUM_KEYPOINTS, 1), traj[0]], 1)                                        # (15,3) = (0,x,y)
-        rgbs = preprocess_tapvid_frames(frames[:n].to(self.device), self.input_size)
+        rgbs = frames[:n].to(self.device).unsqueeze(0) if self.raw else preprocess_tapvid_frames(frames[:n].to(self.device), self.input_size)
         d = self.device
         return dict(rgbs=rgbs, query_points=qp.unsqueeze(0).to(d), trajectories=traj.unsqueeze(0).to(d),
                     visibilities=torch.ones(1, n, self.NUM_KEYPOINTS, device=d)), dict(gt_poses=gt[:, :, :n], original_shape=(h0, w0))
@@ -442,10 +467,14 @@ class BadjaPoses:
 
     form="heatmap": the reference's own first-frame label instead (badja_dataset.py:350-410): data = dict(imgs (1,1,3,T,h,w),
     ref_seg_map (1, J, h, w) float64 = one draw_label_map Gaussian (sigma 3, point (y, x)) per joint on a (h // 2, w // 2) canvas at half
-    the joint coordinates, resized to `size` by cv2_resize_linear (Resize, parity unpinned), img_meta = [dict(original_shape=size)])."""
+    the joint coordinates, resized to `size` by cv2_resize_linear (Resize, parity unpinned), img_meta = [dict(original_shape=size)]).
+
+    raw=True: the frames stay uint8 at their own size on `device` -- rgbs (1, T, h0, w0, 3), imgs (1, 1, T, h0, w0, 3) -- for a tracker whose
+    test_cfg.input = dict(type='rgb8', size=size); joints, maps and meta as before."""
     SIGMA, SCALE = 3, 2
 
-    def __init__(self, root: str, list_path: str = None, size=(320, 512), length: int = -1, device="cpu", form: str = "points"):
+    def __init__(self, root: str, list_path: str = None, size=(320, 512), length: int = -1, device="cpu", form: str = "points", raw=False):
+        self.raw = bool(raw)
         import json
         if form not in ("points", "heatmap"):
             raise ValueError(f"form={form!r}: 'points' or 'heatmap'")
@@ -502,12 +531,11 @@ class BadjaPoses:
         meta = dict(joints=joints, visibles=visibles, segs=segs, original_shape=(h0, w0), name=v["name"])
         if self.form == "heatmap":         # joints (y, x) at the network size, halved, drawn on the half-size canvas (:382-397)
             heat = pose_heatmaps(joints[0][:, ::-1] / self.SCALE, (h // self.SCALE, w // self.SCALE), self.SIGMA, (h, w))
-            rgbs = preprocess_tapvid_frames(frames.to(self.device), self.size)
-            imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()
+            imgs = _label_imgs(frames, self.size, self.device, self.raw)
             return (dict(imgs=imgs, ref_seg_map=torch.from_numpy(heat).unsqueeze(0).to(self.device), img_meta=[dict(original_shape=(h, w))]),
                     meta)
         qp = torch.cat([torch.zeros(J, 1), traj[0]], 1)                                            # (J,3) = (0,x,y)
-        rgbs = preprocess_tapvid_frames(frames.to(self.device), self.size)
+        rgbs = frames.to(self.device).unsqueeze(0) if self.raw else preprocess_tapvid_frames(frames.to(self.device), self.size)
         d = self.device
         return (dict(rgbs=rgbs, query_points=qp.unsqueeze(0).to(d), trajectories=traj.unsqueeze(0).to(d), visibilities=vis.unsqueeze(0).to(d)),
                 dict(joints=joints, visibles=visibles, segs=segs, original_shape=(h0, w0), name=v["name"]))
@@ -554,9 +582,11 @@ class Davis2017:
     PNGs: the palette index is the object id, 0 = background).  Frames go through the RGB->Lab + Normalize contract at their native size
     (no resize).  Item i = (data, meta): data = dict(imgs (1,1,3,T,h,w), ref_seg_map (1,h,w) uint8 = the first annotation,
     img_meta = [dict(original_shape=(h,w))]); meta = dict(name, gt (T,h,w) uint8 -- every annotation the set has, frames without
-    one are all-zero -- n_objects)."""
+    one are all-zero -- n_objects).  raw=True: imgs (1, 1, T, h, w, 3) uint8 on `device`, the decoded frames themselves, for a tracker
+    whose test_cfg.input = dict(type='rgb8'); everything else as before."""
 
-    def __init__(self, root: str, split: str = "val", resolution: str = "480p", device="cpu", max_frames: int = -1):
+    def __init__(self, root: str, split: str = "val", resolution: str = "480p", device="cpu", max_frames: int = -1, raw=False):
+        self.raw = bool(raw)
         self.root, self.res, self.device, self.max_frames = root, resolution, device, int(max_frames)
         with open(os.path.join(root, "ImageSets", "2017", f"{split}.txt")) as f:
             self.sequences = [ln.strip() for ln in f if ln.strip()]
@@ -580,8 +610,7 @@ class Davis2017:
             if os.path.exists(p):
                 im = Image.open(p)
                 gt[t] = np.asarray(im if im.mode in ("P", "L") else im.convert("L"))
-        rgbs = preprocess_tapvid_frames(frames.to(self.device), (h, w))                    # (1,T,3,h,w), native size
-        imgs = rgbs.permute(0, 2, 1, 3, 4).unsqueeze(1).contiguous()                      # (1,1,3,T,h,w)
+        imgs = _label_imgs(frames, (h, w), self.device, self.raw)                         # (1,1,3,T,h,w), native size
         ref = torch.from_numpy(gt[0].copy()).unsqueeze(0).to(self.device)
         data = dict(imgs=imgs, ref_seg_map=ref, img_meta=[dict(original_shape=(h, w))])
         return data, dict(name=seq, gt=gt, n_objects=int(gt[0].max()))

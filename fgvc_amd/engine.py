@@ -745,6 +745,38 @@ def parse_occlusion(spec, default_radius: int) -> Optional[OcclusionConfig]:
     return OcclusionConfig(thresh, radius)
 
 
+@dataclass
+class InputConfig:
+    """test_cfg.input = dict(type='rgb8', size=(h, w) | None, layout='thwc' | 'tchw'), parsed (an extension key): the
+    trackers then take uint8 RGB frames wherever they take float ones and convert them with ops.frames_to_lab.  `size`: the network size
+    the frames are resized to (None: their own); `layout`: where the frame tensor keeps its channels."""
+    size: Optional[Tuple[int, int]] = None
+    layout: str = "thwc"
+
+
+def parse_input(spec) -> Optional[InputConfig]:
+    """None -> None (the option is off: float frames only).  A mapping with type='rgb8' -> InputConfig; any other `type` (or none), an
+    unknown `layout` or key, or a size that is not two positive integers raises ValueError, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.input: a dict such as dict(type='rgb8', size=(256, 256), layout='thwc'), got {type(spec).__name__}")
+    spec = dict(spec)
+    typ = spec.pop("type", None)
+    if typ != "rgb8":
+        raise ValueError(f"test_cfg.input: type={typ!r} (only 'rgb8': uint8 RGB frames)")
+    size, layout = spec.pop("size", None), spec.pop("layout", "thwc")
+    if spec:
+        raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, layout)")
+    if layout not in ops.INPUT_LAYOUTS:
+        raise ValueError(f"test_cfg.input: layout={layout!r} (one of {ops.INPUT_LAYOUTS})")
+    if size is not None:
+        size = tuple(int(v) for v in size)
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError(f"test_cfg.input: size={size} (two positive integers (h, w), or None for the frames' own size)")
+    return InputConfig(size, layout)
+
+
 def backward_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, stats: Optional[dict] = None) -> torch.Tensor:
     """The clip's T - 1 backward coordinate fields (T-1, HW, 2) f32, (x, y) image pixels interleaved: fields[g - 1] = get_coord(query =
     frame g, key = frame g - 1) (vanilla_tracker.py:445-488), the expected position in frame g - 1 of every feature cell of frame g.

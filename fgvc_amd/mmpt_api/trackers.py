@@ -92,6 +92,7 @@ class VanillaTracker(BaseTracker):
         self.stride_sample = g("stride_sample", False)
         self.feat_channels = None          # the encoder's (un-padded) channel count, known after the first get_feats_hwc()
         self.last_cycle_error = None       # (1, T, P) f32 forward-backward errors of the last points call with test_cfg.occlusion set, else None
+        self.input_cfg = engine.parse_input(self.test_cfg.get("input", None))      # test_cfg.input (None: float frames only); a bad key is refused here
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -244,6 +245,45 @@ class VanillaTracker(BaseTracker):
         v = vis_bool.unsqueeze(0)
         return v.to(visibilities.dtype).to(visibilities.device) if visibilities is not None else v.to(torch.float32)
 
+    # ---- raw frames: test_cfg.input (an extension key) -------------------------------------------------------------
+    def _raw_input(self, frames: torch.Tensor, name: str) -> Optional[engine.InputConfig]:
+        """None for float frames (they run as ever, with or without the key); self.input_cfg for uint8 ones, TypeError without the key."""
+        if frames is None or frames.dtype != torch.uint8:
+            return None
+        ic = self.input_cfg
+        if ic is None:
+            raise TypeError(f"{type(self).__name__}: {name} is uint8, and float frames are expected (Lab-normalised network input); raw RGB "
+                            "frames are taken with the extension key test_cfg.input = dict(type='rgb8', size=(h, w) | None, "
+                            "layout='thwc' | 'tchw')")
+        if not frames.is_cuda:
+            raise RuntimeError(f"fgvc_amd.{type(self).__name__} runs on the GPU only (no CPU fallback)")
+        return ic
+
+    def _points_frames(self, rgbs: torch.Tensor) -> torch.Tensor:
+        """The points call's rgbs as float frames (1, T, 3, h, w): uint8 (1, T, h0, w0, 3) | (1, T, 3, h0, w0) goes through the input kernel."""
+        ic = self._raw_input(rgbs, "rgbs")
+        if ic is None:
+            return rgbs
+        if rgbs.dim() != 5 or rgbs.shape[0] != 1:
+            raise ValueError(f"rgbs: uint8 frames of shape (1, T, h0, w0, 3) ('thwc') or (1, T, 3, h0, w0) ('tchw'), got {tuple(rgbs.shape)}")
+        return ops.frames_to_lab(rgbs[0], ic.size, layout=ic.layout).unsqueeze(0)
+
+    def _label_frames(self, imgs: torch.Tensor):
+        """The label-map call's imgs -> the frames padded to a multiple of _pad_unit() (T, 3, hp, wp), the network size (h, w), the pad.
+        Float imgs (1, 1, 3, T, h, w): F.pad and a transposed view.  uint8 imgs (1, 1, T, h0, w0, 3) | (1, 1, T, 3, h0, w0) with test_cfg.input
+        set: the input kernel writes the padded tensor itself."""
+        ic = self._raw_input(imgs, "imgs")
+        if ic is None:
+            h, w = imgs.shape[-2:]
+            _, pad = engine.pad_divide_by(h, w, self._pad_unit())
+            return torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1), (h, w), pad
+        if imgs.dim() != 6:
+            raise ValueError(f"imgs: uint8 frames of shape (1, 1, T, h0, w0, 3) ('thwc') or (1, 1, T, 3, h0, w0) ('tchw'), got {tuple(imgs.shape)}")
+        v = imgs[0, 0]
+        h, w = ic.size if ic.size is not None else (tuple(v.shape[1:3]) if ic.layout == "thwc" else tuple(v.shape[2:4]))
+        _, pad = engine.pad_divide_by(h, w, self._pad_unit())
+        return ops.frames_to_lab(v, (h, w), pad, ic.layout), (h, w), pad
+
     # ---- A10: regrouping by query time ----------------------------------------------------------
     @torch.no_grad()
     def forward_test(self, rgbs=None, query_points=None, trajectories=None, visibilities=None, save_image=False, save_path=None,
@@ -253,6 +293,7 @@ class VanillaTracker(BaseTracker):
         datasets) it propagates segmentation masks instead: forward_test_seg."""
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        rgbs = self._points_frames(rgbs)
         if not rgbs.is_cuda:
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
         assert rgbs.shape[0] == 1, "batch size must be 1 (vanilla_tracker.py:134)"
@@ -322,6 +363,7 @@ class VanillaTracker(BaseTracker):
         g = self.test_cfg.get
         if ref_seg_map is None or imgs is None or img_meta is None:
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
+        self._raw_input(imgs, "imgs")                      # uint8 frames: TypeError without test_cfg.input, the GPU-only rule with it
         self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
         return_maps = bool(g("return_maps", False))        # extension key: the propagated soft maps themselves (the reference's coords=False output)
         if return_maps and g("coords", False):
@@ -354,10 +396,8 @@ class VanillaTracker(BaseTracker):
     def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
         """forward_test_seg past its refusals: index maps -> [ (T, h0, w0) float64 ]."""
         cfg = self._label_config()
-        h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        _, pad = engine.pad_divide_by(h, w, self._pad_unit())
-        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        frames, _, pad = self._label_frames(imgs)                                             # (T, 3, hp, wp)
         seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
         feats, Hf, Wf = self._label_feats(frames, index_map=True)
         stats, self.label_stats = [], {}
@@ -417,12 +457,9 @@ class VanillaTracker(BaseTracker):
     def _heat_inputs(self, imgs, heat, img_meta):
         """Frames and map each padded by its own pad_divide_by with _pad_unit() (:671-672): the padded frames (T, 3, hp, wp), the map's pad,
         (h0, w0)."""
-        unit = self._pad_unit()
-        h, w = imgs.shape[-2:]
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
-        _, pad = engine.pad_divide_by(h, w, unit)
-        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], unit)
-        frames = torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1)                     # (T, 3, hp, wp)
+        _, map_pad = engine.pad_divide_by(heat.shape[1], heat.shape[2], self._pad_unit())
+        frames, _, _ = self._label_frames(imgs)                                               # (T, 3, hp, wp)
         return frames, map_pad, (h0, w0)
 
     def _seg_heatmaps(self, imgs, heat, img_meta):
@@ -583,11 +620,16 @@ class HRVanillaTracker(VanillaTracker):
         Returns what the reference returns: a list over the batch of float64 numpy arrays (2,P,T), rows (x,y)."""
         from .common import bilinear_sample
         self._refuse_occlusion("forward_test_forward (forward warping)")
-        h, w = imgs.shape[-2:]
-        imgs = imgs.reshape((-1,) + imgs.shape[2:])                                    # :599
-        assert imgs.shape[0] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"
-        T = imgs.shape[2]
-        feats, Hf, Wf, norm = self._feats_hwc(imgs[0].transpose(0, 1))
+        ic = self._raw_input(imgs, "imgs")
+        if ic is not None:                                                             # uint8 (B, 1, T, h0, w0, 3) | (B, 1, T, 3, h0, w0): test_cfg.input
+            assert imgs.dim() == 6 and imgs.shape[0] * imgs.shape[1] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"
+            frames = ops.frames_to_lab(imgs[0, 0], ic.size, layout=ic.layout)         # (T, 3, h, w)
+        else:
+            imgs = imgs.reshape((-1,) + imgs.shape[2:])                                # :599
+            assert imgs.shape[0] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"
+            frames = imgs[0].transpose(0, 1)
+        T, (h, w) = frames.shape[0], frames.shape[-2:]
+        feats, Hf, Wf, norm = self._feats_hwc(frames)
         scale = w // Wf                                                                # :609
         coord = torch.flip(ref, (1,)).float()                                          # :611 (B,2,P) -> rows (x,y)
         coords = [coord]
@@ -633,6 +675,7 @@ class HRVanillaTracker(VanillaTracker):
         reference's mask and pose datasets pass): forward_test_seg, on this tracker's local-window affinity."""
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        rgbs = self._points_frames(rgbs)
         if not self.test_cfg.get("with_first", False):
             return self.forward_test_main(rgbs, query_points, trajectories, visibilities)
         # inherited regrouping (vanilla_tracker.py:246-299): one sweep per distinct query time over the tail of the clip; the

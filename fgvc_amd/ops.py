@@ -1328,3 +1328,41 @@ def softmap_readout(bank: Optional[torch.Tensor], heat: torch.Tensor, Hf: int, W
     _lib.call("fgvc_softmap_readout_f32", _ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm,
               hm + lh + uh, wm + lw + uw, lh, lw, h0, w0, f_begin, f_end, int(out_dtype == torch.float64), _ptr(out), _stream(heat))
     return out
+
+
+# ---- the input stage: decoded uint8 RGB frames -> the network's Lab-normalised planar input -------------------
+
+INPUT_LAYOUTS = ("thwc", "tchw")
+
+
+def frames_to_lab(frames_u8: torch.Tensor, size: Optional[Tuple[int, int]] = None, pad: Tuple[int, int, int, int] = (0, 0, 0, 0),
+                  layout: str = "thwc", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 RGB frames (T, h0, w0, 3) ('thwc') or (T, 3, h0, w0) ('tchw') -> (T, 3, hp, wp) f32: per frame exactly
+    datasets.preprocess_tapvid_frames (bilinear resize to `size` = (h, w), None = the frames' own; / 255; RGB -> Lab; (x - [50, 0, 0]) /
+    [50, 127, 127]) at (top, left) of a border of exact zeros, pad = (left, right, top, bottom) as engine.pad_divide_by returns it
+    (F.pad's order) -- one launch of fgvc_frames_rgb8_to_lab_f32.  The frames are read through their own strides: a view (a crop, a
+    permuted tensor, a time slice) is not copied.  `out`: a contiguous (T, 3, hp, wp) f32 tensor on the frames' device to write into."""
+    if layout not in INPUT_LAYOUTS:
+        raise ValueError(f"layout={layout!r}: one of {INPUT_LAYOUTS}")
+    if not frames_u8.is_cuda:
+        raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f"frames_u8: expected torch.uint8, got {frames_u8.dtype}")
+    if frames_u8.dim() != 4:
+        raise ValueError(f"frames_u8: 4 dimensions ({'T, h0, w0, 3' if layout == 'thwc' else 'T, 3, h0, w0'}), got {tuple(frames_u8.shape)}")
+    f = frames_u8 if layout == "thwc" else frames_u8.permute(0, 2, 3, 1)              # (T, h0, w0, 3) view either way
+    T, h0, w0, ch = f.shape
+    if ch != 3:
+        raise ValueError(f"frames_u8: 3 channels (RGB) in layout {layout!r}, got {ch} (shape {tuple(frames_u8.shape)})")
+    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
+    left, right, top, bottom = (int(p) for p in pad)
+    shape = (T, 3, top + h + bottom, left + w + right)
+    if out is None:
+        out = torch.empty(shape, device=f.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != f.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {f.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    st, sy, sx, sc = f.stride()                                                       # (uint8: elements are bytes)
+    _lib.call("fgvc_frames_rgb8_to_lab_f32", _ptr(f), T, h0, w0, st, sy, sx, sc, h, w, left, right, top, bottom, _ptr(out), _stream(f))
+    return out

@@ -328,6 +328,23 @@ int fgvc_topk_coord_rows_f32(const int32_t* idx, const float* weight, int rows, 
 int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* start_xy, int n, int P, int H, int W, int scale,
                          float* back_out, float* err_out, void* stream);
 
+/* ---- The input stage: decoded uint8 RGB frames -> the network's planar f32 input, one launch.  Per frame exactly
+ * what datasets.preprocess_tapvid_frames defines (configs/eval/base_data.py:1-7: Resize, RGB2LAB, Normalize): bilinear resize (h0, w0) ->
+ * (h, w) on the 0..255 values (align_corners=False, no antialiasing, edge clamped; the identity at the same size), / 255 and clamp to
+ * [0, 1], sRGB -> linear -> XYZ -> CIE Lab (D65, OpenCV's documented constants; parity with cv2 itself unpinned), (x - [50, 0, 0]) /
+ * [50, 127, 127].  Source coordinates and bilinear weights are computed in double and rounded once; the rest is f32.
+ *   frames: T frames of h0 x w0 x 3 bytes addressed by four BYTE strides (frame, row, column, channel): channels-last (T, h0, w0, 3),
+ *           planar (T, 3, h0, w0) and non-contiguous crops of either are read in place.
+ *   out [T][3][pad_top + h + pad_bottom][pad_left + w + pad_right] f32, contiguous: the frame at (pad_top, pad_left), the border written
+ *           as exact 0.0f by the same launch (F.pad of the normalised frames, pad_divide_by: common/utils.py:397-410).
+ * At the same size the sRGB transfer is read from a 256-entry table built per workgroup by the function the resize path evaluates.
+ * FGVC_ERR_INVALID_ARG for a null pointer, a non-positive size or a negative pad, and for a shape beyond the launch grid: T > 65535,
+ * more than 262140 padded rows (four per workgroup on a 16-bit grid axis), a padded width of 2^30 or more, a padded plane of 2^31 pixels
+ * or more -- all before any launch.  No workspace, no atomics. */
+int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                                int64_t stride_c, int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out,
+                                void* stream);
+
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage
  *                             (fgvc_pair_topk_f32 with topk=1 on the coarse features)

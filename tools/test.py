@@ -5,6 +5,7 @@
     python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
     python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
     python tools/test.py CONFIG --task davis --occlusion [--cycle-thresh 1.0] [--occluder]   # predicted visibility: DESIGN.md section 13
+    python tools/test.py CONFIG --task davis|vos|jhmdb|badja --raw-frames     # uint8 RGB frames into the model (test_cfg.input): section 14
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -28,6 +29,8 @@ from fgvc_amd import apis, metrics  # noqa: E402
 from fgvc_amd.datasets import Davis2017, davis_evaluate  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
 from fgvc_amd.datasets import MapsAsCoords, badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
+
+POSE_SIZE = dict(jhmdb=(320, 320), badja=(320, 512))          # the network size of the pose tasks (test_pipeline_jhmdb, badja_dataset.py:355-362)
 
 DEFAULT_CFG = dict(
     model=dict(type="VanillaTracker",
@@ -62,6 +65,9 @@ def main():
     ap.add_argument("--cycle-thresh", type=float, default=None, metavar="CELLS",
                     help="with --occlusion: a point is visible while its cycle error is <= this many feature cells (default 1.0)")
     ap.add_argument("--occluder", action="store_true", help="synthetic clips: paste a static rectangle over the later frames (SyntheticTapVid(occluder=True))")
+    ap.add_argument("--raw-frames", action="store_true",
+                    help="hand the decoded uint8 frames to the model (datasets' raw=True) and set test_cfg.input = dict(type='rgb8', size=...): "
+                         "resize, RGB -> Lab and normalisation run in the library's input kernel instead of the datasets' torch chain")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -87,9 +93,9 @@ def main():
                              "(joint_annotations/*.json, JPEGImages/, Annotations/)")
         dataset = None
     elif a.data_root:
-        dataset = TapVidPickles(a.data_root, a.query_mode, tuple(a.size), device=dev)                   # :121-122
+        dataset = TapVidPickles(a.data_root, a.query_mode, tuple(a.size), device=dev, raw=a.raw_frames)   # :121-122
     else:
-        dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev, occluder=a.occluder)
+        dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev, occluder=a.occluder, raw=a.raw_frames)
     loader = StridedLoader(dataset, rank, world) if dataset is not None else None          # :124-134
     key = "test_cfg_" + a.task                                                               # :135
     if key not in cfg and a.task in ("jhmdb", "badja", "vos") and "test_cfg_davis" in cfg:
@@ -113,6 +119,11 @@ def main():
         if distributed:
             raise SystemExit("--occlusion runs on one GPU (--launcher none)")
         test_cfg = dict(test_cfg, occlusion=dict(type="cycle", cycle_thresh=1.0 if a.cycle_thresh is None else a.cycle_thresh, radius=None))
+    if a.raw_frames:
+        if distributed:
+            raise SystemExit("--raw-frames runs on one GPU (--launcher none)")
+        net_size = {"vos": None, **POSE_SIZE}.get(a.task, tuple(a.size))                                  # what each dataset resizes to
+        test_cfg = dict(test_cfg, input=dict(type="rgb8", size=net_size, layout="thwc"))
     model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
@@ -135,7 +146,7 @@ def main():
 
     if a.task == "vos":        # semi-supervised VOS: the first annotation is propagated (VanillaTracker.forward_test_seg), scored by J&F
         if rank == 0:
-            jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev))
+            jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev, raw=a.raw_frames))
             print(json.dumps({"J&F-Mean": round(jf["J&F-Mean"], 4), "J-Mean": round(jf["J-Mean"], 4), "F-Mean": round(jf["F-Mean"], 4)}))
             for name, r in jf["sequences"].items():
                 print(json.dumps({"sequence": name, **{k: round(v, 4) for k, v in r.items()}}))
@@ -146,10 +157,10 @@ def main():
     elif a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
             if heatmap:        # --pose-form heatmap: the reference's own first-frame label (BadjaPoses(form='heatmap'))
-                ds = BadjaPoses(a.data_root, size=(320, 512), device=dev, form="heatmap")
+                ds = BadjaPoses(a.data_root, size=POSE_SIZE["badja"], device=dev, form="heatmap", raw=a.raw_frames)
                 pck = badja_evaluate_heatmap(scored(lambda i: str(ds.videos[i]["name"])), ds)
             else:
-                pck = badja_evaluate(model, BadjaPoses(a.data_root, size=(320, 512), device=dev))
+                pck = badja_evaluate(model, BadjaPoses(a.data_root, size=POSE_SIZE["badja"], device=dev, raw=a.raw_frames))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
             if a.out:
                 with open(a.out, "w") as f:
@@ -160,11 +171,11 @@ def main():
         # other ranks of a `--launcher pytorch` job wait at the common teardown below
         if rank == 0:
             if heatmap:
-                ds = JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev, form="heatmap")
+                ds = JhmdbPoses(a.data_root, split="val", input_size=POSE_SIZE["jhmdb"], device=dev, form="heatmap", raw=a.raw_frames)
                 vname = lambda i: os.path.relpath(ds.samples[i]["video_path"], ds.root).replace(os.sep, "_")   # <action>_<video>
                 pck = jhmdb_evaluate_heatmap(scored(vname), ds)
             else:
-                pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=(320, 320), device=dev))
+                pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=POSE_SIZE["jhmdb"], device=dev, raw=a.raw_frames))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
             if a.out:
                 with open(a.out, "w") as f:
