@@ -87,6 +87,8 @@ SIGNATURES = {
     "fgvc_topk_coord_rows_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_cycle_chase_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fgvc_frames_rgb8_to_lab_f32": (_i, [_p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_jf_tile_rows": (_i, []),
+    "fgvc_jf_counts_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_c2f_refine_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "fgvc_c2f_refine_mode_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p]),
     "fgvc_bn_act_f32": (_i, [_p, _p, _p, _p, _p, _p, _f, _i, _p, _i, _i, _i, _p]),

@@ -41,6 +41,8 @@ int topk_coord_rows_launch(const int32_t*, const float*, int, int, int, int, int
 int cycle_chase_launch(const float*, const float*, const float*, int, int, int, int, int, float*, float*, hipStream_t);
 int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
                               hipStream_t);
+int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
+int jf_tile_rows();
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -594,6 +596,19 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
                "fgvc_frames_rgb8_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels)");
   return frames_rgb8_to_lab_launch(frames, T, h0, w0, stride_t, stride_y, stride_x, stride_c, h, w, pad_left, pad_right, pad_top, pad_bottom,
                                    out, (hipStream_t)stream);
+}
+
+int fgvc_jf_tile_rows(void) { return jf_tile_rows(); }
+
+int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int w, int n_objects, int radius, int64_t* counts, void* stream) {
+  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: negative size (T=%d, %d x %d)", T, h, w);
+  FGVC_REQUIRE(n_objects >= 0 && n_objects <= 255, FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: n_objects=%d (0 .. 255: the ids are bytes)", n_objects);
+  FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: radius=%d (at least 1)", radius);
+  FGVC_REQUIRE(radius <= 64, FGVC_ERR_UNSUPPORTED, "fgvc_jf_counts_u8: radius=%d beyond 64 (the disk reaches one 64-pixel word to either side)", radius);
+  FGVC_REQUIRE((long long)h * w < (1ll << 31), FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: a frame of %d x %d has 2^31 pixels or more", h, w);
+  if (T == 0 || n_objects == 0) return FGVC_OK;                       // no element of `counts` exists
+  FGVC_REQUIRE(gt && pred && counts, FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: null pointer");
+  return jf_counts_launch(gt, pred, T, h, w, n_objects, radius, counts, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

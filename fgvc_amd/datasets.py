@@ -616,12 +616,20 @@ class Davis2017:
         return data, dict(name=seq, gt=gt, n_objects=int(gt[0].max()))
 
 
-def davis_evaluate(model, dataset: "Davis2017") -> dict:
-    """Run the mask path over the set and score it (metrics.davis_jf)."""
+def davis_evaluate(model, dataset: "Davis2017", backend: str = "host") -> dict:
+    """Run the mask path over the set and score it (metrics.davis_jf).  backend='hip': the counts behind J and F come from
+    fgvc_jf_counts_u8; the annotation of a sequence is uploaded once, and a prediction the model returns on the device (test_cfg.masks=
+    'device') is scored where it is."""
     from . import metrics
+    hip = metrics._backend(backend)
     seqs = {}
     for i in range(len(dataset)):
         data, meta = dataset[i]
         pred = model(test_mode=True, **data)[0]
-        seqs[meta["name"]] = (meta["gt"], pred)
-    return metrics.davis_jf(seqs)
+        gt = meta["gt"]
+        if not hip and isinstance(pred, torch.Tensor):                  # (a model with test_cfg.masks='device', scored on the host)
+            pred = pred.cpu().numpy()
+        if hip and isinstance(gt, np.ndarray) and gt.dtype == np.uint8:
+            gt = torch.from_numpy(gt).to(pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda else "cuda")
+        seqs[meta["name"]] = (gt, pred)
+    return metrics.davis_jf(seqs, backend=backend)

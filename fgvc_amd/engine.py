@@ -777,6 +777,20 @@ def parse_input(spec) -> Optional[InputConfig]:
     return InputConfig(size, layout)
 
 
+MASK_FORMS = ("numpy", "device")
+
+
+def parse_masks(value) -> str:
+    """test_cfg.masks (an extension key): how the index-map call returns its masks.  None | 'numpy' -> 'numpy' (the (T, h0, w0) float64
+    host array, as the reference returns), 'device' -> 'device' (the uint8 CUDA tensor propagate_masks made, for metrics' backend='hip');
+    anything else raises ValueError."""
+    if value is None:
+        return "numpy"
+    if value not in MASK_FORMS:
+        raise ValueError(f"test_cfg.masks={value!r}: one of {MASK_FORMS}")
+    return value
+
+
 def backward_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, stats: Optional[dict] = None) -> torch.Tensor:
     """The clip's T - 1 backward coordinate fields (T-1, HW, 2) f32, (x, y) image pixels interleaved: fields[g - 1] = get_coord(query =
     frame g, key = frame g - 1) (vanilla_tracker.py:445-488), the expected position in frame g - 1 of every feature cell of frame g.

@@ -1,4 +1,5 @@
-"""Evaluation arithmetic of the path's consumers -- host-side numpy, not a kernel.
+"""Evaluation arithmetic of the path's consumers -- host-side numpy, not a kernel; the DAVIS J&F functions can take
+their integer pixel counts from the library instead (backend='hip': fgvc_jf_counts_u8).
 
 * tapvid_metrics      : TAP-Vid occlusion accuracy / pts-within-threshold / Jaccard
                         (mmpt/datasets/tapvid_evaluation_datasets.py:106-249)
@@ -251,15 +252,20 @@ def _disk(r: int) -> np.ndarray:
     return (x * x + y * y) <= r * r
 
 
+def jf_radius(shape, bound_th: float = 0.008) -> int:
+    """The disk radius of the boundary measure for masks of `shape` = (h, w): bound_th itself when it is >= 1 (pixels), else
+    ceil(bound_th * the image diagonal)."""
+    return int(bound_th if bound_th >= 1 else math.ceil(bound_th * np.linalg.norm(shape)))
+
+
 def f_measure(foreground_mask: np.ndarray, gt_mask: np.ndarray, void_pixels: Optional[np.ndarray] = None,
               bound_th: float = 0.008) -> float:
     """Boundary F of one frame: precision / recall of the boundary pixels within a disk of ceil(bound_th * diagonal) pixels."""
     from scipy.ndimage import binary_dilation
     keep = np.ones(foreground_mask.shape, bool) if void_pixels is None else ~void_pixels.astype(bool)
-    r = bound_th if bound_th >= 1 else math.ceil(bound_th * np.linalg.norm(foreground_mask.shape))
     fg_b = _seg2bmap(foreground_mask.astype(bool) & keep)
     gt_b = _seg2bmap(gt_mask.astype(bool) & keep)
-    fp = _disk(int(r))
+    fp = _disk(jf_radius(foreground_mask.shape, bound_th))
     fg_d = binary_dilation(fg_b, structure=fp) if fg_b.any() else fg_b
     gt_d = binary_dilation(gt_b, structure=fp) if gt_b.any() else gt_b
     n_fg, n_gt = int(fg_b.sum()), int(gt_b.sum())
@@ -275,10 +281,93 @@ def f_measure(foreground_mask: np.ndarray, gt_mask: np.ndarray, void_pixels: Opt
     return 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
 
 
+BACKENDS = ("host", "hip")
+
+
+def _backend(backend: str, void_pixels=None) -> bool:
+    """True for 'hip' (after its refusals), False for 'host'."""
+    if backend not in BACKENDS:
+        raise ValueError(f"backend={backend!r}: one of {BACKENDS}")
+    if backend == "host":
+        return False
+    if void_pixels is not None:
+        raise NotImplementedError("backend='hip' does not take void_pixels (no caller passes them); use backend='host'")
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("backend='hip' needs a GPU (fgvc_jf_counts_u8 has no CPU path); use backend='host'")
+    return True
+
+
+def _device_ids(ids, n_objects: int):
+    """Id maps (T, h, w) as the kernel reads them: a uint8 CUDA tensor is used in place; anything else goes through numpy as the host scorer
+    reads it (rint; a value outside 1 .. n_objects is no object: 0) and is uploaded as uint8."""
+    import torch
+    if isinstance(ids, torch.Tensor) and ids.is_cuda:
+        if ids.dtype != torch.uint8:
+            raise TypeError(f"backend='hip': a device tensor of ids must be uint8, got {ids.dtype}")
+        return ids
+    m = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids)
+    if m.dtype != np.uint8 or (m.size and int(m.max()) > n_objects):
+        m = np.rint(m)                                        # (compared as it is: a float array is not widened to int64 first)
+        m = np.where((m >= 1) & (m <= n_objects), m, 0).astype(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(m)).cuda()
+
+
+def jf_counts_hip(gt_ids, pred_ids, n_objects: int, radius: int) -> np.ndarray:
+    """(T, n_objects, 6) int64 on the host: one ops.jf_counts call (fgvc_jf_counts_u8) on two (T, h, w) id maps."""
+    from . import ops
+    if not 0 <= n_objects <= 255:
+        raise ValueError(f"backend='hip': {n_objects} objects (the kernel reads byte ids: at most 255)")
+    return ops.jf_counts(_device_ids(gt_ids, n_objects), _device_ids(pred_ids, n_objects), n_objects, radius).cpu().numpy()
+
+
+def jf_from_counts(counts):
+    """counts (T, n, 6) integers as fgvc_jf_counts_u8 writes them (|G & S|, |G | S|, |b(S)|, |b(G)|, |b(S) & dil b(G)|, |b(G) & dil b(S)|)
+    -> (J (T, n), F (T, n)) float64, by the expressions and branches of db_eval_iou and f_measure: the same bits."""
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts).astype(np.int64)
+    assert c.ndim == 3 and c.shape[2] == 6, c.shape
+    inter, union = c[..., 0], c[..., 1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        J = np.asarray(inter / union, dtype=np.float64)
+    J[np.isclose(union, 0)] = 1.0
+    F = np.zeros(c.shape[:2], np.float64)
+    for t in range(c.shape[0]):
+        for o in range(c.shape[1]):
+            n_fg, n_gt, hit_fg, hit_gt = (int(v) for v in c[t, o, 2:])
+            if n_fg == 0 and n_gt == 0:
+                precision = recall = 1.0
+            elif n_fg == 0:
+                precision, recall = 1.0, 0.0
+            elif n_gt == 0:
+                precision, recall = 0.0, 1.0
+            else:
+                precision = float(hit_fg) / n_fg
+                recall = float(hit_gt) / n_gt
+            F[t, o] = 0.0 if precision + recall == 0 else 2 * precision * recall / (precision + recall)
+    return J, F
+
+
+def _binary_u8(mask):
+    """A binary mask (numpy, or a tensor on either side) as the uint8 id map of object 1, on the device."""
+    import torch
+    if isinstance(mask, torch.Tensor):
+        return (mask != 0).to(torch.uint8).cuda()
+    return torch.from_numpy(np.asarray(mask).astype(bool).astype(np.uint8)).cuda()
+
+
 def db_eval_boundary(annotation: np.ndarray, segmentation: np.ndarray, void_pixels: Optional[np.ndarray] = None,
-                     bound_th: float = 0.008):
-    """Boundary F of (h, w) masks (a float) or of (T, h, w) stacks (an array over T)."""
+                     bound_th: float = 0.008, backend: str = "host"):
+    """Boundary F of (h, w) masks (a float) or of (T, h, w) stacks (an array over T).  backend='hip': the counts come from one
+    fgvc_jf_counts_u8 call (ops.jf_counts) and F from jf_from_counts -- the same value."""
     assert annotation.shape == segmentation.shape
+    if _backend(backend, void_pixels):
+        if annotation.ndim not in (2, 3):
+            raise ValueError(f"db_eval_boundary: {annotation.ndim}-D masks")
+        g, s = _binary_u8(annotation), _binary_u8(segmentation)
+        stack = annotation.ndim == 3
+        g, s = (g, s) if stack else (g[None], s[None])
+        F = jf_from_counts(jf_counts_hip(g, s, 1, jf_radius(tuple(annotation.shape[-2:]), bound_th)))[1][:, 0]
+        return F if stack else float(F[0])
     if annotation.ndim == 2:
         return f_measure(segmentation, annotation, void_pixels, bound_th)
     if annotation.ndim != 3:
@@ -311,10 +400,34 @@ class _quiet:
         return self._w.__exit__(*a)
 
 
-def JFM(all_gt_masks: np.ndarray, all_res_masks: np.ndarray, num_objects: Optional[int] = None) -> Dict[str, list]:
+def _jfm(J_of, F_of, n: int) -> Dict[str, list]:
+    out = {k: [] for k in ("JM", "JR", "JD", "FM", "FR", "FD")}
+    for o in range(n):
+        for key, vals in (("J", J_of(o)), ("F", F_of(o))):
+            m, r, d = db_statistics(vals)
+            out[key + "M"].append(m)
+            out[key + "R"].append(r)
+            out[key + "D"].append(d)
+    return out
+
+
+def JFM(all_gt_masks: np.ndarray, all_res_masks: np.ndarray, num_objects: Optional[int] = None, backend: str = "host") -> Dict[str, list]:
     """Per-object J / F statistics of one sequence.  all_gt_masks, all_res_masks: (objects, T, h, w) binary (a result with fewer objects
     is padded with empty masks; more objects than the annotation is an error).  Returns {'JM','JR','JD','FM','FR','FD'}: lists over
-    the objects."""
+    the objects.  backend='hip': the stacks may overlap, so each object is one fgvc_jf_counts_u8 call with n_objects = 1; the statistics
+    stay on the host."""
+    if _backend(backend):
+        gt, res = all_gt_masks, all_res_masks
+        if res.shape[0] > gt.shape[0]:
+            raise ValueError("JFM: the result has more objects than the annotation")
+        r = jf_radius(tuple(gt.shape[-2:]))
+        JF = []
+        for o in range(gt.shape[0]):
+            g = _binary_u8(gt[o])
+            s = _binary_u8(res[o]) if o < res.shape[0] else g.new_zeros(g.shape)        # (a missing object: an empty mask)
+            J, F = jf_from_counts(jf_counts_hip(g, s, 1, r))
+            JF.append((J[:, 0], F[:, 0]))
+        return _jfm(lambda o: JF[o][0], lambda o: JF[o][1], len(JF))
     gt, res = np.asarray(all_gt_masks), np.asarray(all_res_masks)
     if res.shape[0] > gt.shape[0]:
         raise ValueError("JFM: the result has more objects than the annotation")
@@ -338,16 +451,25 @@ def davis_masks_to_objects(masks: np.ndarray, n_objects: int) -> np.ndarray:
     return np.stack([m == k for k in range(1, n_objects + 1)], 0) if n_objects else np.zeros((0, *m.shape), bool)
 
 
-def davis_jf(sequences: Dict[str, tuple]) -> Dict[str, object]:
+def davis_jf(sequences: Dict[str, tuple], backend: str = "host") -> Dict[str, object]:
     """sequences: name -> (gt (T, h, w) ids, prediction (T, h, w) ids).  Frame 0 (the given annotation) and the last frame are left
     out of the statistics as the DAVIS-2017 semi-supervised evaluation does.  Returns the J&F mean, J mean, F mean and per-sequence
-    J&F / J / F means (each a mean over the sequence's objects)."""
+    J&F / J / F means (each a mean over the sequence's objects).  backend='hip': one fgvc_jf_counts_u8 call per sequence on the id maps
+    themselves (uint8 CUDA tensors are read in place, anything else is rounded and uploaded); the frame rule and the statistics stay on
+    the host, and the result is the same."""
+    hip = _backend(backend)
     per_seq, Js, Fs = {}, [], []
     for name, (gt, pred) in sequences.items():
-        gt, pred = np.asarray(gt), np.asarray(pred)
-        n = int(gt.max())
+        if not hip:
+            gt, pred = np.asarray(gt), np.asarray(pred)
         sl = slice(1, -1) if gt.shape[0] > 2 else slice(0, gt.shape[0])
-        r = JFM(davis_masks_to_objects(gt, n)[:, sl], davis_masks_to_objects(np.rint(pred).astype(np.int64), n)[:, sl], n)
+        if hip:
+            n = int(gt.max())
+            J, F = jf_from_counts(jf_counts_hip(gt[sl], pred[sl], n, jf_radius(tuple(gt.shape[-2:]))))
+            r = _jfm(lambda o: J[:, o], lambda o: F[:, o], n)
+        else:
+            n = int(gt.max())
+            r = JFM(davis_masks_to_objects(gt, n)[:, sl], davis_masks_to_objects(np.rint(pred).astype(np.int64), n)[:, sl], n)
         Js.extend(r["JM"])
         Fs.extend(r["FM"])
         jm, fm = float(np.mean(r["JM"])), float(np.mean(r["FM"]))

@@ -93,6 +93,7 @@ class VanillaTracker(BaseTracker):
         self.feat_channels = None          # the encoder's (un-padded) channel count, known after the first get_feats_hwc()
         self.last_cycle_error = None       # (1, T, P) f32 forward-backward errors of the last points call with test_cfg.occlusion set, else None
         self.input_cfg = engine.parse_input(self.test_cfg.get("input", None))      # test_cfg.input (None: float frames only); a bad key is refused here
+        self.masks_form = engine.parse_masks(self.test_cfg.get("masks", None))     # test_cfg.masks: 'numpy' (default) | 'device'; the index-map call only
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -394,7 +395,8 @@ class VanillaTracker(BaseTracker):
         return self._seg_index_maps(imgs, ref_seg_map, img_meta)
 
     def _seg_index_maps(self, imgs, ref_seg_map, img_meta):
-        """forward_test_seg past its refusals: index maps -> [ (T, h0, w0) float64 ]."""
+        """forward_test_seg past its refusals: index maps -> [ (T, h0, w0) float64 ]; with test_cfg.masks='device' (an extension key; DESIGN.md
+        section 15) the uint8 CUDA tensor itself, which metrics.davis_jf(backend='hip') scores in place."""
         cfg = self._label_config()
         h0, w0 = (int(v) for v in img_meta[0]["original_shape"][:2])
         frames, _, pad = self._label_frames(imgs)                                             # (T, 3, hp, wp)
@@ -405,6 +407,8 @@ class VanillaTracker(BaseTracker):
                                        affinity_stats=self.label_stats)
         self._refine_stats = stats or None
         self._check_kernels()
+        if self.masks_form == "device":
+            return [masks]
         return [masks.cpu().numpy().astype("float64")]
 
     def _forward_test_heatmap(self, imgs, heat, img_meta, return_maps=False):

@@ -1366,3 +1366,42 @@ def frames_to_lab(frames_u8: torch.Tensor, size: Optional[Tuple[int, int]] = Non
     st, sy, sx, sc = f.stride()                                                       # (uint8: elements are bytes)
     _lib.call("fgvc_frames_rgb8_to_lab_f32", _ptr(f), T, h0, w0, st, sy, sx, sc, h, w, left, right, top, bottom, _ptr(out), _stream(f))
     return out
+
+
+# ---- DAVIS J&F on the device: the integer counts metrics.db_eval_iou / f_measure divide ------------------------
+
+JF_TILE = 32            # rows one workgroup of fgvc_jf_counts_u8 owns (= fgvc_jf_tile_rows(); the tests put mask edges on its multiples)
+JF_MAX_RADIUS = 64
+
+
+def jf_counts(gt: torch.Tensor, pred: torch.Tensor, n_objects: int, radius: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gt, pred (T, h, w) uint8 object ids (0 = background) -> (T, n_objects, 6) int64: per frame and object o = 1 .. n_objects, with
+    G = (gt == o) and S = (pred == o): |G & S|, |G | S|, |b(S)|, |b(G)|, |b(S) & dil(b(G))|, |b(G) & dil(b(S))| -- b = metrics._seg2bmap,
+    dil = the dilation by metrics._disk(radius) -- one launch of fgvc_jf_counts_u8 on the current stream; metrics.jf_from_counts turns
+    them into J and F.  A non-contiguous view is made contiguous (a copy).  `out`: a contiguous (T, n_objects, 6) int64 tensor on gt's
+    device; every element is written, the caller clears nothing."""
+    for name, m in (("gt", gt), ("pred", pred)):
+        if not m.is_cuda:
+            raise _lib.FgvcHipError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
+        if m.dtype != torch.uint8:
+            raise TypeError(f"{name}: expected torch.uint8 object ids, got {m.dtype}")
+        if m.dim() != 3:
+            raise ValueError(f"{name}: 3 dimensions (T, h, w), got {tuple(m.shape)}")
+    if gt.shape != pred.shape or gt.device != pred.device:
+        raise ValueError(f"gt {tuple(gt.shape)} on {gt.device} and pred {tuple(pred.shape)} on {pred.device}: one shape, one device")
+    n_objects, radius = int(n_objects), int(radius)
+    if not 0 <= n_objects <= 255:
+        raise ValueError(f"n_objects={n_objects}: 0 .. 255 (the ids are bytes)")
+    if not 1 <= radius <= JF_MAX_RADIUS:
+        raise ValueError(f"radius={radius}: 1 .. {JF_MAX_RADIUS}")
+    T, h, w = gt.shape
+    shape = (T, n_objects, 6)
+    if out is None:
+        out = torch.empty(shape, device=gt.device, dtype=torch.int64)
+    elif tuple(out.shape) != shape or out.dtype != torch.int64 or out.device != gt.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous int64 tensor of shape {shape} on {gt.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0 or n_objects == 0:
+        return out
+    gt, pred = gt.contiguous(), pred.contiguous()
+    _lib.call("fgvc_jf_counts_u8", _ptr(gt), _ptr(pred), T, h, w, n_objects, radius, _ptr(out), _stream(gt))
+    return out

@@ -345,6 +345,20 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
                                 int64_t stride_c, int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out,
                                 void* stream);
 
+/* ---- DAVIS J&F on the device: the integer pixel counts that metrics.db_eval_iou and metrics.f_measure divide.
+ *   gt, pred [T][h][w] uint8 object ids, 0 = background.  For object o = 1 .. n_objects: G = (gt == o), S = (pred == o); an id above
+ *           n_objects belongs to no object (metrics.davis_masks_to_objects).
+ *   counts [T][n_objects][6] int64: |G & S|, |G | S|, |b(S)|, |b(G)|, |b(S) & dil(b(G))|, |b(G) & dil(b(S))|.
+ * b(.) is metrics._seg2bmap: a pixel is a boundary pixel when it differs from its east, south or south-east neighbour, neighbours outside
+ * the image counting as 0; then the last row compares east only, the last column south only, and the bottom-right corner is never one.
+ * dil(B)(p) holds when some q INSIDE the image has B(q) and |p - q|^2 <= radius^2 (scipy's binary_dilation with metrics._disk and a zero
+ * border; nothing wraps across a row's end).  Every element of `counts` is written by the call (it clears them on `stream`, then adds
+ * integers: deterministic).  1 <= radius <= 64, 0 <= n_objects <= 255; with T = 0 or n_objects = 0 nothing is launched.
+ * FGVC_ERR_UNSUPPORTED for a radius above 64; FGVC_ERR_INVALID_ARG for a null pointer, a negative size, radius < 1, n_objects outside
+ * 0 .. 255 and a frame of 2^31 pixels or more.  fgvc_jf_tile_rows(): the rows one workgroup owns (tests put mask edges on its multiples). */
+int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int w, int n_objects, int radius, int64_t* counts, void* stream);
+int fgvc_jf_tile_rows(void);
+
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage
  *                             (fgvc_pair_topk_f32 with topk=1 on the coarse features)

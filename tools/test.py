@@ -6,6 +6,7 @@
     python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
     python tools/test.py CONFIG --task davis --occlusion [--cycle-thresh 1.0] [--occluder]   # predicted visibility: DESIGN.md section 13
     python tools/test.py CONFIG --task davis|vos|jhmdb|badja --raw-frames     # uint8 RGB frames into the model (test_cfg.input): section 14
+    python tools/test.py CONFIG --task vos --data-root DIR --gpu-metrics     # masks stay on the device, J&F from fgvc_jf_counts_u8: section 15
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -68,6 +69,9 @@ def main():
     ap.add_argument("--raw-frames", action="store_true",
                     help="hand the decoded uint8 frames to the model (datasets' raw=True) and set test_cfg.input = dict(type='rgb8', size=...): "
                          "resize, RGB -> Lab and normalisation run in the library's input kernel instead of the datasets' torch chain")
+    ap.add_argument("--gpu-metrics", action="store_true",
+                    help="--task vos: keep the propagated masks on the device (test_cfg.masks='device') and score J&F from the counts of "
+                         "the library's fgvc_jf_counts_u8 (metrics.davis_jf(backend='hip')): the same numbers, DESIGN.md section 15")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -124,6 +128,10 @@ def main():
             raise SystemExit("--raw-frames runs on one GPU (--launcher none)")
         net_size = {"vos": None, **POSE_SIZE}.get(a.task, tuple(a.size))                                  # what each dataset resizes to
         test_cfg = dict(test_cfg, input=dict(type="rgb8", size=net_size, layout="thwc"))
+    if a.gpu_metrics:
+        if a.task != "vos":
+            raise SystemExit("--gpu-metrics goes with --task vos (the J&F of the mask path)")
+        test_cfg = dict(test_cfg, masks="device")
     model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
@@ -146,7 +154,8 @@ def main():
 
     if a.task == "vos":        # semi-supervised VOS: the first annotation is propagated (VanillaTracker.forward_test_seg), scored by J&F
         if rank == 0:
-            jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev, raw=a.raw_frames))
+            jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev, raw=a.raw_frames),
+                                backend="hip" if a.gpu_metrics else "host")
             print(json.dumps({"J&F-Mean": round(jf["J&F-Mean"], 4), "J-Mean": round(jf["J-Mean"], 4), "F-Mean": round(jf["F-Mean"], 4)}))
             for name, r in jf["sequences"].items():
                 print(json.dumps({"sequence": name, **{k: round(v, 4) for k, v in r.items()}}))
