@@ -43,6 +43,10 @@ int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long lon
                               hipStream_t);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
+int render_frames_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
+                         const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
+                         int, const double*, hipStream_t);
+void render_tile(int*, int*);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -609,6 +613,52 @@ int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int 
   if (T == 0 || n_objects == 0) return FGVC_OK;                       // no element of `counts` exists
   FGVC_REQUIRE(gt && pred && counts, FGVC_ERR_INVALID_ARG, "fgvc_jf_counts_u8: null pointer");
   return jf_counts_launch(gt, pred, T, h, w, n_objects, radius, counts, (hipStream_t)stream);
+}
+
+int fgvc_render_tile_rows(void) {
+  int rows, cols;
+  render_tile(&rows, &cols);
+  return rows;
+}
+
+int fgvc_render_tile_cols(void) {
+  int rows, cols;
+  render_tile(&rows, &cols);
+  return cols;
+}
+
+int fgvc_render_frames_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                          int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                          const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                          int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                          const uint8_t* colors, int P, int radius, const double* icon, void* stream) {
+  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: negative size (T=%d, %d x %d)", T, h, w);
+  FGVC_REQUIRE(P >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: P=%d", P);
+  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
+  if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
+  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: null pointer");
+  const long long row = 3ll * w;
+  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_frames_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
+  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_frames_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
+               (long long)out_stride_t, (long long)out_stride_y, h, w);
+  if (ids) {
+    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: ids without a palette");
+    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: alpha=%d (0 .. 256)", alpha);
+    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_frames_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
+  }
+  if (tracks && P > 0) {
+    FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: radius=%d (at least 1)", radius);
+    FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_frames_u8: radius=%d beyond 31", radius);
+    FGVC_REQUIRE(colors && icon, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: tracks without colors or the icon table");
+    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon)) & 7u) == 0, FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_frames_u8: tracks and icon must be 8-byte aligned");
+  }
+  return render_frames_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                              palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
+                              visibles_stride_t, colors, P, radius, icon, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

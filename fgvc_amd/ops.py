@@ -1405,3 +1405,112 @@ def jf_counts(gt: torch.Tensor, pred: torch.Tensor, n_objects: int, radius: int,
     gt, pred = gt.contiguous(), pred.contiguous()
     _lib.call("fgvc_jf_counts_u8", _ptr(gt), _ptr(pred), T, h, w, n_objects, radius, _ptr(out), _stream(gt))
     return out
+
+
+# ---- render: mask overlay and point icons onto uint8 video -------------------------------------------------------
+
+RENDER_TILE = (8, 256)  # rows, columns one workgroup of fgvc_render_frames_u8 owns (= fgvc_render_tile_rows/_cols(); the tests put points on its corners)
+RENDER_MAX_RADIUS = 31
+_render_tables: dict = {}
+
+
+def _render_table(key, device, make):
+    """Small constant tables of the renderer on the device (the icon per radius, the default palette), uploaded once per device."""
+    k = (key, str(device))
+    if k not in _render_tables:
+        import numpy as np
+        _render_tables[k] = torch.from_numpy(np.array(make())).to(device)             # (a writable copy: the tables are read-only)
+    return _render_tables[k]
+
+
+def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, alpha: int = 128,
+                  contour: bool = True, tracks: Optional[torch.Tensor] = None, visibles: Optional[torch.Tensor] = None,
+                  colors: Optional[torch.Tensor] = None, radius: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames_u8 (T, H, W, 3) uint8 -> the same with the objects of ids (T, H, W) uint8 blended in (palette (256, 3) uint8, None: the DAVIS
+    palette; alpha 0 .. 256; contour) and then the points of tracks (P, T, 2) as (x, y) painted on (visibles (P, T) bool or uint8, None: all;
+    colors (P, 3) uint8, None: viz.track_colors(P); radius 1 .. 31, None: the reference's round(min(H, W) * 0.015)) -- viz.render's host
+    backend bit for bit, in one launch of fgvc_render_frames_u8 on the current stream.  Everything is a tensor on the frames' device.
+    Frames, ids and `out` are read and written through their own frame and row strides (a time slice or a cropped window is not copied;
+    pixels must be packed); tracks of another float type are converted to float64 first (exact).  `out`: a (T, H, W, 3) uint8 tensor to write
+    into, `frames_u8` itself included; neither ids nor tracks: a copy."""
+    from . import viz
+    if not frames_u8.is_cuda:
+        raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f"frames_u8: expected torch.uint8, got {frames_u8.dtype}")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames_u8: (T, H, W, 3), got {tuple(frames_u8.shape)}")
+    dev = frames_u8.device
+    T, H, W, _ = frames_u8.shape
+
+    def packed(x, px):
+        """the view itself when its pixels are packed (px bytes each), its rows apart and its strides non-negative, else a contiguous copy"""
+        inner = x.stride(2) == px and (px == 1 or x.stride(3) == 1)
+        return x if x.numel() == 0 or (inner and x.stride(0) >= 0 and x.stride(1) >= W * px) else x.contiguous()
+    f = packed(frames_u8, 3)
+    if out is None:
+        out = torch.empty((T, H, W, 3), device=dev, dtype=torch.uint8)
+    else:
+        if tuple(out.shape) != (T, H, W, 3) or out.dtype != torch.uint8 or out.device != dev:
+            raise ValueError(f"out: a uint8 tensor of shape {(T, H, W, 3)} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if packed(out, 3) is not out:
+            raise ValueError(f"out: packed pixels and non-negative strides, got strides {out.stride()}")
+    args_ids = (None, 0, 0, None, 128, 0)
+    if ids is not None:
+        if not ids.is_cuda or ids.device != dev:
+            raise ValueError(f"ids: on {dev} with the frames, got {ids.device}")
+        if ids.dtype != torch.uint8:
+            raise TypeError(f"ids: expected torch.uint8 object ids, got {ids.dtype}")
+        if tuple(ids.shape) != (T, H, W):
+            raise ValueError(f"ids: {(T, H, W)} to go with the frames, got {tuple(ids.shape)}")
+        if int(alpha) != alpha or not 0 <= int(alpha) <= 256:
+            raise ValueError(f"alpha={alpha!r}: an integer in 0 .. 256")
+        if palette is None:
+            palette = _render_table("palette", dev, viz.davis_palette)
+        if palette.dtype != torch.uint8:
+            raise TypeError(f"palette: expected torch.uint8, got {palette.dtype}")
+        if tuple(palette.shape) != (256, 3) or palette.device != dev:
+            raise ValueError(f"palette: (256, 3) on {dev}, got {tuple(palette.shape)} on {palette.device}")
+        m, palette = packed(ids, 1), palette.contiguous()
+        args_ids = (m, m.stride(0), m.stride(1), palette, int(alpha), int(bool(contour)))
+    args_pts = (None, 0, 0, None, 0, 0, None, 0, 0, None)
+    if tracks is not None:
+        if tracks.device != dev:
+            raise ValueError(f"tracks: on {dev} with the frames, got {tracks.device}")
+        if tracks.dim() != 3 or tracks.shape[1] != T or tracks.shape[2] != 2:
+            raise ValueError(f"tracks: (P, {T}, 2) to go with the frames, got {tuple(tracks.shape)}")
+        if tracks.dtype == torch.bool or tracks.dtype.is_complex:
+            raise TypeError(f"tracks: a real number type, got {tracks.dtype}")
+        P = tracks.shape[0]
+        r = viz.check_radius(radius, H, W)
+        tr = tracks.to(torch.float64)
+        if tr.stride(2) != 1 or tr.data_ptr() % 8:
+            tr = tr.contiguous()
+        vis = None
+        if visibles is not None:
+            if visibles.dtype not in (torch.bool, torch.uint8):
+                raise TypeError(f"visibles: expected torch.bool (or uint8), got {visibles.dtype}")
+            if tuple(visibles.shape) != (P, T) or visibles.device != dev:
+                raise ValueError(f"visibles: {(P, T)} on {dev} to go with the tracks, got {tuple(visibles.shape)} on {visibles.device}")
+            vis = visibles.view(torch.uint8) if visibles.dtype == torch.bool else visibles
+        if colors is None:
+            colors = torch.from_numpy(viz.track_colors(P)).to(dev)
+        if colors.dtype != torch.uint8:
+            raise TypeError(f"colors: expected torch.uint8, got {colors.dtype}")
+        if tuple(colors.shape) != (P, 3) or colors.device != dev:
+            raise ValueError(f"colors: {(P, 3)} on {dev} to go with the tracks, got {tuple(colors.shape)} on {colors.device}")
+        colors = colors.contiguous()
+        icon = _render_table(("icon", r), dev, lambda: viz.icon_table(r))
+        args_pts = (tr, tr.stride(0), tr.stride(1), vis, 0 if vis is None else vis.stride(0), 0 if vis is None else vis.stride(1), colors, P, r,
+                    icon)
+    if T == 0 or H == 0 or W == 0:
+        return out
+    m, m_st, m_sy, pal, al, ct = args_ids
+    tr, tr_sp, tr_st, vis, v_sp, v_st, col, P, r, icon = args_pts
+
+    def ptr(x):
+        return None if x is None else _ptr(x)
+    _lib.call("fgvc_render_frames_u8", _ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W,
+              ptr(m), m_st, m_sy, ptr(pal), al, ct, ptr(tr), tr_sp, tr_st, ptr(vis), v_sp, v_st, ptr(col), int(P or 0), int(r or 0), ptr(icon),
+              _stream(f))
+    return out

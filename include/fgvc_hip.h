@@ -359,6 +359,34 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
 int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int w, int n_objects, int radius, int64_t* counts, void* stream);
 int fgvc_jf_tile_rows(void);
 
+/* ---- Render: mask overlay and point icons onto uint8 RGB video, all T frames in one launch; fgvc_amd/viz.py's host
+ * backend bit for bit.
+ *   frames, out [T][h][w][3] uint8, each through its own frame and row strides in bytes (pixels are packed: 3 bytes); `out` may be `frames`
+ *           itself (same strides) -- a pixel depends on its own input pixel and on ids only -- and must not overlap it otherwise.
+ *   ids     [T][h][w] uint8 through its own frame and row strides, or null (no overlay).  k = ids[t][y][x] > 0:
+ *           out_c = (frame_c (256 - alpha) + palette[k][c] alpha + 128) >> 8, alpha 0 .. 256, palette [256][3] uint8; with contour != 0 a
+ *           pixel whose left, right, upper or lower in-image neighbour has another id takes palette[k][c] unblended.  k == 0: unchanged.
+ *   tracks  float64, (x, y) of point i on frame t at tracks[i * tracks_stride_p + t * tracks_stride_t + {0, 1}] (strides in doubles), or
+ *           null / P == 0 (no points); visibles uint8 at [i * visibles_stride_p + t * visibles_stride_t], non-zero = drawn, null = all;
+ *           colors [P][3] uint8; icon [(2 r + 1)^2] float64, the dot's opacity (viz.icon_table: computed once on the host).
+ *           After the overlay every visible point with finite coordinates is blended in INDEX ORDER onto the pixels its window covers:
+ *           x = track_x + 0.5 clamped to [0, w], x1 = floor(x), x2 = x1 + 1 (y alike); a = py + r + 1 - y1, b = px + r + 1 - x1 in
+ *           [0, 2 r + 1]; with I = icon, zero outside,
+ *             patch = I(a,b)(x2-x)(y2-y) + I(a-1,b)(x2-x)(y-y1) + I(a,b-1)(x-x1)(y2-y) + I(a-1,b-1)(x-x1)(y-y1)
+ *             v_c = (1 - patch) v_c + patch colors[i][c], truncated towards zero to uint8 after every point
+ *           in float64 without contraction, products and sums left to right (the reference's paint_point_track, gathered per pixel).
+ * Neither ids nor tracks: a copy.  No workspace, no atomics; runs on `stream`.  FGVC_ERR_UNSUPPORTED for a radius above 31;
+ * FGVC_ERR_INVALID_ARG for a null pointer, a negative size, a frame of 2^29 pixels or more, alpha outside 0 .. 256, radius < 1, row strides
+ * below a row's bytes, overlapping rows or frames of `out`, tracks or icon not 8-byte aligned -- all before any launch.  With T, h or w = 0
+ * nothing is launched.  The two tile functions give the rows and columns one workgroup owns (tests put points and contours on their multiples). */
+int fgvc_render_frames_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                          int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                          const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                          int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                          const uint8_t* colors, int P, int radius, const double* icon, void* stream);
+int fgvc_render_tile_rows(void);
+int fgvc_render_tile_cols(void);
+
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage
  *                             (fgvc_pair_topk_f32 with topk=1 on the coarse features)

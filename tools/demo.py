@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Track points or propagate a first-frame mask through a clip and write the annotated frames (the reference's tools/demo.py, without cv2 or
+mediapy: frames come and go through PIL).
+
+    python tools/demo.py FRAMES_DIR --task points --query-points t x y [t x y ...] --out OUT
+    python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
+    python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
+
+FRAMES_DIR holds the clip's frames as JPEG / PNG files, taken in name order.  The frames go to the model as they are decoded -- uint8 RGB, on
+the device -- through test_cfg.input = dict(type='rgb8'); the mask task keeps its id maps on the device
+(test_cfg.masks='device', section 15); fgvc_amd.viz.render(backend='hip') paints tracks or masks onto the uint8 frames in one launch
+(section 16) and OUT gets frame_%05d.png and demo.gif.  --host-render paints with the numpy backend instead (the same bytes, for comparison).
+Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
+Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import fgvc_amd.mmpt_api as api  # noqa: E402
+from fgvc_amd import viz  # noqa: E402
+
+EXTENSIONS = (".jpg", ".jpeg", ".png")
+
+
+def load_frames(path: str) -> np.ndarray:
+    from PIL import Image
+    names = sorted(n for n in os.listdir(path) if n.lower().endswith(EXTENSIONS))
+    if not names:
+        raise FileNotFoundError(f"{path}: no {' / '.join(EXTENSIONS)} files")
+    frames = [np.asarray(Image.open(os.path.join(path, n)).convert("RGB")) for n in names]
+    if len({f.shape for f in frames}) != 1:
+        raise ValueError(f"{path}: the frames differ in size")
+    return np.stack(frames)
+
+
+def synthetic_frames(T: int, H: int, W: int, seed: int = 0) -> np.ndarray:
+    """A smooth random texture that drifts by (1, 2) px a frame under a fixed vignette, plus noise: (T, H, W, 3) uint8."""
+    rng = np.random.default_rng(seed)
+    cell = 8
+    coarse = rng.random((-(-(H + T) // cell) + 2, -(-(W + 2 * T) // cell) + 2, 3))
+    tex = np.kron(coarse, np.ones((cell, cell, 1)))
+    k = np.ones(cell) / cell
+    for ax in (0, 1):
+        tex = np.apply_along_axis(lambda v: np.convolve(v, k, mode="same"), ax, tex)
+    yy, xx = np.mgrid[0:H, 0:W]
+    shade = 1.0 - 0.3 * (((yy / H - 0.5) ** 2 + (xx / W - 0.5) ** 2))[..., None]
+    out = [tex[cell + t:cell + t + H, cell + 2 * t:cell + 2 * t + W] * shade * 300.0 - 22.0 + rng.normal(0.0, 4.0, (H, W, 3)) for t in range(T)]
+    return np.clip(np.rint(np.stack(out)), 0, 255).astype(np.uint8)
+
+
+def build_model(a, dev, **extra):
+    cfg = dict(precede_frames=a.precede_frames, topk=a.topk, temperature=0.07, neighbor_range=a.neighbor_range, with_first=True,
+               with_first_neighbor=True, batch_step=a.batch_step, **extra)
+    model = api.build_model(dict(type=a.tracker, backbone=dict(type="ResNet", depth=18, strides=tuple(a.strides), out_indices=(2,),
+                                                              pool_type="none")), train_cfg=None, test_cfg=api.ConfigDict(**cfg))
+    torch.manual_seed(a.seed)
+    model.init_weights()
+    if a.checkpoint:
+        api.load_checkpoint(model, a.checkpoint)
+    return model.to(dev).eval()
+
+
+def run_points(a, frames: np.ndarray, dev):
+    """-> tracks (P, T, 2) float64 in the clip's pixel frame, visibles (P, T) bool (from the query time on), query points (P, 3) as returned."""
+    T, H, W = frames.shape[:3]
+    q = np.asarray(a.query_points, np.float64)
+    if q.size == 0 or q.size % 3:
+        raise ValueError("--query-points: t x y [t x y ...]")
+    q = q.reshape(-1, 3)
+    if (q[:, 0] < 0).any() or (q[:, 0] >= T).any():
+        raise ValueError(f"--query-points: a query time outside 0 .. {T - 1}")
+    size = tuple(a.size) if a.size else (H, W)
+    q[:, 1:] = viz.scale_tracks(q[:, 1:], (H, W), size)
+    model = build_model(a, dev, input=dict(type="rgb8", size=tuple(a.size) if a.size else None, layout="thwc"))
+    qp = torch.from_numpy(q).float()[None].to(dev)
+    P = q.shape[0]
+    with torch.no_grad():
+        out = model(test_mode=True, rgbs=torch.from_numpy(frames).to(dev)[None], query_points=qp,
+                    trajectories=torch.zeros(1, T, P, 2, device=dev), visibilities=torch.ones(1, T, P, device=dev))
+    traj, qp_out = out[2][0], out[4][0]                                  # (T, P, 2) at the model's size; the points in the order of its columns
+    tracks = viz.scale_tracks(traj.permute(1, 0, 2), size, (H, W))
+    visibles = np.arange(T)[None, :] >= qp_out[:, :1].cpu().numpy()
+    return tracks, visibles, qp_out.cpu().numpy()
+
+
+def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
+    """-> (T, H, W) uint8 object ids on the device, frame 0 the given mask."""
+    from PIL import Image
+    T, H, W = frames.shape[:3]
+    mask = np.asarray(Image.open(a.first_mask))
+    if mask.ndim != 2 or mask.shape != (H, W):
+        raise ValueError(f"--first-mask: a palette or grey PNG of object ids, {H} x {W} as the frames, got an array of shape {mask.shape}")
+    model = build_model(a, dev, input=dict(type="rgb8", size=None, layout="thwc"), masks="device")
+    with torch.no_grad():
+        out = model(test_mode=True, imgs=torch.from_numpy(frames).to(dev)[None, None], ref_seg_map=torch.from_numpy(mask.astype(np.uint8))[None].to(dev),
+                    img_meta=[dict(original_shape=(H, W))])
+    return out[0]
+
+
+def write(out_dir: str, rendered: np.ndarray, fps: float):
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    images = [Image.fromarray(f) for f in rendered]
+    for t, im in enumerate(images):
+        im.save(os.path.join(out_dir, f"frame_{t:05d}.png"))
+    images[0].save(os.path.join(out_dir, "demo.gif"), save_all=True, append_images=images[1:], duration=int(round(1000.0 / fps)), loop=0)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("frames", nargs="?", help="a directory of JPEG / PNG frames")
+    ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"), help="a generated clip instead of FRAMES_DIR")
+    ap.add_argument("--task", choices=("points", "vos"), required=True)
+    ap.add_argument("--query-points", type=float, nargs="+", default=[], metavar="V", help="t x y [t x y ...], pixels of the clip")
+    ap.add_argument("--first-mask", help="PNG of object ids for frame 0 (--task vos)")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--host-render", action="store_true", help="paint with viz's numpy backend instead of the kernel")
+    ap.add_argument("--size", type=int, nargs=2, metavar=("h", "w"), help="run the points model at this size")
+    ap.add_argument("--radius", type=int, default=None)
+    ap.add_argument("--alpha", type=int, default=128)
+    ap.add_argument("--no-contour", action="store_true")
+    ap.add_argument("--fps", type=float, default=10.0)
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--tracker", default="VanillaTracker", choices=("VanillaTracker", "HRVanillaTracker"))
+    ap.add_argument("--strides", type=int, nargs=4, default=(1, 2, 1, 1))
+    ap.add_argument("--neighbor-range", type=int, default=30)
+    ap.add_argument("--precede-frames", type=int, default=5)
+    ap.add_argument("--topk", type=int, default=10)
+    ap.add_argument("--batch-step", type=int, default=8)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    if (a.frames is None) == (a.synthetic is None):
+        ap.error("give FRAMES_DIR or --synthetic T H W")
+    if a.task == "points" and not a.query_points:
+        ap.error("--task points needs --query-points")
+    if a.task == "vos" and not a.first_mask:
+        ap.error("--task vos needs --first-mask")
+    if not torch.cuda.is_available():
+        raise RuntimeError("tools/demo.py runs the model on the GPU (fgvc_amd has no CPU path)")
+    dev = torch.device("cuda:0")
+    frames = synthetic_frames(*a.synthetic, seed=a.seed) if a.synthetic else load_frames(a.frames)
+    tracks = visibles = ids = points = None
+    if a.task == "points":
+        tracks, visibles, points = run_points(a, frames, dev)
+    else:
+        ids = run_vos(a, frames, dev)
+    kw = dict(ids=ids, tracks=tracks, visibles=visibles, radius=a.radius, alpha=a.alpha, contour=not a.no_contour)
+    if a.host_render:
+        rendered = viz.render(frames, backend="host", **kw)
+    else:
+        rendered = viz.render(torch.from_numpy(frames).to(dev), backend="hip", **kw).cpu().numpy()
+    write(a.out, rendered, a.fps)
+    print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}, {'host' if a.host_render else 'hip'} renderer)")
+    return dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
+
+
+if __name__ == "__main__":
+    main()
