@@ -54,7 +54,7 @@ int conv_split_launch(const uint16_t*, const uint16_t*, const float*, const floa
                       int, int, int, int, int, int, int, int, int*, hipStream_t, unsigned char* y_bank = nullptr, int bank_normalize = 1, const uint16_t* x2 = nullptr,
                       const uint16_t* w2 = nullptr, int Cin2 = 0, int bank_row_bytes = 1024);
 int conv_s2_launch(const uint16_t*, const uint16_t*, const float*, uint16_t*, float*, int, int, int, int, int, int, int, int, int,
-                   int, int, int, int, int*, hipStream_t);
+                   int, int, int, int, int*, const uint16_t*, const float*, float*, int, hipStream_t);
 int conv64_launch(const uint16_t*, const uint16_t*, const float*, const float*, const uint16_t*, uint16_t*, float*, int, int, int, int, int, int,
                   int, int, int, int, int*, hipStream_t);
 int stem7_launch(const float*, const uint16_t*, const float*, uint16_t*, float*, int, int, int, int, int, int, int, int, int, int, int*,
@@ -838,6 +838,14 @@ int fgvc_conv_s2_split_f32(const uint16_t* x, const uint16_t* w, const float* bi
 int fgvc_conv_s2_split_fmt_f32(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y_split, float* y_f32, int N,
                                int H, int W, int Hp, int Wp, int Cin, int Cout, int KS, int Hop, int Wop, int relu, int out_fmt,
                                int out_scale_log2, int* overflow, void* stream) {
+  return fgvc_conv_s2_split_proj_fmt_f32(x, w, bias, y_split, y_f32, nullptr, nullptr, nullptr, N, H, W, Hp, Wp, Cin, Cout, KS, Cout, Hop, Wop,
+                                         relu, 0, out_fmt, out_scale_log2, overflow, stream);
+}
+
+int fgvc_conv_s2_split_proj_fmt_f32(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y_split, float* y_f32,
+                                    const uint16_t* w2, const float* bias2, float* y2_f32, int N, int H, int W, int Hp, int Wp, int Cin,
+                                    int Cout, int KS, int Cout2, int Hop, int Wop, int relu, int relu2, int out_fmt, int out_scale_log2,
+                                    int* overflow, void* stream) {
   FGVC_REQUIRE(x && w && bias && (y_split || y_f32), FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_f32: null pointer");
   FGVC_REQUIRE(out_fmt >= 0 && out_fmt <= 3 && out_scale_log2 > -100 && out_scale_log2 < 100, FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_fmt_f32: bad output format / scale");
   FGVC_REQUIRE(out_fmt == FGVC_ACT_BF16X2 || !y_split || overflow, FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_fmt_f32: an f16-format output needs the overflow word");
@@ -852,9 +860,16 @@ int fgvc_conv_s2_split_fmt_f32(const uint16_t* x, const uint16_t* w, const float
   FGVC_REQUIRE(aligned16(x) && aligned16(w) && aligned16(bias) && aligned16(y_split) && aligned16(y_f32),
                FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_f32: 16-byte alignment required");
   FGVC_REQUIRE((const void*)x != (const void*)y_split, FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_f32: in-place not supported");
+  if (w2 || bias2 || y2_f32) {                                // the projection in the same launch: all three or none
+    FGVC_REQUIRE(w2 && bias2 && y2_f32, FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_proj_fmt_f32: null pointer (w2, bias2 and y2_f32 go together)");
+    FGVC_REQUIRE(KS == 3, FGVC_ERR_UNSUPPORTED, "fgvc_conv_s2_split_proj_fmt_f32: the projection rides in the 3x3 kernel only (KS = %d)", KS);
+    FGVC_REQUIRE(Cout2 == Cout, FGVC_ERR_UNSUPPORTED, "fgvc_conv_s2_split_proj_fmt_f32: the projection's Cout=%d differs from the convolution's %d", Cout2, Cout);
+    FGVC_REQUIRE(aligned16(w2) && aligned16(bias2) && aligned16(y2_f32), FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_proj_fmt_f32: 16-byte alignment required");
+    FGVC_REQUIRE((const void*)y2_f32 != (const void*)y_f32, FGVC_ERR_INVALID_ARG, "fgvc_conv_s2_split_proj_fmt_f32: the two f32 outputs must differ");
+  }
   if (N == 0) return FGVC_OK;
   return conv_s2_launch(x, w, bias, y_split, y_f32, N, Hp, Wp, Cin, Cout, KS, Ho, Wo, Hop, Wop, relu, out_fmt, out_scale_log2, overflow,
-                        (hipStream_t)stream);
+                        w2, bias2, y2_f32, relu2, (hipStream_t)stream);
 }
 
 int fgvc_stem7_split_f32(const float* x, const uint16_t* w, const float* bias, uint16_t* y_split, float* y_f32, int N, int H,

@@ -161,6 +161,9 @@ class ResNet(nn.Module):
     fold_projection = True         # a block's stride-1 1 x 1 projection shortcut rides in the sums of the block's second convolution
                                    # (fgvc_conv_split_proj_fmt_f32: 256 output channels, 3 x 3; not in the f16f8 arithmetic, whose e4m3
                                    # forms cannot take a forced weight scale): no projection launch, no dense f32 identity (False: A/B)
+    fuse_s2_projection = True      # a stride-2 block's 1 x 1 / stride 2 projection rides in the launch of the block's 3 x 3 / stride 2 convolution
+                                   # (fgvc_conv_s2_split_proj_fmt_f32: it reads that kernel's centre tap); bit-identical outputs.  Calibration
+                                   # passes and other shapes keep the two launches (False: A/B, tools/ab_switch.sh)
     layer1_whole_batch = True      # the stem and layer 1 once over the whole batch, the stream lanes fork behind them (see _trunk)
     fuse_bank = True               # the trunk's last convolution writes the pair kernel's feature bank itself (fgvc_conv_split_bank_f16f6p_f32)
                                    # when the caller asks for f16f6 rows of a 256-channel stage: no dense f32 output, no normalise pass;
@@ -556,10 +559,16 @@ class ResNet(nn.Module):
                 H, W = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
                 bufs = self._split_buffers((si, bi), N, Cout, H, W, dev, ("s_a", "s_y", "f_y", "f_idt"))
                 buf = {k: v[lo:hi] for k, v in bufs.items()}
-                ops.conv_s2_split(cur["split"], wt["ds"][0], wt["ds"][1], Hi, Wi, relu=False, out_f32=buf["f_idt"])
                 idt = buf["f_idt"]
-                ops.conv_s2_split(cur["split"], wt["c1"][0], wt["c1"][1], Hi, Wi, relu=True, out_split=buf["s_a"], out_fmt=f_a,
-                                  out_scale_log2=s_a, overflow=ovf)
+                w1, wd = wt["c1"][0], wt["ds"][0]
+                if self.fuse_s2_projection and calib is None and w1.shape[0] == 9 and wd.shape[0] == 1 and wd.shape[2] == w1.shape[2]:
+                    # one launch: the projection's pixels are the 3x3 kernel's centre tap (fgvc_conv_s2_split_proj_fmt_f32)
+                    ops.conv_s2_split(cur["split"], w1, wt["c1"][1], Hi, Wi, relu=True, out_split=buf["s_a"], out_fmt=f_a,
+                                      out_scale_log2=s_a, overflow=ovf, proj=(wd, wt["ds"][1], idt))
+                else:
+                    ops.conv_s2_split(cur["split"], wd, wt["ds"][1], Hi, Wi, relu=False, out_f32=idt)
+                    ops.conv_s2_split(cur["split"], w1, wt["c1"][1], Hi, Wi, relu=True, out_split=buf["s_a"], out_fmt=f_a,
+                                      out_scale_log2=s_a, overflow=ovf)
             elif blk.conv1.conv.stride != (1, 1):
                 # other strides: strided 3x3 and strided projection in MIOpen, NHWC in and out (the dense f32 tensors ARE
                 # channels_last tensors), then back onto the bf16 pipe: ReLU + split in one pass
@@ -780,7 +789,7 @@ class ResNet(nn.Module):
         cache = self.__dict__.setdefault("_split_cache", {})
         # (everything a captured pass bakes in besides the input: the class-level switches tests and A/B runs flip between calls)
         sig = (self.arith, self.split_lanes, self.use_conv64, self.use_stem7, self.use_s2_conv, self.conv64_f16f8, self.res_from_split,
-               self.use_split_conv, self.fuse_bank, self.fold_projection, self.layer1_whole_batch, tuple(self.out_indices))
+               self.use_split_conv, self.fuse_bank, self.fold_projection, self.fuse_s2_projection, self.layer1_whole_batch, tuple(self.out_indices))
         key = ("graph", tuple(x.shape), x.device, bool(normalize), split_fmt, split_if is not None, sig)
         ent = cache.get(key)
         if ent is None:                                        # first call of this shape: eager (it may calibrate and allocate)

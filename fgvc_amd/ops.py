@@ -1061,16 +1061,32 @@ def conv64_split(x_split: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, H: 
 
 def conv_s2_split(x_split: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, H: int, W: int, relu: bool,
                   out_split: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None, out_fmt: int = ACT_BF16X2,
-                  out_scale_log2: int = 0, overflow: Optional[torch.Tensor] = None) -> None:
+                  out_scale_log2: int = 0, overflow: Optional[torch.Tensor] = None,
+                  proj: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, proj_relu: bool = False) -> None:
     """3x3 / stride 2 / pad 1 or 1x1 / stride 2 convolution + bias (+ ReLU) on the bf16 pipe (fgvc_conv_s2_split_f32).
     x_split: padded split NHWC of the (N, H, W) input; w, bias from prepare_conv_s2; outputs for the
-    ((H-1)//2+1, (W-1)//2+1) result: out_split (padded split NHWC) and / or out_f32 (dense NHWC f32)."""
-    x_split = _chk(x_split, torch.int16, "x_split")
+    ((H-1)//2+1, (W-1)//2+1) result: out_split (padded split NHWC) and / or out_f32 (dense NHWC f32).
+    proj = (w2, bias2, out2_f32): the block's 1x1 / stride 2 projection of the same input in the same launch (3x3 form only,
+    fgvc_conv_s2_split_proj_fmt_f32): w2, bias2 from prepare_conv_s2 of the 1x1 weights with the same Cout, out2_f32 dense NHWC f32;
+    both results equal the two separate calls bit for bit."""
     N, Hp, Wp, nch, _ = x_split.shape
     taps, nch_w, n_ct = w.shape[:3]
     Cout = n_ct * 32
-    assert tuple(w.shape[3:]) == (4, 64, 8) and nch_w == nch and taps in (1, 9) and bias.shape == (Cout,)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if proj is not None:                       # refused on the host, before anything touches the device
+        w2, bias2, out2 = proj
+        if taps != 9:
+            raise ValueError("conv_s2_split: a projection rides in the 3x3 form only (w has %d taps)" % taps)
+        if w2.dim() != 6 or tuple(w2.shape[:2]) != (1, nch) or tuple(w2.shape[3:]) != (4, 64, 8) or w2.dtype != torch.int16:
+            raise ValueError("conv_s2_split: proj weights must be prepare_conv_s2's 1x1 form (1, %d, Cout/32, 4, 64, 8) int16, got %s %s"
+                             % (nch, tuple(w2.shape), w2.dtype))
+        if w2.shape[2] != n_ct or tuple(bias2.shape) != (Cout,):
+            raise ValueError("conv_s2_split: the projection's Cout (%d, bias %s) differs from the convolution's %d"
+                             % (w2.shape[2] * 32, tuple(bias2.shape), Cout))
+        if out2.dtype != torch.float32 or tuple(out2.shape) != (N, Ho, Wo, Cout) or not out2.is_contiguous():
+            raise ValueError("conv_s2_split: proj output must be contiguous f32 %s" % ((N, Ho, Wo, Cout),))
+    x_split = _chk(x_split, torch.int16, "x_split")
+    assert tuple(w.shape[3:]) == (4, 64, 8) and nch_w == nch and taps in (1, 9) and bias.shape == (Cout,)
     Hop, Wop = conv_pad_dims(Ho, Wo)
     if out_split is not None:
         assert out_split.dtype == torch.int16 and tuple(out_split.shape) == (N, Hop, Wop, Cout // 32, 64) and out_split.is_contiguous()
@@ -1078,6 +1094,13 @@ def conv_s2_split(x_split: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, H:
         assert out_f32.dtype == torch.float32 and tuple(out_f32.shape) == (N, Ho, Wo, Cout) and out_f32.is_contiguous()
     if out_fmt != ACT_BF16X2 and out_split is not None:
         assert overflow is not None and overflow.dtype == torch.int32 and overflow.device == x_split.device
+    if proj is not None:
+        w2, bias2, out2 = _chk(proj[0], torch.int16, "proj w2"), _chk(proj[1], torch.float32, "proj bias2"), proj[2]
+        assert out2.device == x_split.device
+        _lib.call("fgvc_conv_s2_split_proj_fmt_f32", _ptr(x_split), _ptr(w), _ptr(bias), _ptr(out_split), _ptr(out_f32), _ptr(w2), _ptr(bias2),
+                  _ptr(out2), N, H, W, Hp, Wp, nch * 32, Cout, 3, w2.shape[2] * 32, Hop, Wop, int(relu), int(proj_relu), int(out_fmt),
+                  int(out_scale_log2), _ptr(overflow), _stream(x_split))
+        return
     _lib.call("fgvc_conv_s2_split_fmt_f32", _ptr(x_split), _ptr(w), _ptr(bias), _ptr(out_split), _ptr(out_f32), N, H, W, Hp, Wp,
               nch * 32, Cout, 3 if taps == 9 else 1, Hop, Wop, int(relu), int(out_fmt), int(out_scale_log2), _ptr(overflow),
               _stream(x_split))

@@ -511,6 +511,14 @@ int fgvc_conv_s2_split_f32(const uint16_t* x, const uint16_t* w, const float* bi
 int fgvc_conv_s2_split_fmt_f32(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y_split, float* y_f32, int N,
                                int H, int W, int Hp, int Wp, int Cin, int Cout, int KS, int Hop, int Wop, int relu, int out_fmt,
                                int out_scale_log2, int* overflow, void* stream);
+/* ... and the block's 1x1 / stride 2 PROJECTION of the same input in the same launch (KS = 3 only; w2, bias2, y2_f32 all null: exactly
+ * fgvc_conv_s2_split_fmt_f32): y2_f32 = conv1x1s2(x, w2) + bias2 [ReLU if relu2], dense NHWC f32 [N][Ho][Wo][Cout], w2 in the KS = 1
+ * operand order.  The projection reads the 3x3 kernel's centre tap, which is already staged; both outputs equal the two separate
+ * launches bit for bit.  Cout2 != Cout or KS != 3 with a projection: FGVC_ERR_UNSUPPORTED. */
+int fgvc_conv_s2_split_proj_fmt_f32(const uint16_t* x, const uint16_t* w, const float* bias, uint16_t* y_split, float* y_f32,
+                                    const uint16_t* w2, const float* bias2, float* y2_f32, int N, int H, int W, int Hp, int Wp, int Cin,
+                                    int Cout, int KS, int Cout2, int Hop, int Wop, int relu, int relu2, int out_fmt, int out_scale_log2,
+                                    int* overflow, void* stream);
 /* The stem: 7x7 / stride 2 / zero padding 3 convolution of 3-channel frames to 64 channels, BatchNorm folded, + bias
  * (+ ReLU) (resnet.py:457-466 with pool_type 'none'), from the f32 NCHW frames x[N][3][H][W] to y_f32 (dense NHWC f32
  * [N][Ho][Wo][64]) and / or y_split (padded split NHWC, Hop x Wop); Ho x Wo = ((H-1)/2+1) x ((W-1)/2+1).

@@ -38,7 +38,8 @@ names = {"fgvc_pair_topk_f16f6": "pair_topk_kernel_v7", "fgvc_pair_topk_f16f6[v8
          "fgvc_merge_refine_topk_f32[scan]": "refine_scan_kernel",
          "fgvc_conv64_split_f32": "conv64_kernel", "fgvc_conv64_split_fmt_f32[conv1]": "conv64p_kernel<false, false, 1>",
          "fgvc_conv64_split_fmt_f32[conv2]": "conv64p_kernel<true, true, 1>",
-         "fgvc_stem7_split_f32": "stem7_kernel", "fgvc_conv_s2_split_f32": "conv_s2_kernel<3>"}
+         "fgvc_stem7_split_f32": "stem7_kernel", "fgvc_conv_s2_split_f32": "conv_s2_kernel<3, false>",
+         "fgvc_conv_s2_split_proj_fmt_f32": "conv_s2_kernel<3, true>"}       # (the 3x3 / stride 2 convolution alone | with the block's projection riding along)
 HW = 120 * 214
 tiles = -(-HW // 32) * -(-HW // 32)
 # matrix-pipe cycles the dense kernels execute by construction (ragged tiles included), for the cross-check
