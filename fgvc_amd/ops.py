@@ -557,7 +557,8 @@ def dense_attend(qfeat: torch.Tensor, kfeat: torch.Tensor, labels: torch.Tensor,
                  dense_mask: Optional[torch.Tensor] = None, precision: str = "f32") -> torch.Tensor:
     """topk=None branch (local_attention.py:376-383): weights over every unmasked key of every key slot.
     qfeat (HWq, C) f32 rows, kfeat (T, HWk, C), labels (T, HWk, P) -> (HWq, P).  One HWk x HWq volume slab lives at a time
-    (fgvc_corr_volume_f32, or _bf16x3 with precision='bf16x3' for C % 64 == 0), streamed once by fgvc_dense_attend_f32.
+    (fgvc_corr_volume_f32 for C = 32, 64, 128 or 256, or _bf16x3 with precision='bf16x3' for C = 64, 128 or 256 -- any other
+    width is refused), streamed once by fgvc_dense_attend_f32.
     mode: 'softmax' | 'cosine' (clamp(min=0)^2) | 'raw' (the affinity itself is the weight: local_square_attention, :38-103)."""
     qfeat, kfeat = _chk(qfeat, torch.float32, "qfeat"), _chk(kfeat, torch.float32, "kfeat")
     labels = _chk(labels, torch.float32, "labels")

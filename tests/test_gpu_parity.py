@@ -10,7 +10,9 @@ import pytest
 import torch
 
 from oracle import fgvc_oracle as O
+from tests import volume_cases as VC
 from tests import window_cases as WC
+from tests.volume_cases import _decode_f16f6          # the decoder of fgvc_split_f16f6 rows, shared with tests/test_gpu_volume_ops.py
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -163,6 +165,8 @@ def test_corr_volume(dev):
         vb = ops.corr_volume(qs, ks, 0.07, "bf16").cpu()
         eb = float((vb.double() - ref64).abs().max())
         assert eb < 3e-2, eb        # plain bf16 is NOT within the 1e-3 bar (reported, reduced precision; bound ~ 5 sigma of its rounding)
+        mb, Ab = VC.bf16_model64(qs, ks, 0.07)      # ... but it IS hi.hi of its own operands: f32 accumulation only, every entry (tests/volume_cases.py)
+        assert bool(((vb.double() - mb).abs() <= VC.accum_bound("bf16", C, Ab, 0.07)).all())
         e8 = -1.0
         if C == 256:               # f16 + block-scaled fp8 cross terms: parity-grade at two bf16-MFMA times per tile
             v8 = ops.corr_volume(ops.split_f16f8(qf), ops.split_f16f8(kf), 0.07, "f16f8").cpu()
@@ -201,30 +205,6 @@ def test_corr_volume_f16f8_ragged_shapes_and_adversarial_rows(dev):
             assert vol.shape == (HWk, HWq)
             err = float((vol.double() - ref).abs().max())
             assert err < TOL, (prec, HWq, HWk, kind, err)
-
-
-def _decode_f16f6(sp):
-    """fgvc_split_f16f6 rows (n, 1024) uint8 -> h, h6, l6 as (n, 256) float64 (h6 / l6 dequantised with their 2^(s-4) scales);
-    the layout is documented in fgvc_amd/csrc/corr_volume_f6.hip"""
-    import numpy as np
-    sp = sp.cpu().numpy()
-    n = sp.shape[0]
-    h = sp[:, :512].copy().view(np.float16).astype(np.float64)
-    lut = np.array([(m / 8.0 if e == 0 else (1 + m / 8.0) * 2.0 ** (e - 1)) for e in range(4) for m in range(8)])
-    lut = np.concatenate([lut, -lut])
-    outs = []
-    for base in (512, 704):
-        vals = np.zeros((n, 256))
-        for u in range(2):
-            for g in range(4):
-                b16 = sp[:, base + 96 * u + 16 * g: base + 96 * u + 16 * g + 16]
-                b8 = sp[:, base + 96 * u + 64 + 8 * g: base + 96 * u + 64 + 8 * g + 8]
-                bits = np.unpackbits(np.concatenate([b16, b8], axis=1), axis=1, bitorder="little")     # (n, 192)
-                codes = (bits.reshape(n, 32, 6) * (1 << np.arange(6))).sum(-1)
-                sc = sp[:, 896 + 4 * g + (u if base == 512 else 2 + u)].astype(np.int64) - 127
-                vals[:, 128 * u + 32 * g: 128 * u + 32 * g + 32] = lut[codes] * (2.0 ** sc)[:, None]
-        outs.append(vals)
-    return h, outs[0], outs[1]
 
 
 def test_split_f16f6_format(dev):
