@@ -39,6 +39,9 @@ int local_merge_plan_launch(const int32_t*, const float*, const int32_t*, int, i
 int topk_coord_launch(const int32_t*, const float*, int, int, int, int, int, float*, hipStream_t);
 int topk_coord_rows_launch(const int32_t*, const float*, int, int, int, int, int, int, float*, hipStream_t);
 int cycle_chase_launch(const float*, const float*, const float*, int, int, int, int, int, float*, float*, hipStream_t);
+int flow_from_lists_launch(const int32_t*, const float*, int, int, int, int, int, int, int, int, int, int, int, float*, uint8_t*, hipStream_t);
+int flow_consistency_launch(const float*, const float*, int, int, int, int, float, float*, float*, hipStream_t);
+int warp_launch(const float*, const float*, int, int, int, int, int, int, float*, hipStream_t);
 int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
                               hipStream_t);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
@@ -584,6 +587,35 @@ int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* st
                  reinterpret_cast<uintptr_t>(back_out)) & 7u) == 0,
                FGVC_ERR_INVALID_ARG, "fgvc_cycle_chase_f32: the (x, y) arrays must be 8-byte aligned");
   return cycle_chase_launch(fields, traj, start_xy, n, P, H, W, scale, back_out, err_out, (hipStream_t)stream);
+}
+
+int fgvc_flow_from_lists_f32(const int32_t* idx, const float* weight, int rows, int H, int W, int R, int topk, int scale, int renorm, int h,
+                             int w, int pad_left, int pad_top, float* flow_out, uint8_t* valid_out, void* stream) {
+  FGVC_REQUIRE(idx && weight && flow_out && valid_out, FGVC_ERR_INVALID_ARG, "fgvc_flow_from_lists_f32: null pointer");
+  FGVC_REQUIRE(rows >= 1 && rows <= 65535 && H > 0 && W > 0 && R >= 0 && topk >= 1 && scale >= 1 && (long long)H * W < (1ll << 30),
+               FGVC_ERR_INVALID_ARG, "fgvc_flow_from_lists_f32: bad shape (rows=%d, %d x %d cells, R=%d, topk=%d, scale=%d)", rows, H, W, R, topk, scale);
+  // grid.y = ceil(h / 16) is 16-bit; pixel and cell coordinates times scale stay inside an int
+  FGVC_REQUIRE(h > 0 && w > 0 && pad_left >= 0 && pad_top >= 0 && h <= 16 * 65535 && (long long)h * w < (1ll << 30) &&
+                   (long long)pad_left + w < (1ll << 30) && (long long)pad_top + h < (1ll << 30) && (long long)imax(H, W) * scale < (1ll << 30),
+               FGVC_ERR_INVALID_ARG, "fgvc_flow_from_lists_f32: bad output (%d x %d, pad %d, %d)", h, w, pad_left, pad_top);
+  return flow_from_lists_launch(idx, weight, rows, H, W, R, topk, scale, renorm != 0, h, w, pad_left, pad_top, flow_out, valid_out,
+                                (hipStream_t)stream);
+}
+
+int fgvc_flow_consistency_f32(const float* flow_fw, const float* flow_bw, int n, int h, int w, int mode, float diff, float* occ_fw,
+                              float* occ_bw, void* stream) {
+  FGVC_REQUIRE(flow_fw && flow_bw && occ_fw && occ_bw, FGVC_ERR_INVALID_ARG, "fgvc_flow_consistency_f32: null pointer");
+  FGVC_REQUIRE(n >= 1 && n <= 65535 && h > 0 && w > 0 && (long long)h * w < (1ll << 30), FGVC_ERR_INVALID_ARG,
+               "fgvc_flow_consistency_f32: bad shape (n=%d, %d x %d)", n, h, w);
+  FGVC_REQUIRE(mode == FGVC_FLOW_CONSISTENCY || mode == FGVC_FLOW_FB_ABS, FGVC_ERR_INVALID_ARG, "fgvc_flow_consistency_f32: mode=%d", mode);
+  return flow_consistency_launch(flow_fw, flow_bw, n, h, w, mode, diff, occ_fw, occ_bw, (hipStream_t)stream);
+}
+
+int fgvc_warp_f32(const float* feat, const float* flow, int N, int C, int H, int W, int align_corners, int use_mask, float* out, void* stream) {
+  FGVC_REQUIRE(feat && flow && out, FGVC_ERR_INVALID_ARG, "fgvc_warp_f32: null pointer");
+  FGVC_REQUIRE(N >= 1 && N <= 65535 && C >= 1 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), FGVC_ERR_INVALID_ARG,
+               "fgvc_warp_f32: bad shape (N=%d, C=%d, %d x %d)", N, C, H, W);
+  return warp_launch(feat, flow, N, C, H, W, align_corners != 0, use_mask != 0, out, (hipStream_t)stream);
 }
 
 int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,

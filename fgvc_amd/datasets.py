@@ -633,3 +633,36 @@ def davis_evaluate(model, dataset: "Davis2017", backend: str = "host") -> dict:
             gt = torch.from_numpy(gt).to(pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda else "cuda")
         seqs[meta["name"]] = (gt, pred)
     return metrics.davis_jf(seqs, backend=backend)
+
+
+FLO_MAGIC = 202021.25       # 'PIEH' read as a little-endian float32: the Middlebury .flo header
+
+
+def write_flo(path, flow) -> None:
+    """Middlebury .flo: the magic float, int32 width and height, then h x w (u, v) float32 pairs row by row, little-endian.  flow (2, h, w)
+    (channel 0 = x, as the trackers return it) or (h, w, 2); numpy only."""
+    f = np.asarray(flow)
+    if f.ndim != 3 or 2 not in (f.shape[0], f.shape[2]):
+        raise ValueError(f"write_flo: a flow of shape (2, h, w) or (h, w, 2), got {f.shape}")
+    if f.shape[0] == 2:                                                   # (2, h, w) wins where both readings fit
+        f = f.transpose(1, 2, 0)
+    h, w = f.shape[:2]
+    with open(path, "wb") as fh:
+        np.array([FLO_MAGIC], "<f4").tofile(fh)
+        np.array([w, h], "<i4").tofile(fh)
+        np.ascontiguousarray(f, "<f4").tofile(fh)
+
+
+def read_flo(path) -> np.ndarray:
+    """-> (2, h, w) float32, channel 0 = x.  ValueError for a wrong magic number or a truncated file."""
+    with open(path, "rb") as fh:
+        head = fh.read(12)
+        if len(head) != 12 or np.frombuffer(head[:4], "<f4")[0] != np.float32(FLO_MAGIC):
+            raise ValueError(f"{path}: not a Middlebury .flo file (magic number)")
+        w, h = (int(v) for v in np.frombuffer(head[4:], "<i4"))
+        if w < 1 or h < 1:
+            raise ValueError(f"{path}: size {w} x {h}")
+        data = np.frombuffer(fh.read(), "<f4")
+    if data.size != 2 * h * w:
+        raise ValueError(f"{path}: {data.size} values for a {h} x {w} flow")
+    return np.ascontiguousarray(data.reshape(h, w, 2).transpose(2, 0, 1)).astype(np.float32)

@@ -844,3 +844,99 @@ def cycle_check_groups(fields: torch.Tensor, traj: torch.Tensor, times: torch.Te
         v, e, _ = cycle_check(fields, traj[s:, cols], s, q, scale, thresh, Hf, Wf)
         vis[s:, cols], err[s:, cols] = v, e
     return vis, err
+
+
+# ---- dense optical flow between frames (test_cfg.flow, an extension key) ------------------------------------------------
+#
+# The window lists of a frame pair ARE a correspondence: the cycle check above reads them as coordinate fields on the feature grid.  Here
+# both time directions of every pair `step` frames apart are planned as single-slot rows of ONE affinity run, read out to full resolution by
+# one kernel, and checked against each other by one more.
+
+FLOW_OCCLUSIONS = ("consistency", "fb_abs")
+
+
+@dataclass
+class FlowConfig:
+    """test_cfg.flow = dict(type='window', radius=None, step=1, renorm=True, occlusion=None | 'consistency' | 'fb_abs', diff=1.5), parsed.
+    `radius`: the local window of the lists, in feature cells; `step`: the frame distance of a pair; `renorm`: ops.flow_from_lists';
+    `occlusion`: the forward-backward check to run on the two flows (ops.flow_consistency), `diff` its 'fb_abs' threshold in pixels."""
+    radius: int = 12
+    step: int = 1
+    renorm: bool = True
+    occlusion: Optional[str] = None
+    diff: float = 1.5
+
+
+def parse_flow(spec, default_radius: int) -> Optional[FlowConfig]:
+    """None -> None (the option is off).  A mapping with type='window' -> FlowConfig; any other `type` (or none), an unknown key or a value
+    out of range raises ValueError ('range_map', the reference's third occlusion mode, NotImplementedError: ops.flow_consistency says
+    why), a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError("test_cfg.flow: a dict such as dict(type='window', radius=None, step=1, renorm=True, occlusion=None, diff=1.5), "
+                        f"got {type(spec).__name__}")
+    spec = dict(spec)
+    typ = spec.pop("type", None)
+    if typ != "window":
+        raise ValueError(f"test_cfg.flow: type={typ!r} (only 'window': the read-out of the local window's top-k lists)")
+    radius, step, renorm = spec.pop("radius", None), spec.pop("step", 1), spec.pop("renorm", True)
+    occlusion, diff = spec.pop("occlusion", None), spec.pop("diff", 1.5)
+    if spec:
+        raise ValueError(f"test_cfg.flow: unknown key(s) {sorted(spec)} (type, radius, step, renorm, occlusion, diff)")
+    radius = int(default_radius) if radius is None else int(radius)
+    if radius < 0:
+        raise ValueError(f"test_cfg.flow: radius={radius}")
+    if isinstance(step, bool) or int(step) != step or int(step) < 1:
+        raise ValueError(f"test_cfg.flow: step={step!r} (the frame distance of a pair: an integer >= 1)")
+    if not isinstance(renorm, (bool, int)) or renorm not in (0, 1):
+        raise ValueError(f"test_cfg.flow: renorm={renorm!r} (True or False)")
+    if occlusion == "range_map":
+        ops._flow_mode(occlusion)
+    if occlusion is not None and occlusion not in FLOW_OCCLUSIONS:
+        raise ValueError(f"test_cfg.flow: occlusion={occlusion!r} (None or one of {FLOW_OCCLUSIONS})")
+    diff = float(diff)
+    if not (math.isfinite(diff) and diff >= 0):
+        raise ValueError(f"test_cfg.flow: diff={diff} (a finite number of pixels >= 0)")
+    return FlowConfig(radius, int(step), bool(renorm), occlusion, diff)
+
+
+def flow_plan(n_frames: int, step: int, HW: int, cfg: LocalConfig) -> LocalPlan:
+    """The schedule of a clip's flow pairs, one key slot per row (t_max = 1): rows 0 .. T-step-1 are the forward pairs (query g, key
+    g + step), the T - step rows after them the backward pairs (query g + step, key g).  Rows are chunked so that a chunk's pair lists
+    (HW * topk * 8 bytes per pair) stay within cfg.pair_budget, as plan_local_clip chunks."""
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"flow_plan: step={step}")
+    n = max(0, int(n_frames) - step)
+    pairs = [(g, g + step) for g in range(n)] + [(g + step, g) for g in range(n)]
+    pair_bytes = HW * int(cfg.topk) * 8
+    if pairs and pair_bytes > cfg.pair_budget:
+        raise ValueError(f"pair_budget={cfg.pair_budget} bytes holds less than one pair's lists ({pair_bytes} bytes)")
+    per = max(1, int(cfg.pair_budget) // pair_bytes) if pairs else 1
+    chunks = [(r0, min(r0 + per, len(pairs)), r0, min(r0 + per, len(pairs))) for r0 in range(0, len(pairs), per)]
+    return LocalPlan(int(n_frames), pairs, [[p] for p in range(len(pairs))], [[kf] for _, kf in pairs], 1, chunks, pair_bytes)
+
+
+def flow_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, size: Tuple[int, int],
+                pad: Tuple[int, int] = (0, 0), step: int = 1, renorm: bool = True, stats: Optional[dict] = None):
+    """Dense flow of every frame pair `step` apart, both directions: flow_fw[g] takes frame g to frame g + step, flow_bw[g] frame g + step
+    to frame g.  feats_hwc as run_local_affinity takes them; `cfg`: a LocalConfig (its radius is the window; precede_frames / with_first are
+    not read: the plan is flow_plan's); `scale` = padded frame / feature grid, `size` = the network size (h, w), `pad` = (left, top).
+    Returns flow_fw, flow_bw (T-step, 2, h, w) f32 and valid_fw, valid_bw (T-step, h, w) uint8 -- one affinity run (chunked within
+    cfg.pair_budget) and ONE fgvc_flow_from_lists_f32 launch for both directions.  `stats`: run_local_affinity's."""
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    n = max(0, T - int(step))
+    h, w = (int(v) for v in size)
+    if n == 0:
+        z, v = torch.empty((0, 2, h, w), device=dev), torch.empty((0, h, w), device=dev, dtype=torch.uint8)
+        return z, z.clone(), v, v.clone()
+    plan = flow_plan(T, step, Hf * Wf, cfg)
+    idx, _, weight = run_local_affinity(feats_hwc, Hf, Wf, plan, cfg, stats)
+    flow, valid = ops.flow_from_lists(idx, weight, Hf, Wf, int(cfg.radius), int(scale), (h, w), pad, renorm)
+    return flow[:n], flow[n:], valid[:n], valid[n:]
+
+
+def flow_occlusion(flow_fw: torch.Tensor, flow_bw: torch.Tensor, mode: str = "consistency", diff: float = 1.5):
+    """occ_fw, occ_bw (n, 1, h, w) f32, 1 = consistent: the reference's occlusion_estimation on the two flows (ops.flow_consistency)."""
+    return ops.flow_consistency(flow_fw, flow_bw, mode, diff)

@@ -476,3 +476,27 @@ def davis_jf(sequences: Dict[str, tuple], backend: str = "host") -> Dict[str, ob
         per_seq[name] = {"J&F": (jm + fm) / 2, "J": jm, "F": fm}
     jm, fm = float(np.mean(Js)), float(np.mean(Fs))
     return {"J&F-Mean": (jm + fm) / 2, "J-Mean": jm, "F-Mean": fm, "sequences": per_seq}
+
+
+def flow_epe(pred, gt, valid=None) -> dict:
+    """End-point error of a dense flow: pred, gt (..., 2, h, w) torch tensors (channel 0 = x) on one device, either one; valid (..., h, w)
+    or (..., 1, h, w), non-zero = scored (None: every pixel).  Returns {'epe': the mean error in pixels, '1px' / '3px' / '5px': the share
+    of scored pixels whose error is below 1, 3 and 5 px, 'n': how many were scored}; with no scored pixel the four figures are NaN."""
+    import torch
+    if pred.shape != gt.shape or pred.dim() < 3 or pred.shape[-3] != 2:
+        raise ValueError(f"flow_epe: two flows of one shape (..., 2, h, w), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    err = (pred.to(torch.float64) - gt.to(torch.float64)).pow(2).sum(-3).sqrt()                      # (..., h, w)
+    if valid is None:
+        keep = torch.ones_like(err, dtype=torch.bool)
+    else:
+        keep = valid != 0
+        if keep.dim() == err.dim() + 1 and keep.shape[-3] == 1:
+            keep = keep.squeeze(-3)
+        if keep.shape != err.shape:
+            raise ValueError(f"flow_epe: valid of shape {tuple(valid.shape)} for flows of shape {tuple(pred.shape)}")
+    e = err[keep.to(err.device)]
+    n = int(e.numel())
+    if n == 0:
+        return {"epe": float("nan"), "1px": float("nan"), "3px": float("nan"), "5px": float("nan"), "n": 0}
+    return {"epe": float(e.mean()), "1px": float((e < 1).double().mean()), "3px": float((e < 3).double().mean()),
+            "5px": float((e < 5).double().mean()), "n": n}

@@ -12,6 +12,7 @@ import torch
 
 from .. import ops
 from ..ops import MaskSpec
+from .registry import OPERATORS
 
 __all__ = [
     "NeighborMask", "spatial_neighbor", "masked_attention_efficient", "masked_attention_efficient_v2",
@@ -19,6 +20,7 @@ __all__ = [
     "masked_attention_efficient_correlation_v2",
     "compute_affinity", "propagate", "non_local_attention", "local_square_attention", "coords_grid", "cat", "video2images",
     "images2video", "bilinear_sample",
+    "Warp", "coords_grid_warp", "flow_to_coords", "forward_backward_consistency", "forward_backward_absdiff", "occlusion_estimation",
 ]
 
 
@@ -375,3 +377,76 @@ def masked_attention_efficient_correlation(query_frame, key_frames, value, radiu
     unused."""
     return masked_attention_efficient_correlation_v2(query_frame, key_frames, value, radius, corr_infer, feat_extractor,
                                                      temperature=temperature, topk=topk, normalize=normalize, sstep=sstep, tstep=tstep)
+
+
+# ---- dense flow: warp.py and occlusion_estimation.py (DESIGN.md section 17) ---------------------------------------------------------------
+def _flow_f32(t, name: str):
+    """GPU tensors only, f32 only: the reference itself fails on float64 input (Warp multiplies by a mask made with torch.ones, f32, and
+    grid_sample refuses the mixed pair)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: float32 only, got {t.dtype} (the reference fails on anything else: the mask Warp builds with "
+                        "torch.ones is float32)")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
+    return t
+
+
+def flow_to_coords(flow):
+    """occlusion_estimation.py:9-24: the pixel grid shifted by `flow` (B, 2, H, W), channel 0 = x."""
+    B, _, H, W = flow.shape
+    yy, xx = torch.meshgrid(torch.arange(0, H, device=flow.device), torch.arange(0, W, device=flow.device), indexing="ij")
+    return torch.stack([xx, yy], 0).float()[None].repeat(B, 1, 1, 1) + flow
+
+
+def coords_grid_warp(flow):
+    """warp.py:9-26: the shifted grid scaled to [-1, 1] by W - 1 / H - 1, (B, H, W, 2)."""
+    _, _, H, W = flow.shape
+    grid = flow_to_coords(flow)
+    grid[:, 0] = grid[:, 0] * 2. / max(W - 1, 1) - 1.
+    grid[:, 1] = grid[:, 1] * 2. / max(H - 1, 1) - 1.
+    return grid.permute(0, 2, 3, 1)
+
+
+@OPERATORS.register_module()
+class Warp(torch.nn.Module):
+    """warp.py:28-90: warp a feature map by a flow (fgvc_warp_f32).  mode='bilinear' and padding_mode='zeros' only."""
+
+    def __init__(self, mode: str = "bilinear", padding_mode: str = "zeros", align_corners: bool = False, use_mask: bool = True):
+        super().__init__()
+        self.mode, self.padding_mode, self.align_corners, self.use_mask = mode, padding_mode, align_corners, use_mask
+
+    def forward(self, feat, flow):
+        if self.mode != "bilinear" or self.padding_mode != "zeros":
+            raise NotImplementedError(f"fgvc_amd: Warp(mode={self.mode!r}, padding_mode={self.padding_mode!r}); only 'bilinear' / 'zeros'")
+        return ops.warp(_flow_f32(feat, "feat"), _flow_f32(flow, "flow"), bool(self.align_corners), bool(self.use_mask))
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}(mode={self.mode}, padding_mode={self.padding_mode}, align_corners={self.align_corners},"
+                f"use_mask={self.use_mask})")
+
+
+def occlusion_estimation(flow_fw, flow_bw, mode: str = "consistency", **kwarg):
+    """occlusion_estimation.py:147-177: dict(occ_fw, occ_bw), (N, 1, H, W), 1 = not occluded; both directions in one launch
+    (fgvc_flow_consistency_f32).  `warp_cfg` is accepted and ignored, as the reference ignores it (:108, :135 build Warp() with its
+    defaults); `diff` is read by 'fb_abs'.  'range_map' raises NotImplementedError."""
+    assert mode in ("consistency", "range_map", "fb_abs"), f"mode must be 'consistency', 'range_map' or 'fb_abs', but got {mode}"
+    ops._flow_mode(mode)                                    # 'range_map': refused before anything else is looked at
+    kwarg = dict(kwarg)
+    kwarg.pop("warp_cfg", None)
+    diff = kwarg.pop("diff", 1.5)
+    if kwarg:
+        raise TypeError(f"occlusion_estimation: unexpected keyword(s) {sorted(kwarg)}")
+    occ_fw, occ_bw = ops.flow_consistency(_flow_f32(flow_fw, "flow_fw"), _flow_f32(flow_bw, "flow_bw"), mode, diff)
+    return dict(occ_fw=occ_fw, occ_bw=occ_bw)
+
+
+def forward_backward_consistency(flow_fw, flow_bw, warp_cfg: dict = dict(type="Warp", align_corners=True)):
+    """occlusion_estimation.py:95-119 (one direction of the launch that computes both)."""
+    return occlusion_estimation(flow_fw, flow_bw, "consistency")["occ_fw"]
+
+
+def forward_backward_absdiff(flow_fw, flow_bw, warp_cfg: dict = dict(type="Warp", align_corners=True), diff: int = 1.5):
+    """occlusion_estimation.py:122-144."""
+    return occlusion_estimation(flow_fw, flow_bw, "fb_abs", diff=diff)["occ_fw"]

@@ -204,29 +204,88 @@ class VanillaTracker(BaseTracker):
             raise NotImplementedError(f"fgvc_amd: test_cfg.occlusion is read by the points call only (rgbs= / query_points=); {what} "
                                       "has no visibility output -- remove the key for this call")
 
-    def _cycle_fields(self, feats, Hf, Wf, w, occ: engine.OcclusionConfig):
-        """The clip's backward coordinate fields from the bank get_feats_hwc(split=True) returned, on this tracker's own topk, temperature
-        and normalisation key.  The f16 + FP6 bank gives its exact f32 channels (a view), a split_f16x2 bank goes in as it is where the
-        16-bit pair kernel takes the window, any other bank as f32 rows.  Returns (fields (T-1, HW, 2), scale)."""
+    def _window_rows(self, feats, Hf, Wf, radius: int, key: str = "occlusion"):
+        """The bank get_feats_hwc(split=True) returned, as the rows engine.run_local_affinity takes for a window of `radius`, and the
+        LocalConfig of single-slot pairs on this tracker's own topk, temperature and normalisation key.  The f16 + FP6 bank gives its exact
+        f32 channels (a view), a split_f16x2 bank goes in as it is where the 16-bit pair kernel takes the window, any other bank as f32
+        rows.  `key`: the test_cfg key that asked, for the refusal's text."""
         cfg = self.engine_config()
         fmt = ops.bank_format(feats, cfg.bank_fmt)
         if fmt == "f16f6x":
             rows = ops.f32_of_f16f6x(feats)
         elif fmt == "f16f6":
-            raise NotImplementedError("fgvc_amd: test_cfg.occlusion needs f32-grade rows; a split_f16f6p() bank (pair_split_fmt='f16f6' with "
+            raise NotImplementedError(f"fgvc_amd: test_cfg.{key} needs f32-grade rows; a split_f16f6p() bank (pair_split_fmt='f16f6' with "
                                       "pair_refine=False) holds 11-bit ones -- set pair_refine=True (the default) or pair_split_fmt='f16'")
         elif fmt == "f16" and not ops.split_path_ok(feats.shape[-1], Hf, Wf, cfg.topk, cfg.with_norm, None,
-                                                    ops.MaskSpec(ry=occ.radius, rx=occ.radius), True):
+                                                    ops.MaskSpec(ry=radius, rx=radius), True):
             rows = ops.unsplit_f16x2(feats)
         else:
             rows = feats
         lc = engine.LocalConfig(temperature=cfg.softmax_temperature(self.feat_channels or rows.shape[-1]), topk=int(cfg.topk),
-                                precede_frames=1, radius=occ.radius, with_first=False, with_norm=bool(cfg.with_norm),
+                                precede_frames=1, radius=radius, with_first=False, with_norm=bool(cfg.with_norm),
                                 pair_precision="f32" if cfg.pair_precision == "f32" else "auto",
                                 pair_budget=int(self.test_cfg.get("pair_budget", engine.LOCAL_PAIR_BUDGET)))
+        return rows, lc
+
+    def _cycle_fields(self, feats, Hf, Wf, w, occ: engine.OcclusionConfig):
+        """The clip's backward coordinate fields from the bank get_feats_hwc(split=True) returned (_window_rows).  Returns
+        (fields (T-1, HW, 2), scale)."""
+        rows, lc = self._window_rows(feats, Hf, Wf, occ.radius)
         scale = w // Wf                                                               # vanilla_tracker.py:609
         self.cycle_stats = {}
         return engine.backward_fields(rows, Hf, Wf, lc, scale, self.cycle_stats), scale
+
+    # ---- dense optical flow between frames (test_cfg.flow, an extension key; DESIGN.md section 17) ---------------------------------------
+    def _flow(self) -> Optional[engine.FlowConfig]:
+        """test_cfg.flow parsed (None: the option is off).  The default window is this tracker's own: neighbor_range // 2."""
+        spec = self.test_cfg.get("flow", None)
+        if spec is None:
+            return None
+        nr = self.test_cfg.get("neighbor_range", self._default_neighbor_range)
+        if nr is None and hasattr(spec, "keys") and dict(spec).get("radius") is None:
+            raise ValueError("test_cfg.flow: neighbor_range is None (no window to derive the lists' from); give flow.radius")
+        return engine.parse_flow(spec, 0 if nr is None else int(nr) // 2)
+
+    @torch.no_grad()
+    def forward_test_flow(self, imgs, img_meta=None):
+        """Dense flow between the frames of a clip `step` apart, both time directions.  imgs as the label-map call takes them: float
+        (1, 1, 3, T, h, w), or uint8 frames with test_cfg.input.  Returns a dict of CUDA tensors at the network size (h, w): flow_fw[g] takes
+        frame g to frame g + step and flow_bw[g] back, (T-step, 2, h, w) f32 in pixels, channel 0 = x; valid_fw / valid_bw (T-step, h, w)
+        uint8; with flow.occlusion set, occ_fw / occ_bw (T-step, 1, h, w) f32, 1 = consistent.  self.flow_stats: what the affinity reported."""
+        fc = self._flow()
+        if fc is None:
+            raise ValueError(f"{type(self).__name__}.forward_test_flow needs test_cfg.flow = dict(type='window', ...)")
+        if self.test_cfg.get("occlusion", None) is not None:
+            raise ValueError("fgvc_amd: test_cfg.flow and test_cfg.occlusion are both set; the flow call has its own check "
+                             "(flow.occlusion = 'consistency' | 'fb_abs') and the cycle check belongs to the points call -- remove one")
+        if imgs is None:
+            raise TypeError(f"{type(self).__name__}.forward_test_flow needs imgs")
+        ic = self._raw_input(imgs, "imgs")
+        if not imgs.is_cuda:
+            raise RuntimeError(f"fgvc_amd.{type(self).__name__} runs on the GPU only (no CPU fallback)")
+        if ic is None and (imgs.dim() != 6 or imgs.shape[0] != 1 or imgs.shape[1] != 1 or imgs.shape[2] != 3):
+            raise ValueError(f"imgs: float frames of shape (1, 1, 3, T, h, w), got {tuple(imgs.shape)}")
+        frames, (h, w), pad = self._label_frames(imgs)                                        # (T, 3, hp, wp)
+        feats, Hf, Wf = self._label_feats(frames)
+        hp, wp = frames.shape[-2:]
+        if hp % Hf or wp % Wf or hp // Hf != wp // Wf:
+            raise NotImplementedError(f"fgvc_amd: the flow read-out needs a feature cell on every `scale`-th pixel of the padded frame; {hp} x {wp} "
+                                      f"over {Hf} x {Wf} features is no whole pitch -- pad the frames to the encoder's output stride "
+                                      "(HRVanillaTracker: build it with stride = that stride)")
+        rows, lc = self._window_rows(feats, Hf, Wf, fc.radius, "flow")
+        scale = wp // Wf
+        self.flow_stats = {}
+        fw, bw, vfw, vbw = engine.flow_fields(rows, Hf, Wf, lc, scale, (h, w), (pad[0], pad[2]), fc.step, fc.renorm, self.flow_stats)
+        out = dict(flow_fw=fw, flow_bw=bw, valid_fw=vfw, valid_bw=vbw)
+        if fc.occlusion is not None:
+            out["occ_fw"], out["occ_bw"] = engine.flow_occlusion(fw, bw, fc.occlusion, fc.diff)
+        self._check_kernels()
+        return out
+
+    def _flow_call(self, rgbs, query_points, imgs, ref_seg_map) -> bool:
+        """forward_test's third call form: imgs= alone (no first-frame labels) with test_cfg.flow set.  Without the key nothing changes."""
+        return (self.test_cfg.get("flow", None) is not None and imgs is not None and ref_seg_map is None
+                and rgbs is None and query_points is None)
 
     def _visibility_from_frame0(self, feats, Hf, Wf, w, coords, qp, visibilities, occ):
         """The fourth return element of the un-regrouped call: every point is tracked from frame 0, whatever its query time
@@ -292,6 +351,8 @@ class VanillaTracker(BaseTracker):
         """rgbs (1,T,3,h,w), query_points (1,P,3)=(t,x,y), trajectories (1,T,P,2), visibilities (1,T,P).
         Called with imgs= / ref_seg_map= / img_meta= (what BaseModel.forward(test_mode=True, **data) passes for the reference's mask
         datasets) it propagates segmentation masks instead: forward_test_seg."""
+        if self._flow_call(rgbs, query_points, imgs, ref_seg_map):
+            return self.forward_test_flow(imgs, img_meta)
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
         rgbs = self._points_frames(rgbs)
@@ -667,6 +728,14 @@ class HRVanillaTracker(VanillaTracker):
                                       "vanilla_tracker.py:753); a head or stride_sample is not supported there")
         return self.get_feats_hwc(frames, split=False)
 
+    def _window_rows(self, feats, Hf, Wf, radius: int, key: str = "flow"):
+        """_label_feats' f32 rows as they are, and the LocalConfig of single-slot pairs on the keys the label-map path reads
+        (_label_config: `temperature`, `topk`, `with_norm`).  (The points call's cycle check has its own: _cycle_fields.)"""
+        c = self._label_config()
+        return feats, engine.LocalConfig(temperature=c.temperature, topk=c.topk, precede_frames=1, radius=radius, with_first=False,
+                                         with_norm=c.with_norm, pair_precision="f32" if c.pair_precision == "f32" else "auto",
+                                         pair_budget=c.pair_budget)
+
     def _pad_unit(self) -> int:
         """The tracker's own `stride` (vanilla_tracker.py:671-672), not the encoder's output stride; the feature grid is whatever the encoder
         makes of the padded frame."""
@@ -677,6 +746,8 @@ class HRVanillaTracker(VanillaTracker):
                      iteration=None, imgs=None, ref_seg_map=None, img_meta=None, **kw):
         """Points: rgbs / query_points / trajectories / visibilities (below).  Label maps (imgs= / ref_seg_map= / img_meta=, what the
         reference's mask and pose datasets pass): forward_test_seg, on this tracker's local-window affinity."""
+        if self._flow_call(rgbs, query_points, imgs, ref_seg_map):
+            return self.forward_test_flow(imgs, img_meta)
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
         rgbs = self._points_frames(rgbs)

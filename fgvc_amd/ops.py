@@ -726,6 +726,73 @@ def cycle_chase(fields: torch.Tensor, traj: torch.Tensor, start_xy: torch.Tensor
     return back, err
 
 
+FLOW_MODES = {"consistency": 0, "fb_abs": 1}       # FGVC_FLOW_CONSISTENCY, FGVC_FLOW_FB_ABS
+
+
+def flow_from_lists(idx: torch.Tensor, weight: torch.Tensor, Hf: int, Wf: int, R: int, scale: int, size: Tuple[int, int],
+                    pad: Tuple[int, int] = (0, 0), renorm: bool = True, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Single-slot window lists -> dense flow (fgvc_flow_from_lists_f32), every row in one launch.  idx / weight (rows, Hf*Wf, k) as
+    run_local_affinity returns them; `size` = the network size (h, w), `pad` = (left, top) of the padded frame the features were taken
+    from (a feature cell sits on padded pixel cell * scale).  Returns flow (rows, 2, h, w) f32 in pixels, channel 0 = x, and valid
+    (rows, h, w) uint8.  renorm: divide a cell's coordinate sum by its weight sum (taps outside the image dropped) before the cell's own
+    coordinate is subtracted; False keeps get_coord's sum, whose zero-padded taps pull towards the origin.  `out`: (flow, valid) to write
+    into, contiguous and of exactly those shapes and dtypes."""
+    idx, weight = _chk(idx, torch.int32, "idx"), _chk(weight, torch.float32, "weight")
+    assert idx.dim() == 3 and idx.shape == weight.shape and idx.shape[1] == Hf * Wf
+    (h, w), (left, top) = (int(v) for v in size), (int(v) for v in pad)
+    rows = idx.shape[0]
+    if out is None:
+        out = (torch.empty((rows, 2, h, w), device=idx.device, dtype=torch.float32),
+               torch.empty((rows, h, w), device=idx.device, dtype=torch.uint8))
+    flow, valid = out
+    for t, dt, shp in ((flow, torch.float32, (rows, 2, h, w)), (valid, torch.uint8, (rows, h, w))):
+        if not (t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shp and t.device == idx.device):
+            raise ValueError(f"out: contiguous {dt} of shape {shp} on {idx.device}, got {t.dtype} {tuple(t.shape)}")
+    if rows:
+        _lib.call("fgvc_flow_from_lists_f32", _ptr(idx), _ptr(weight), rows, Hf, Wf, int(R), idx.shape[2], int(scale), int(bool(renorm)),
+                  h, w, left, top, _ptr(flow), _ptr(valid), _stream(idx))
+    return flow, valid
+
+
+def _flow_mode(mode: str) -> int:
+    if mode == "range_map":
+        raise NotImplementedError("fgvc_amd: occlusion mode 'range_map' is a scatter-add whose threshold depends on the summation order; "
+                                  "only 'consistency' and 'fb_abs' are built")
+    if mode not in FLOW_MODES:
+        raise ValueError(f"mode={mode!r}: one of {tuple(FLOW_MODES)} ('range_map' is not built)")
+    return FLOW_MODES[mode]
+
+
+def flow_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor, mode: str = "consistency", diff: float = 1.5):
+    """Both directions of the reference's occlusion_estimation in one launch (fgvc_flow_consistency_f32): flows (n, 2, h, w) f32 ->
+    occ_fw, occ_bw (n, 1, h, w) f32, 1 = consistent.  mode 'consistency' | 'fb_abs' (`diff` is read by 'fb_abs' only)."""
+    m = _flow_mode(mode)
+    flow_fw, flow_bw = _chk(flow_fw, torch.float32, "flow_fw"), _chk(flow_bw, torch.float32, "flow_bw")
+    if flow_fw.dim() != 4 or flow_fw.shape[1] != 2 or flow_bw.shape != flow_fw.shape:
+        raise ValueError(f"flow_fw / flow_bw: two (n, 2, h, w) tensors, got {tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}")
+    n, _, h, w = flow_fw.shape
+    occ_fw = torch.empty((n, 1, h, w), device=flow_fw.device, dtype=torch.float32)
+    occ_bw = torch.empty_like(occ_fw)
+    if occ_fw.numel():
+        _lib.call("fgvc_flow_consistency_f32", _ptr(flow_fw), _ptr(flow_bw), n, h, w, m, float(diff), _ptr(occ_fw), _ptr(occ_bw),
+                  _stream(flow_fw))
+    return occ_fw, occ_bw
+
+
+def warp(feat: torch.Tensor, flow: torch.Tensor, align_corners: bool = False, use_mask: bool = True) -> torch.Tensor:
+    """The reference's Warp.forward(feat, flow) with mode='bilinear', padding_mode='zeros' (fgvc_warp_f32): feat (N, C, H, W) f32,
+    flow (N, 2, H, W) f32 -> (N, C, H, W)."""
+    feat, flow = _chk(feat, torch.float32, "feat"), _chk(flow, torch.float32, "flow")
+    if feat.dim() != 4 or flow.dim() != 4 or flow.shape[1] != 2 or flow.shape[0] != feat.shape[0] or flow.shape[2:] != feat.shape[2:]:
+        raise ValueError(f"feat (N, C, H, W) and flow (N, 2, H, W), got {tuple(feat.shape)} and {tuple(flow.shape)}")
+    N, Cn, H, W = feat.shape
+    out = torch.empty_like(feat)
+    if out.numel():
+        _lib.call("fgvc_warp_f32", _ptr(feat), _ptr(flow), N, Cn, H, W, int(bool(align_corners)), int(bool(use_mask)), _ptr(out),
+                  _stream(feat))
+    return out
+
+
 def c2f_refine(coarse_arg: torch.Tensor, qfine: torch.Tensor, kfine: torch.Tensor, vfine: torch.Tensor, H: int,
                W: int, scale: int, Rf: int, topk: int, temperature: float, mode: str = "softmax"):
     """A6 fine stage. coarse_arg int32 (T, HW); qfine (sHsW, Cf); kfine (T, sHsW, Cf); vfine (T, sHsW, P); mode "softmax" or

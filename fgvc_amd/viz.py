@@ -296,3 +296,48 @@ def overlay_masks(frames, ids, palette=None, alpha: int = 128, contour: bool = T
     if ids is None:
         raise ValueError("ids: (T, H, W) uint8, got None")
     return render(frames, ids=ids, palette=palette, alpha=alpha, contour=contour, backend=backend)
+
+
+# ---- dense flow -----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def flow_wheel() -> np.ndarray:
+    """The 55-colour wheel of the Middlebury flow code (Baker et al., "A Database and Evaluation Methodology for Optical Flow"): (55, 3)
+    float64 in [0, 1], the six ramps red-yellow 15, yellow-green 6, green-cyan 4, cyan-blue 11, blue-magenta 13, magenta-red 6."""
+    ramps = ((15, 0, 1, +1), (6, 1, 0, -1), (4, 1, 2, +1), (11, 2, 1, -1), (13, 2, 0, +1), (6, 0, 2, -1))     # (length, full, ramping, direction)
+    wheel, at = np.zeros((55, 3)), 0
+    for n, full, ramp, sign in ramps:
+        t = np.floor(255.0 * np.arange(n) / n) / 255.0
+        wheel[at:at + n, full] = 1.0
+        wheel[at:at + n, ramp] = t if sign > 0 else 1.0 - t
+        at += n
+    return wheel
+
+
+def flow_to_rgb(flow, max_mag: Optional[float] = None) -> np.ndarray:
+    """A flow (2, h, w) or (n, 2, h, w) (channel 0 = x; numpy or a tensor on either device) as colours (h, w, 3) / (n, h, w, 3) uint8:
+    hue from the direction on flow_wheel(), saturation from the magnitude over `max_mag` (None: the largest finite magnitude of the call),
+    white at zero flow, a darkened colour beyond max_mag, black where the flow is not finite.  Host numpy in float64; there is no device
+    backend (the colours are a picture for people, made once per saved frame)."""
+    f = np.asarray(flow.detach().cpu() if hasattr(flow, "detach") else flow, np.float64)
+    if f.ndim not in (3, 4) or f.shape[-3] != 2:
+        raise ValueError(f"flow_to_rgb: a flow of shape (2, h, w) or (n, 2, h, w), got {f.shape}")
+    u, v = f[..., 0, :, :], f[..., 1, :, :]
+    fin = np.isfinite(u) & np.isfinite(v)
+    u, v = np.where(fin, u, 0.0), np.where(fin, v, 0.0)
+    mag = np.hypot(u, v)
+    if max_mag is None:
+        max_mag = float(mag.max()) if mag.size else 0.0
+    if not max_mag > 0:
+        max_mag = 1.0
+    r = mag / max_mag
+    wheel = flow_wheel()
+    a = (np.arctan2(-v, -u) / np.pi + 1.0) / 2.0 * (len(wheel) - 1)
+    k0 = np.floor(a).astype(np.int64)
+    k1 = (k0 + 1) % len(wheel)
+    t = (a - k0)[..., None]
+    col = (1.0 - t) * wheel[k0] + t * wheel[k1]
+    rr = r[..., None]
+    col = np.where(rr <= 1.0, 1.0 - rr * (1.0 - col), col * 0.75)
+    out = np.floor(255.0 * col).astype(np.uint8)
+    out[~fin] = 0
+    return out

@@ -328,6 +328,38 @@ int fgvc_topk_coord_rows_f32(const int32_t* idx, const float* weight, int rows, 
 int fgvc_cycle_chase_f32(const float* fields, const float* traj, const float* start_xy, int n, int P, int H, int W, int scale,
                          float* back_out, float* err_out, void* stream);
 
+/* ---- Dense optical flow.
+ * Read-out: `rows` single-slot window lists (fgvc_local_merge_plan_f32: idx = tap, negative = empty) -> full-resolution flow, one launch.
+ *   idx / weight [rows][H*W][topk] on the H x W feature grid, window radius R; a feature cell sits on padded pixel cell * scale.
+ *   Per cell, over its non-empty taps inside the grid (the selection of fgvc_topk_coord_rows_f32): S = sum w, C = sum w (kx, ky) scale;
+ *   displacement = C / S - (qx, qy) scale with renorm != 0, C - (qx, qy) scale with renorm == 0 (get_coord's own sum: its zero-padded
+ *   taps pull towards the origin); S == 0: displacement 0, the cell is invalid.
+ *   Output pixel (x, y) is padded pixel (X, Y) = (x + pad_left, y + pad_top): cells floor(X / scale) and the one after it, both clamped
+ *   to W - 1 (rows alike to H - 1), interpolated bilinearly with the fractions (X mod scale) / scale.
+ *   flow_out [rows][2][h][w] f32 in pixels, channel 0 = x; valid_out [rows][h][w] uint8 = 1 when all four cells are valid.
+ * FGVC_ERR_INVALID_ARG for a null pointer, rows outside 1 .. 65535, a non-positive size, a negative pad, a feature grid of 2^30 cells or more,
+ * an output plane of 2^30 pixels or more, h above 1048560.  No atomics, no workspace. */
+int fgvc_flow_from_lists_f32(const int32_t* idx, const float* weight, int rows, int H, int W, int R, int topk, int scale, int renorm,
+                             int h, int w, int pad_left, int pad_top, float* flow_out, uint8_t* valid_out, void* stream);
+
+/* Forward-backward check of two dense flows, both directions in one launch: the reference's occlusion_estimation
+ * (occlusion_estimation.py:95-177) as it runs.  flow_fw / flow_bw [n][2][h][w] f32; occ_fw / occ_bw [n][1][h][w] f32, 1 = consistent.
+ *   warped = Warp()(other, own): bilinear, zero padding, align_corners=False on a grid normalised by w - 1 / h - 1, times
+ *   (grid_sample(ones) > 0.9999);  sq = sum_c (own_c + warped_c)^2.
+ *   FGVC_FLOW_CONSISTENCY: sq < sum_c (own_c * 2 + warped_c^2) * 0.01 + 0.5;   FGVC_FLOW_FB_ABS: sqrt(sq) < diff.
+ * f32 arithmetic without contraction.  FGVC_ERR_INVALID_ARG for a null pointer, n outside 1 .. 65535, a non-positive size, a plane of 2^30
+ * pixels or more, an unknown mode.  No atomics, no workspace. */
+#define FGVC_FLOW_CONSISTENCY 0
+#define FGVC_FLOW_FB_ABS 1
+int fgvc_flow_consistency_f32(const float* flow_fw, const float* flow_bw, int n, int h, int w, int mode, float diff, float* occ_fw,
+                              float* occ_bw, void* stream);
+
+/* The reference's Warp.forward (warp.py:55-82) with mode='bilinear', padding_mode='zeros': feat [N][C][H][W], flow [N][2][H][W] ->
+ * out [N][C][H][W] = grid_sample(feat, grid) * mask, grid = (pixel + flow) * 2 / max(size - 1, 1) - 1, mask = (grid_sample(ones, grid) >
+ * 0.9999) with use_mask != 0, else 1.  Same limits as the check above. */
+int fgvc_warp_f32(const float* feat, const float* flow, int N, int C, int H, int W, int align_corners, int use_mask, float* out,
+                  void* stream);
+
 /* ---- The input stage: decoded uint8 RGB frames -> the network's planar f32 input, one launch.  Per frame exactly
  * what datasets.preprocess_tapvid_frames defines (configs/eval/base_data.py:1-7: Resize, RGB2LAB, Normalize): bilinear resize (h0, w0) ->
  * (h, w) on the 0..255 values (align_corners=False, no antialiasing, edge clamped; the identity at the same size), / 255 and clamp to

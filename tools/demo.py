@@ -5,11 +5,14 @@ mediapy: frames come and go through PIL).
     python tools/demo.py FRAMES_DIR --task points --query-points t x y [t x y ...] --out OUT
     python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
+    python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
 
 FRAMES_DIR holds the clip's frames as JPEG / PNG files, taken in name order.  The frames go to the model as they are decoded -- uint8 RGB, on
 the device -- through test_cfg.input = dict(type='rgb8'); the mask task keeps its id maps on the device
 (test_cfg.masks='device', section 15); fgvc_amd.viz.render(backend='hip') paints tracks or masks onto the uint8 frames in one launch
 (section 16) and OUT gets frame_%05d.png and demo.gif.  --host-render paints with the numpy backend instead (the same bytes, for comparison).
+--task flow writes the dense forward flow of every frame pair (test_cfg.flow, section 17) as flow_%05d.flo and, coloured by
+fgvc_amd.viz.flow_to_rgb on the host, flow_%05d.png.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -104,6 +107,30 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     return out[0]
 
 
+def run_flow(a, frames: np.ndarray, dev) -> dict:
+    """-> forward_test_flow's dict of device tensors at the clip's own size (test_cfg.flow)."""
+    flow = dict(type="window", step=a.flow_step, occlusion=a.flow_occlusion)
+    model = build_model(a, dev, input=dict(type="rgb8", size=None, layout="thwc"), flow=flow)
+    with torch.no_grad():
+        return model(test_mode=True, imgs=torch.from_numpy(frames).to(dev)[None, None])
+
+
+def write_flow(out_dir: str, out: dict) -> int:
+    """flow_%05d.flo (Middlebury) and flow_%05d.png (viz.flow_to_rgb, one colour scale for the clip) of the forward flow; with a check,
+    occ_%05d.png (white = consistent)."""
+    from PIL import Image
+    from fgvc_amd import datasets
+    os.makedirs(out_dir, exist_ok=True)
+    fw = out["flow_fw"].cpu().numpy()
+    rgb = viz.flow_to_rgb(fw)
+    for t in range(fw.shape[0]):
+        datasets.write_flo(os.path.join(out_dir, f"flow_{t:05d}.flo"), fw[t])
+        Image.fromarray(rgb[t]).save(os.path.join(out_dir, f"flow_{t:05d}.png"))
+        if "occ_fw" in out:
+            Image.fromarray((out["occ_fw"][t, 0].cpu().numpy() * 255).astype(np.uint8)).save(os.path.join(out_dir, f"occ_{t:05d}.png"))
+    return fw.shape[0]
+
+
 def write(out_dir: str, rendered: np.ndarray, fps: float):
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
@@ -117,7 +144,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("frames", nargs="?", help="a directory of JPEG / PNG frames")
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"), help="a generated clip instead of FRAMES_DIR")
-    ap.add_argument("--task", choices=("points", "vos"), required=True)
+    ap.add_argument("--task", choices=("points", "vos", "flow"), required=True)
+    ap.add_argument("--flow-step", type=int, default=1, help="frame distance of a flow pair (--task flow)")
+    ap.add_argument("--flow-occlusion", choices=("consistency", "fb_abs"), default=None, help="also write the forward check's mask (--task flow)")
     ap.add_argument("--query-points", type=float, nargs="+", default=[], metavar="V", help="t x y [t x y ...], pixels of the clip")
     ap.add_argument("--first-mask", help="PNG of object ids for frame 0 (--task vos)")
     ap.add_argument("--out", required=True)
@@ -147,6 +176,10 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     frames = synthetic_frames(*a.synthetic, seed=a.seed) if a.synthetic else load_frames(a.frames)
     tracks = visibles = ids = points = None
+    if a.task == "flow":
+        n = write_flow(a.out, run_flow(a, frames, dev))
+        print(f"{a.out}: {n} flow fields of {frames.shape[1]} x {frames.shape[2]} as flow_%05d.flo and flow_%05d.png")
+        return
     if a.task == "points":
         tracks, visibles, points = run_points(a, frames, dev)
     else:
