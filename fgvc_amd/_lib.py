@@ -90,6 +90,7 @@ SIGNATURES = {
     "fgvc_flow_from_lists_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fgvc_flow_consistency_f32": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
     "fgvc_warp_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_flow_chain_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fgvc_frames_rgb8_to_lab_f32": (_i, [_p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_jf_tile_rows": (_i, []),
     "fgvc_jf_counts_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),

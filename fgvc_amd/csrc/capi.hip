@@ -42,6 +42,8 @@ int cycle_chase_launch(const float*, const float*, const float*, int, int, int, 
 int flow_from_lists_launch(const int32_t*, const float*, int, int, int, int, int, int, int, int, int, int, int, float*, uint8_t*, hipStream_t);
 int flow_consistency_launch(const float*, const float*, int, int, int, int, float, float*, float*, hipStream_t);
 int warp_launch(const float*, const float*, int, int, int, int, int, int, float*, hipStream_t);
+int flow_chain_launch(const float*, const float*, const uint8_t*, const uint8_t*, const float*, int, int, int, int, int, float*, uint8_t*,
+                      hipStream_t);
 int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
                               hipStream_t);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
@@ -616,6 +618,22 @@ int fgvc_warp_f32(const float* feat, const float* flow, int N, int C, int H, int
   FGVC_REQUIRE(N >= 1 && N <= 65535 && C >= 1 && H > 0 && W > 0 && (long long)H * W < (1ll << 30), FGVC_ERR_INVALID_ARG,
                "fgvc_warp_f32: bad shape (N=%d, C=%d, %d x %d)", N, C, H, W);
   return warp_launch(feat, flow, N, C, H, W, align_corners != 0, use_mask != 0, out, (hipStream_t)stream);
+}
+
+int fgvc_flow_chain_f32(const float* flow_fw, const float* flow_bw, const uint8_t* ok_fw, const uint8_t* ok_bw, const float* query, int T,
+                        int P, int h, int w, int visibility, float* traj_out, uint8_t* vis_out, void* stream) {
+  FGVC_REQUIRE(T >= 1 && T <= 65536 && P >= 0 && h > 0 && w > 0 && (long long)h * w < (1ll << 30), FGVC_ERR_INVALID_ARG,
+               "fgvc_flow_chain_f32: bad shape (T=%d, P=%d, %d x %d)", T, P, h, w);
+  FGVC_REQUIRE(visibility == FGVC_CHAIN_FRAME || visibility == FGVC_CHAIN_CONSISTENCY, FGVC_ERR_INVALID_ARG,
+               "fgvc_flow_chain_f32: visibility=%d", visibility);
+  if (P == 0) return FGVC_OK;
+  FGVC_REQUIRE(query && traj_out && vis_out && (T == 1 || (flow_fw && flow_bw)), FGVC_ERR_INVALID_ARG, "fgvc_flow_chain_f32: null pointer");
+  FGVC_REQUIRE(visibility == FGVC_CHAIN_FRAME || T == 1 || (ok_fw && ok_bw), FGVC_ERR_INVALID_ARG,
+               "fgvc_flow_chain_f32: visibility 'consistency' needs both masks");
+  FGVC_REQUIRE(((uintptr_t)traj_out & 7) == 0, FGVC_ERR_INVALID_ARG, "fgvc_flow_chain_f32: alignment (8 bytes for traj_out)");
+  const bool sticky = visibility == FGVC_CHAIN_CONSISTENCY;
+  return flow_chain_launch(flow_fw, flow_bw, sticky ? ok_fw : nullptr, sticky ? ok_bw : nullptr, query, T, P, h, w, sticky, traj_out, vis_out,
+                           (hipStream_t)stream);
 }
 
 int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,

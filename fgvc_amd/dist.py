@@ -450,6 +450,9 @@ def track_points_sharded(backend, rgbs: torch.Tensor, query_points: torch.Tensor
     if getattr(getattr(backend, "model", None), "test_cfg", None) is not None and backend.model.test_cfg.get("occlusion", None) is not None:
         raise NotImplementedError("fgvc_amd: test_cfg.occlusion (the forward-backward visibility read-out) is not computed on the sharded "
                                   "path; call the model itself (model(test_mode=True, rgbs=..., query_points=...)) or remove the key")
+    if getattr(getattr(backend, "model", None), "test_cfg", None) is not None and backend.model.test_cfg.get("chain", None) is not None:
+        raise NotImplementedError("fgvc_amd: test_cfg.chain (point tracks chained through the dense flow) is not computed on the sharded "
+                                  "path; call the model itself (model(test_mode=True, rgbs=..., query_points=...)) or remove the key")
     if getattr(rgbs, "dtype", None) == torch.uint8:
         raise NotImplementedError("fgvc_amd: the sharded path takes float (Lab-normalised) frames; raw uint8 frames (test_cfg.input) are "
                                   "converted by the model call itself -- or convert them first: ops.frames_to_lab(frames_u8, size)")

@@ -940,3 +940,144 @@ def flow_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, sca
 def flow_occlusion(flow_fw: torch.Tensor, flow_bw: torch.Tensor, mode: str = "consistency", diff: float = 1.5):
     """occ_fw, occ_bw (n, 1, h, w) f32, 1 = consistent: the reference's occlusion_estimation on the two flows (ops.flow_consistency)."""
     return ops.flow_consistency(flow_fw, flow_bw, mode, diff)
+
+
+# ---- point tracks in both time directions by chaining the dense flow (test_cfg.chain, an extension key; DESIGN.md section 18) ----------------
+#
+# The reference's TAP-Vid flow-chaining baseline (RAFT.forward_test, raft.py:247-289): positions are pushed forward through flow_fw, pinned to
+# the query point at the query time, and pulled backward through flow_bw for every frame before it.  chain_points_host is the rule written
+# down in float32 scalars, chain_points the product path (one fgvc_flow_chain_f32 launch).
+
+CHAIN_VISIBILITIES = ("frame", "consistency")
+CHAIN_LIMIT = 2.0 ** 23
+
+
+@dataclass
+class ChainConfig:
+    """test_cfg.chain = dict(type='flow', visibility='frame' | 'consistency'), parsed.  'frame': the reference's rule, a point is visible
+    while it is inside the frame; 'consistency': it also stays invisible past the first hop that starts outside the frame or on a pixel the
+    flow's forward-backward check rejects."""
+    visibility: str = "frame"
+
+
+def parse_chain(spec) -> Optional[ChainConfig]:
+    """None -> None (the option is off).  A mapping with type='flow' -> ChainConfig; any other `type` (or none), an unknown key or an unknown
+    visibility raises ValueError, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.chain: a dict such as dict(type='flow', visibility='frame'), got {type(spec).__name__}")
+    spec = dict(spec)
+    typ = spec.pop("type", None)
+    if typ != "flow":
+        raise ValueError(f"test_cfg.chain: type={typ!r} (only 'flow': chaining the dense flow of test_cfg.flow)")
+    visibility = spec.pop("visibility", "frame")
+    if spec:
+        raise ValueError(f"test_cfg.chain: unknown key(s) {sorted(spec)} (type, visibility)")
+    if visibility not in CHAIN_VISIBILITIES:
+        raise ValueError(f"test_cfg.chain: visibility={visibility!r} (one of {CHAIN_VISIBILITIES})")
+    return ChainConfig(visibility)
+
+
+def check_query_times(times, n_frames: int) -> None:
+    """ValueError unless every query time (a host sequence or tensor) is an integer of [0, n_frames)."""
+    t = torch.as_tensor(times).detach().to("cpu", torch.float64).flatten()
+    bad = ~(torch.isfinite(t) & (t == t.floor()) & (t >= 0) & (t < n_frames))
+    if bool(bad.any()):
+        raise ValueError(f"query_points: query time {float(t[bad][0])} (integers in [0, {n_frames}) are tracked)")
+
+
+def grid_queries(t: int, h: int, w: int, stride: int, offset=None) -> torch.Tensor:
+    """(P, 3) f32 queries (t, x, y) on a regular grid of frame t: x = ox, ox + stride, ... < w and y alike, row-major (y outer).  `offset`
+    = (ox, oy), default (stride // 2, stride // 2).  Dense tracks are the points call with these queries."""
+    t, h, w, stride = int(t), int(h), int(w), int(stride)
+    if stride < 1 or h < 1 or w < 1 or t < 0:
+        raise ValueError(f"grid_queries: t={t}, {h} x {w}, stride={stride}")
+    ox, oy = (stride // 2, stride // 2) if offset is None else (int(offset[0]), int(offset[1]))
+    if not (0 <= ox < w and 0 <= oy < h):
+        raise ValueError(f"grid_queries: offset=({ox}, {oy}) outside the {h} x {w} frame")
+    ys, xs = torch.meshgrid(torch.arange(oy, h, stride, dtype=torch.float32), torch.arange(ox, w, stride, dtype=torch.float32), indexing="ij")
+    return torch.stack([torch.full_like(xs, float(t)), xs, ys], -1).reshape(-1, 3)
+
+
+def chain_points_host(flow_fw, flow_bw, query, ok_fw=None, ok_bw=None, visibility: str = "frame"):
+    """The rule fgvc_flow_chain_f32 is held to, on numpy arrays in float32 scalars.  flow_fw / flow_bw (T-1, 2, h, w), query (P, 3) =
+    (t, x, y), ok_fw / ok_bw (T-1, h, w) for visibility='consistency'.  Returns traj (T, P, 2) float32 and vis (T, P) uint8.
+
+    Per point: traj[tq] = (x, y) as given; for t = tq+1 .. T-1: c = c + S(flow_fw[t-1], c); from the query point again, for t = tq-1 .. 0:
+    c = c + S(flow_bw[t], c).  S is the reference's bilinear_sample2d (samp.py:5-99): taps at the clamped floor and floor + 1, weights from
+    the unclamped ones, ((w00 i00 + w01 i01) + w10 i10) + w11 i11.  A position that is non-finite or at 2^23 or beyond is never turned into
+    an index: that frame and every later one on that side are NaN and invisible (the query frame keeps the query); a query time that is no
+    integer of [0, T) makes every frame of the point NaN."""
+    import numpy as np
+    f32 = np.float32
+    if visibility not in CHAIN_VISIBILITIES:
+        raise ValueError(f"visibility={visibility!r}: one of {CHAIN_VISIBILITIES}")
+    flow_fw, flow_bw = np.asarray(flow_fw, f32), np.asarray(flow_bw, f32)
+    query = np.asarray(query, f32)
+    n, _, h, w = flow_fw.shape
+    assert flow_fw.shape == flow_bw.shape == (n, 2, h, w) and query.ndim == 2 and query.shape[1] == 3
+    sticky = visibility == "consistency"
+    if sticky:
+        if ok_fw is None or ok_bw is None:
+            raise ValueError("visibility='consistency' needs ok_fw and ok_bw, (T-1, h, w)")
+        ok_fw, ok_bw = np.asarray(ok_fw), np.asarray(ok_bw)
+        assert ok_fw.shape == ok_bw.shape == (n, h, w)
+    T, P = n + 1, query.shape[0]
+    traj = np.full((T, P, 2), np.nan, f32)
+    vis = np.zeros((T, P), np.uint8)
+    one, half, wf, hf = f32(1), f32(0.5), f32(w), f32(h)
+
+    def bad(x, y):
+        return not (abs(x) < CHAIN_LIMIT and abs(y) < CHAIN_LIMIT)
+
+    def inside(x, y):
+        return bool(x >= 0 and y >= 0 and x < wf and y < hf)
+
+    def clamp(v, hi):
+        return min(max(int(v), 0), hi)
+
+    def hop(field, ok, x, y):
+        x0f, y0f = np.floor(x), np.floor(y)
+        x1f, y1f = x0f + one, y0f + one
+        xa, xb, ya, yb = clamp(x0f, w - 1), clamp(int(x0f) + 1, w - 1), clamp(y0f, h - 1), clamp(int(y0f) + 1, h - 1)
+        w00, w01, w10, w11 = (x1f - x) * (y1f - y), (x - x0f) * (y1f - y), (x1f - x) * (y - y0f), (x - x0f) * (y - y0f)
+        d = [((w00 * pl[ya, xa] + w01 * pl[ya, xb]) + w10 * pl[yb, xa]) + w11 * pl[yb, xb] for pl in (field[0], field[1])]
+        good = True
+        if sticky:
+            good = inside(x, y) and ok[clamp(np.floor(y + half), h - 1), clamp(np.floor(x + half), w - 1)] != 0
+        return x + d[0], y + d[1], good
+
+    with np.errstate(all="ignore"):
+        for p in range(P):
+            qt, qx, qy = query[p]
+            if not (qt >= 0 and qt < T and np.floor(qt) == qt):
+                continue
+            tq = int(qt)
+            traj[tq, p] = (qx, qy)
+            vis[tq, p] = inside(qx, qy)
+            for frames, fields, oks, at in ((range(tq + 1, T), flow_fw, ok_fw, -1), (range(tq - 1, -1, -1), flow_bw, ok_bw, 0)):
+                x, y, all_good = qx, qy, True
+                for t in frames:
+                    if bad(x, y):
+                        break
+                    x, y, good = hop(fields[t + at], oks[t + at] if sticky else None, x, y)
+                    all_good = all_good and good
+                    if bad(x, y):
+                        break
+                    traj[t, p] = (x, y)
+                    vis[t, p] = inside(x, y) and (all_good or not sticky)
+    return traj, vis
+
+
+def chain_points(flow_fw: torch.Tensor, flow_bw: torch.Tensor, query: torch.Tensor, ok_fw: Optional[torch.Tensor] = None,
+                 ok_bw: Optional[torch.Tensor] = None, visibility: str = "frame") -> Tuple[torch.Tensor, torch.Tensor]:
+    """chain_points_host on the device: traj (T, P, 2) f32 and vis (T, P) uint8 from one fgvc_flow_chain_f32 launch (ops.flow_chain).
+    query (P, 3) = (t, x, y), any float dtype, on any device."""
+    q = query.to(flow_fw.device, torch.float32)
+    return ops.flow_chain(flow_fw, flow_bw, q, ok_fw, ok_bw, visibility)
+
+
+def chain_masks(flow: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """ok_fw, ok_bw (T-1, h, w) uint8 of a forward_test_flow result with its forward-backward check: valid & (occ == 1)."""
+    return tuple(((flow["valid_" + d] != 0) & (flow["occ_" + d][:, 0] == 1)).to(torch.uint8) for d in ("fw", "bw"))

@@ -94,6 +94,8 @@ class VanillaTracker(BaseTracker):
         self.last_cycle_error = None       # (1, T, P) f32 forward-backward errors of the last points call with test_cfg.occlusion set, else None
         self.input_cfg = engine.parse_input(self.test_cfg.get("input", None))      # test_cfg.input (None: float frames only); a bad key is refused here
         self.masks_form = engine.parse_masks(self.test_cfg.get("masks", None))     # test_cfg.masks: 'numpy' (default) | 'device'; the index-map call only
+        self.chain_cfg = engine.parse_chain(self.test_cfg.get("chain", None))      # test_cfg.chain (None: the points call propagates labels, as ever)
+        self.last_flow = None              # forward_test_flow's dict of the last points call with test_cfg.chain set, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -236,9 +238,10 @@ class VanillaTracker(BaseTracker):
         return engine.backward_fields(rows, Hf, Wf, lc, scale, self.cycle_stats), scale
 
     # ---- dense optical flow between frames (test_cfg.flow, an extension key) ---------------------------------------
-    def _flow(self) -> Optional[engine.FlowConfig]:
-        """test_cfg.flow parsed (None: the option is off).  The default window is this tracker's own: neighbor_range // 2."""
-        spec = self.test_cfg.get("flow", None)
+    def _flow(self, spec=None) -> Optional[engine.FlowConfig]:
+        """test_cfg.flow (or `spec` in its place) parsed (None: the option is off).  The default window is this tracker's own:
+        neighbor_range // 2."""
+        spec = self.test_cfg.get("flow", None) if spec is None else spec
         if spec is None:
             return None
         nr = self.test_cfg.get("neighbor_range", self._default_neighbor_range)
@@ -247,12 +250,13 @@ class VanillaTracker(BaseTracker):
         return engine.parse_flow(spec, 0 if nr is None else int(nr) // 2)
 
     @torch.no_grad()
-    def forward_test_flow(self, imgs, img_meta=None):
+    def forward_test_flow(self, imgs, img_meta=None, fc: Optional[engine.FlowConfig] = None):
         """Dense flow between the frames of a clip `step` apart, both time directions.  imgs as the label-map call takes them: float
         (1, 1, 3, T, h, w), or uint8 frames with test_cfg.input.  Returns a dict of CUDA tensors at the network size (h, w): flow_fw[g] takes
         frame g to frame g + step and flow_bw[g] back, (T-step, 2, h, w) f32 in pixels, channel 0 = x; valid_fw / valid_bw (T-step, h, w)
-        uint8; with flow.occlusion set, occ_fw / occ_bw (T-step, 1, h, w) f32, 1 = consistent.  self.flow_stats: what the affinity reported."""
-        fc = self._flow()
+        uint8; with flow.occlusion set, occ_fw / occ_bw (T-step, 1, h, w) f32, 1 = consistent.  self.flow_stats: what the affinity reported.
+        `fc`: a parsed configuration in test_cfg.flow's place (the chained points call's)."""
+        fc = self._flow() if fc is None else fc
         if fc is None:
             raise ValueError(f"{type(self).__name__}.forward_test_flow needs test_cfg.flow = dict(type='window', ...)")
         if self.test_cfg.get("occlusion", None) is not None:
@@ -286,6 +290,40 @@ class VanillaTracker(BaseTracker):
         """forward_test's third call form: imgs= alone (no first-frame labels) with test_cfg.flow set.  Without the key nothing changes."""
         return (self.test_cfg.get("flow", None) is not None and imgs is not None and ref_seg_map is None
                 and rgbs is None and query_points is None)
+
+    # ---- point tracks in both time directions by chaining the flow (test_cfg.chain, an extension key; DESIGN.md section 18) -----------------
+    @torch.no_grad()
+    def forward_test_chain(self, rgbs, query_points, trajectories=None, visibilities=None):
+        """The points call with test_cfg.chain set: the clip's dense flow (forward_test_flow on test_cfg.flow, else dict(type='window')), then
+        every query point chained through it forward and backward in time by one kernel (engine.chain_points: the reference's
+        RAFT.forward_test, raft.py:247-289).  rgbs float (1, T, 3, h, w), or uint8 frames with test_cfg.input; query_points (1, P, 3) =
+        (t, x, y) in pixels of the network size.  Returns the reference's 5-tuple with the points in their given order; traj_pred
+        (1, T, P, 2) is filled for all T frames, vis_pred (1, T, P) by chain.visibility.  The flows stay in self.last_flow."""
+        cc = self.chain_cfg
+        if self.test_cfg.get("occlusion", None) is not None:
+            raise ValueError("fgvc_amd: test_cfg.chain and test_cfg.occlusion are both set; the chained call has its own visibility "
+                             "(chain.visibility = 'frame' | 'consistency') and the cycle check belongs to label propagation -- remove one")
+        spec = self.test_cfg.get("flow", None)
+        fc = self._flow(spec if spec is not None else dict(type="window"))
+        if fc.step != 1:
+            raise ValueError(f"fgvc_amd: test_cfg.chain walks frame by frame; test_cfg.flow has step={fc.step} (set step=1)")
+        if cc.visibility == "consistency" and fc.occlusion is None:
+            fc.occlusion = "consistency"
+        if rgbs.dim() != 5 or rgbs.shape[0] != 1:
+            raise ValueError(f"rgbs: frames of shape (1, T, 3, h, w), or uint8 ones as test_cfg.input lays them out, got {tuple(rgbs.shape)}")
+        if query_points.dim() != 3 or query_points.shape[0] != 1 or query_points.shape[2] != 3:
+            raise ValueError(f"query_points: (1, P, 3) = (t, x, y), got {tuple(query_points.shape)}")
+        engine.check_query_times(query_points[0, :, 0], rgbs.shape[1])
+        # the flow call's layout: float (1, 1, 3, T, h, w) -- a view --, uint8 (1, 1, T, ...)
+        imgs = rgbs.unsqueeze(1) if rgbs.dtype == torch.uint8 else rgbs.transpose(1, 2).unsqueeze(1)
+        self.last_flow = flow = self.forward_test_flow(imgs, fc=fc)
+        ok_fw, ok_bw = engine.chain_masks(flow) if cc.visibility == "consistency" else (None, None)
+        traj, vis = engine.chain_points(flow["flow_fw"], flow["flow_bw"], query_points[0], ok_fw, ok_bw, cc.visibility)
+        traj, vis = traj.unsqueeze(0), vis.unsqueeze(0)
+        if trajectories is not None:
+            traj = traj.to(trajectories.device, trajectories.dtype)
+        vis = vis.to(visibilities.device, visibilities.dtype) if visibilities is not None else vis.to(torch.float32)
+        return trajectories, visibilities, traj, vis, query_points
 
     def _visibility_from_frame0(self, feats, Hf, Wf, w, coords, qp, visibilities, occ):
         """The fourth return element of the un-regrouped call: every point is tracked from frame 0, whatever its query time
@@ -355,6 +393,8 @@ class VanillaTracker(BaseTracker):
             return self.forward_test_flow(imgs, img_meta)
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        if self.chain_cfg is not None:
+            return self.forward_test_chain(rgbs, query_points, trajectories, visibilities)
         rgbs = self._points_frames(rgbs)
         if not rgbs.is_cuda:
             raise RuntimeError("fgvc_amd.VanillaTracker runs on the GPU only (no CPU fallback)")
@@ -750,6 +790,8 @@ class HRVanillaTracker(VanillaTracker):
             return self.forward_test_flow(imgs, img_meta)
         if self._label_call(rgbs, query_points, imgs, ref_seg_map, img_meta):
             return self.forward_test_seg(imgs, ref_seg_map, img_meta, save_image=save_image, save_path=save_path, iteration=iteration)
+        if self.chain_cfg is not None:
+            return self.forward_test_chain(rgbs, query_points, trajectories, visibilities)
         rgbs = self._points_frames(rgbs)
         if not self.test_cfg.get("with_first", False):
             return self.forward_test_main(rgbs, query_points, trajectories, visibilities)

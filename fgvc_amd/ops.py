@@ -793,6 +793,49 @@ def warp(feat: torch.Tensor, flow: torch.Tensor, align_corners: bool = False, us
     return out
 
 
+CHAIN_VISIBILITIES = {"frame": 0, "consistency": 1}       # FGVC_CHAIN_FRAME, FGVC_CHAIN_CONSISTENCY
+
+
+def flow_chain(flow_fw: torch.Tensor, flow_bw: torch.Tensor, query: torch.Tensor, ok_fw: Optional[torch.Tensor] = None,
+               ok_bw: Optional[torch.Tensor] = None, visibility: str = "frame", out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Query points tracked through a clip in both time directions by chaining its flow (fgvc_flow_chain_f32), one launch: the reference's
+    RAFT.forward_test chain (raft.py:247-289) bit for bit.  flow_fw / flow_bw (T-1, 2, h, w) f32 as forward_test_flow returns them at
+    step = 1; query (P, 3) f32 = (t, x, y) (any strides: a contiguous copy is chained); ok_fw / ok_bw (T-1, h, w) uint8, needed by
+    visibility='consistency' (a frame is visible while it is inside the frame and every hop from the query frame started inside it on a
+    set mask pixel) and not read by 'frame' (inside the frame, per frame).  Returns traj (T, P, 2) f32 and vis (T, P) uint8.  A position
+    that is non-finite or beyond 2^23 ends its side of the track in NaN, invisible; so does a query time that is no integer of [0, T).
+    T = 1 returns the query points, P = 0 empty tensors without a launch.  `out`: (traj, vis) to write into, contiguous and of exactly
+    those shapes and dtypes."""
+    if visibility not in CHAIN_VISIBILITIES:
+        raise ValueError(f"visibility={visibility!r}: one of {tuple(CHAIN_VISIBILITIES)}")
+    flow_fw, flow_bw = _chk(flow_fw, torch.float32, "flow_fw"), _chk(flow_bw, torch.float32, "flow_bw")
+    query = _chk(query, torch.float32, "query")
+    if flow_fw.dim() != 4 or flow_fw.shape[1] != 2 or flow_bw.shape != flow_fw.shape:
+        raise ValueError(f"flow_fw / flow_bw: two (T-1, 2, h, w) tensors, got {tuple(flow_fw.shape)} and {tuple(flow_bw.shape)}")
+    if query.dim() != 2 or query.shape[1] != 3:
+        raise ValueError(f"query: (P, 3) = (t, x, y), got {tuple(query.shape)}")
+    n, _, h, w = flow_fw.shape
+    T, P, dev = n + 1, query.shape[0], flow_fw.device
+    if visibility == "consistency":
+        if ok_fw is None or ok_bw is None:
+            raise ValueError("visibility='consistency' needs ok_fw and ok_bw, (T-1, h, w) uint8")
+        ok_fw, ok_bw = _chk(ok_fw, torch.uint8, "ok_fw"), _chk(ok_bw, torch.uint8, "ok_bw")
+        if tuple(ok_fw.shape) != (n, h, w) or tuple(ok_bw.shape) != (n, h, w):
+            raise ValueError(f"ok_fw / ok_bw: two ({n}, {h}, {w}) tensors, got {tuple(ok_fw.shape)} and {tuple(ok_bw.shape)}")
+    else:
+        ok_fw = ok_bw = None
+    if out is None:
+        out = (torch.empty((T, P, 2), device=dev, dtype=torch.float32), torch.empty((T, P), device=dev, dtype=torch.uint8))
+    traj, vis = out
+    for t, dt, shp in ((traj, torch.float32, (T, P, 2)), (vis, torch.uint8, (T, P))):
+        if not (t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shp and t.device == dev):
+            raise ValueError(f"out: contiguous {dt} of shape {shp} on {dev}, got {t.dtype} {tuple(t.shape)}")
+    if P:
+        _lib.call("fgvc_flow_chain_f32", _ptr(flow_fw if n else None), _ptr(flow_bw if n else None), _ptr(ok_fw if n else None),
+                  _ptr(ok_bw if n else None), _ptr(query), T, P, h, w, CHAIN_VISIBILITIES[visibility], _ptr(traj), _ptr(vis), _stream(query))
+    return traj, vis
+
+
 def c2f_refine(coarse_arg: torch.Tensor, qfine: torch.Tensor, kfine: torch.Tensor, vfine: torch.Tensor, H: int,
                W: int, scale: int, Rf: int, topk: int, temperature: float, mode: str = "softmax"):
     """A6 fine stage. coarse_arg int32 (T, HW); qfine (sHsW, Cf); kfine (T, sHsW, Cf); vfine (T, sHsW, P); mode "softmax" or

@@ -360,6 +360,28 @@ int fgvc_flow_consistency_f32(const float* flow_fw, const float* flow_bw, int n,
 int fgvc_warp_f32(const float* feat, const float* flow, int N, int C, int H, int W, int align_corners, int use_mask, float* out,
                   void* stream);
 
+/* ---- Point tracks in both time directions by chaining the dense flow: the reference's TAP-Vid flow-chaining
+ * baseline (RAFT.forward_test, raft.py:247-289, on bilinear_sample2d, samp.py:5-99), whole clip, every point, both directions, one launch.
+ *   flow_fw / flow_bw [T-1][2][h][w] f32, channel 0 = x: flow_fw[g] takes frame g to g + 1, flow_bw[g] frame g + 1 to g (null with T = 1);
+ *   query [P][3] f32 = (t, x, y); ok_fw / ok_bw [T-1][h][w] uint8, read by FGVC_CHAIN_CONSISTENCY only.
+ * Per point: traj[tq] = (x, y) as given; for t = tq + 1 .. T - 1: c = c + S(flow_fw[t - 1], c); from the query point again, for
+ * t = tq - 1 .. 0: c = c + S(flow_bw[t], c).  S = bilinear_sample2d in f32 without contraction: x0f = floorf(x), x1f = x0f + 1 (y alike);
+ * taps at clamp(x0, 0, w - 1), clamp(x0 + 1, 0, w - 1) (y alike); weights (x1f-x)(y1f-y), (x-x0f)(y1f-y), (x1f-x)(y-y0f), (x-x0f)(y-y0f);
+ * value ((w00 i00 + w01 i01) + w10 i10) + w11 i11, every product rounded.
+ *   FGVC_CHAIN_FRAME (raft.py:285-288): vis = x >= 0 && y >= 0 && x < w && y < h, per frame.
+ *   FGVC_CHAIN_CONSISTENCY: a hop is good when its source position is inside the frame and ok[clamp(floorf(y + 0.5f))][clamp(floorf(x + 0.5f))]
+ *   of that hop's field is non-zero; a frame is visible when it is inside the frame and every hop between the query frame and it was good.
+ * Fail closed: a position that is non-finite or has |x| or |y| >= 2^23 is never turned into an index -- that frame and every later one on
+ * that side are NaN with vis = 0 (the query frame keeps the query as given); a query time that is no integer of [0, T) makes every frame of
+ * its point NaN with vis = 0.
+ *   traj_out [T][P][2] f32 (8-byte aligned), vis_out [T][P] uint8.  P = 0: nothing is launched.
+ * FGVC_ERR_INVALID_ARG for T outside 1 .. 65536, a negative P, a non-positive size, a plane of 2^30 pixels or more, an unknown visibility,
+ * a null pointer that is read, a misaligned traj_out.  No atomics, no workspace. */
+#define FGVC_CHAIN_FRAME 0
+#define FGVC_CHAIN_CONSISTENCY 1
+int fgvc_flow_chain_f32(const float* flow_fw, const float* flow_bw, const uint8_t* ok_fw, const uint8_t* ok_bw, const float* query, int T,
+                        int P, int h, int w, int visibility, float* traj_out, uint8_t* vis_out, void* stream);
+
 /* ---- The input stage: decoded uint8 RGB frames -> the network's planar f32 input, one launch.  Per frame exactly
  * what datasets.preprocess_tapvid_frames defines (configs/eval/base_data.py:1-7: Resize, RGB2LAB, Normalize): bilinear resize (h0, w0) ->
  * (h, w) on the 0..255 values (align_corners=False, no antialiasing, edge clamped; the identity at the same size), / 255 and clamp to

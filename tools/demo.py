@@ -5,6 +5,7 @@ mediapy: frames come and go through PIL).
     python tools/demo.py FRAMES_DIR --task points --query-points t x y [t x y ...] --out OUT
     python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
+    python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
 
 FRAMES_DIR holds the clip's frames as JPEG / PNG files, taken in name order.  The frames go to the model as they are decoded -- uint8 RGB, on
@@ -71,7 +72,8 @@ def build_model(a, dev, **extra):
 
 
 def run_points(a, frames: np.ndarray, dev):
-    """-> tracks (P, T, 2) float64 in the clip's pixel frame, visibles (P, T) bool (from the query time on), query points (P, 3) as returned."""
+    """-> tracks (P, T, 2) float64 in the clip's pixel frame, visibles (P, T) bool (from the query time on; with --chain the chained call's own
+    visibility, on both sides of it), query points (P, 3) as returned."""
     T, H, W = frames.shape[:3]
     q = np.asarray(a.query_points, np.float64)
     if q.size == 0 or q.size % 3:
@@ -81,7 +83,8 @@ def run_points(a, frames: np.ndarray, dev):
         raise ValueError(f"--query-points: a query time outside 0 .. {T - 1}")
     size = tuple(a.size) if a.size else (H, W)
     q[:, 1:] = viz.scale_tracks(q[:, 1:], (H, W), size)
-    model = build_model(a, dev, input=dict(type="rgb8", size=tuple(a.size) if a.size else None, layout="thwc"))
+    chain = dict(chain=dict(type="flow", visibility=a.chain_visibility)) if a.chain else {}
+    model = build_model(a, dev, input=dict(type="rgb8", size=tuple(a.size) if a.size else None, layout="thwc"), **chain)
     qp = torch.from_numpy(q).float()[None].to(dev)
     P = q.shape[0]
     with torch.no_grad():
@@ -89,7 +92,10 @@ def run_points(a, frames: np.ndarray, dev):
                     trajectories=torch.zeros(1, T, P, 2, device=dev), visibilities=torch.ones(1, T, P, device=dev))
     traj, qp_out = out[2][0], out[4][0]                                  # (T, P, 2) at the model's size; the points in the order of its columns
     tracks = viz.scale_tracks(traj.permute(1, 0, 2), size, (H, W))
-    visibles = np.arange(T)[None, :] >= qp_out[:, :1].cpu().numpy()
+    if a.chain:                                                          # tracked on both sides of the query time, with a predicted visibility
+        visibles = out[3][0].t().cpu().numpy() != 0
+    else:
+        visibles = np.arange(T)[None, :] >= qp_out[:, :1].cpu().numpy()
     return tracks, visibles, qp_out.cpu().numpy()
 
 
@@ -147,6 +153,9 @@ def main(argv=None):
     ap.add_argument("--task", choices=("points", "vos", "flow"), required=True)
     ap.add_argument("--flow-step", type=int, default=1, help="frame distance of a flow pair (--task flow)")
     ap.add_argument("--flow-occlusion", choices=("consistency", "fb_abs"), default=None, help="also write the forward check's mask (--task flow)")
+    ap.add_argument("--chain", action="store_true",
+                    help="--task points: track by chaining the dense flow, forward and backward in time (test_cfg.chain, DESIGN.md section 18)")
+    ap.add_argument("--chain-visibility", choices=("frame", "consistency"), default="frame", help="with --chain: chain.visibility")
     ap.add_argument("--query-points", type=float, nargs="+", default=[], metavar="V", help="t x y [t x y ...], pixels of the clip")
     ap.add_argument("--first-mask", help="PNG of object ids for frame 0 (--task vos)")
     ap.add_argument("--out", required=True)

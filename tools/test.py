@@ -5,6 +5,7 @@
     python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
     python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
     python tools/test.py CONFIG --task davis --occlusion [--cycle-thresh 1.0] [--occluder]   # predicted visibility: DESIGN.md section 13
+    python tools/test.py CONFIG --task davis --chain [--chain-visibility frame|consistency] [--query-mode strided]   # flow chaining: section 18
     python tools/test.py CONFIG --task davis|vos|jhmdb|badja --raw-frames     # uint8 RGB frames into the model (test_cfg.input): section 14
     python tools/test.py CONFIG --task vos --data-root DIR --gpu-metrics     # masks stay on the device, J&F from fgvc_jf_counts_u8: section 15
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
@@ -65,6 +66,11 @@ def main():
                          "average_jaccard and occlusion_accuracy then score a prediction instead of all-occluded zeros")
     ap.add_argument("--cycle-thresh", type=float, default=None, metavar="CELLS",
                     help="with --occlusion: a point is visible while its cycle error is <= this many feature cells (default 1.0)")
+    ap.add_argument("--chain", action="store_true",
+                    help="track by chaining the dense flow, forward and backward in time (test_cfg.chain = dict(type='flow', ...), DESIGN.md "
+                         "section 18): the frames before a query time, which --query-mode strided scores, are tracked too")
+    ap.add_argument("--chain-visibility", choices=("frame", "consistency"), default=None,
+                    help="with --chain: 'frame' (default, the reference's rule: visible while inside the frame) or 'consistency'")
     ap.add_argument("--occluder", action="store_true", help="synthetic clips: paste a static rectangle over the later frames (SyntheticTapVid(occluder=True))")
     ap.add_argument("--raw-frames", action="store_true",
                     help="hand the decoded uint8 frames to the model (datasets' raw=True) and set test_cfg.input = dict(type='rgb8', size=...): "
@@ -123,6 +129,16 @@ def main():
         if distributed:
             raise SystemExit("--occlusion runs on one GPU (--launcher none)")
         test_cfg = dict(test_cfg, occlusion=dict(type="cycle", cycle_thresh=1.0 if a.cycle_thresh is None else a.cycle_thresh, radius=None))
+    if a.chain_visibility is not None and not a.chain:
+        raise SystemExit("--chain-visibility goes with --chain")
+    if a.chain:
+        if dataset is None:
+            raise SystemExit("--chain is a form of the points call: TAP-Vid tasks only (not vos / jhmdb / badja)")
+        if distributed:
+            raise SystemExit("--chain runs on one GPU (--launcher none)")
+        if a.occlusion:
+            raise SystemExit("--chain has its own visibility (--chain-visibility); --occlusion belongs to label propagation")
+        test_cfg = dict(test_cfg, chain=dict(type="flow", visibility=a.chain_visibility or "frame"))
     if a.raw_frames:
         if distributed:
             raise SystemExit("--raw-frames runs on one GPU (--launcher none)")
