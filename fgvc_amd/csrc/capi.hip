@@ -46,6 +46,10 @@ int flow_chain_launch(const float*, const float*, const uint8_t*, const uint8_t*
                       hipStream_t);
 int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
                               hipStream_t);
+int frames_yuv420_to_lab_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
+                                long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
+int frames_yuv420_to_rgb8_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
+                                 long long, const float*, int, uint8_t*, hipStream_t);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
 int render_frames_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
@@ -650,6 +654,42 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
                "fgvc_frames_rgb8_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels)");
   return frames_rgb8_to_lab_launch(frames, T, h0, w0, stride_t, stride_y, stride_x, stride_c, h, w, pad_left, pad_right, pad_top, pad_bottom,
                                    out, (hipStream_t)stream);
+}
+
+int fgvc_frames_yuv420_to_lab_f32(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
+                                  int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy,
+                                  float crv, float cgu, float cgv, float cbu, int siting, int h, int w, int pad_left, int pad_right,
+                                  int pad_top, int pad_bottom, float* out, void* stream) {
+  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_lab_f32: null pointer");
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_lab_f32: non-positive size (T=%d, %d x %d -> %d x %d)", T, h0, w0, h, w);
+  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_lab_f32: negative pad (%d, %d, %d, %d)", pad_left, pad_right, pad_top, pad_bottom);
+  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_lab_f32: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", siting);
+  const long long hp = (long long)pad_top + h + pad_bottom, wp = (long long)pad_left + w + pad_right;
+  // the grid of fgvc_frames_rgb8_to_lab_f32; a source column's position in quarter chroma samples, 2 x, stays inside an int
+  FGVC_REQUIRE(T <= 65535 && hp <= 4 * 65535ll && wp < (1ll << 30) && hp * wp < (1ll << 31) && h0 < (1 << 30) && w0 < (1 << 30),
+               FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels, "
+               "source sides < 2^30)");
+  const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
+  return frames_yuv420_to_lab_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, h, w,
+                                     pad_left, pad_right, pad_top, pad_bottom, out, (hipStream_t)stream);
+}
+
+int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
+                               int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy, float crv,
+                               float cgu, float cgv, float cbu, int siting, uint8_t* out, void* stream) {
+  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_rgb8: null pointer");
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_rgb8: non-positive size (T=%d, %d x %d)", T, h0, w0);
+  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_rgb8: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", siting);
+  FGVC_REQUIRE(T <= 65535 && h0 <= 4 * 65535ll && w0 < (1 << 30) && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuv420_to_rgb8: shape beyond the launch grid (T <= 65535, rows <= 262140, frame < 2^31 pixels)");
+  const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
+  return frames_yuv420_to_rgb8_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, out,
+                                      (hipStream_t)stream);
 }
 
 int fgvc_jf_tile_rows(void) { return jf_tile_rows(); }

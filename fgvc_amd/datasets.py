@@ -666,3 +666,137 @@ def read_flo(path) -> np.ndarray:
     if data.size != 2 * h * w:
         raise ValueError(f"{path}: {data.size} values for a {h} x {w} flow")
     return np.ascontiguousarray(data.reshape(h, w, 2).transpose(2, 0, 1)).astype(np.float32)
+
+
+# ---- 8-bit YUV 4:2:0 video: the input contract as torch ops, and Y4M files -----------------------------------------
+def _chroma_taps(n_luma: int, n: int, back: bool, device):
+    """Chroma samples around every luma index of one axis: s = p / 2 - 0.25 (`back`) or p / 2, clamped to [0, n - 1] -> i0, i1, weight of i1."""
+    p = torch.arange(n_luma, device=device, dtype=torch.float32)
+    s = (p / 2 - (0.25 if back else 0.0)).clamp(0, n - 1)
+    i0 = s.floor()
+    return i0.long(), (i0.long() + 1).clamp(max=n - 1), s - i0
+
+
+def yuv420_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, siting: str = "left") -> torch.Tensor:
+    """One chroma plane (T, ch, cw) uint8 -> its value at every luma pixel (T, h0, w0) f32: bilinear, edge clamped, vertically between the
+    luma rows, horizontally on the even luma columns ('left': MPEG-2, H.264, HEVC) or between them ('center': JPEG, MPEG-1).  Exact: quarter
+    weights on byte samples."""
+    if siting not in ("left", "center"):
+        raise ValueError(f"siting={siting!r}: 'left' or 'center'")
+    c = c.to(torch.float32)
+    y0, y1, ly = _chroma_taps(h0, c.shape[1], True, c.device)
+    x0, x1, lx = _chroma_taps(w0, c.shape[2], siting == "center", c.device)
+    r0, r1 = c[:, y0], c[:, y1]
+    top = (1 - lx) * r0[:, :, x0] + lx * r0[:, :, x1]
+    bot = (1 - lx) * r1[:, :, x0] + lx * r1[:, :, x1]
+    return (1 - ly)[:, None] * top + ly[:, None] * bot
+
+
+def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                  siting: str = "left") -> torch.Tensor:
+    """Planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> R'G'B' (T, 3, h0, w0) f32 on the 0..255 scale, neither clamped
+    nor rounded: chroma at the luma pixel, then yy = cy (Y - y_off), R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with
+    ops.yuv_coefficients rounded to f32 -- one rounded f32 operation after another, the order the kernels keep.  CPU or GPU tensors."""
+    from .ops import yuv_coefficients
+    y_off, cy, crv, cgu, cgv, cbu = (float(np.float32(c)) for c in yuv_coefficients(matrix, range))
+    T, h0, w0 = y.shape
+    want = (T, (h0 + 1) // 2, (w0 + 1) // 2)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)}, got {tuple(u.shape)} and {tuple(v.shape)}")
+    yy = cy * (y.to(torch.float32) - y_off)
+    cb = yuv420_chroma_at_luma(u, h0, w0, siting) - 128.0
+    cr = yuv420_chroma_at_luma(v, h0, w0, siting) - 128.0
+    return torch.stack([yy + crv * cr, (yy + cgu * cb) + cgv * cr, yy + cbu * cb], 1)
+
+
+def yuv420_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                   siting: str = "left") -> torch.Tensor:
+    """-> (T, h0, w0, 3) uint8: yuv420_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_frames_to_rgb8 computes)."""
+    rgb = yuv420_to_rgb(y, u, v, matrix, range, siting)
+    return rgb.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def preprocess_yuv420_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size=None, matrix: str = "bt601", range: str = "limited",
+                             siting: str = "left") -> torch.Tensor:
+    """8-bit YUV 4:2:0 planes -> (1, T, 3, h, w) float32 network input: yuv420_to_rgb, then preprocess_tapvid_frames' steps on the unclamped
+    R'G'B' (bilinear resize to `size`, None = the frames' own; / 255 and clamp; RGB -> Lab; (x - [50, 0, 0]) / [50, 127, 127]).  The contract
+    ops.yuv_frames_to_lab is held to."""
+    x = yuv420_to_rgb(y, u, v, matrix, range, siting)
+    if size is not None and tuple(x.shape[-2:]) != tuple(size):
+        x = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
+    lab = rgb_to_lab((x / 255.0).clamp(0, 1))
+    mean = torch.tensor([50.0, 0.0, 0.0], device=lab.device).view(1, 3, 1, 1)
+    std = torch.tensor([50.0, 127.0, 127.0], device=lab.device).view(1, 3, 1, 1)
+    return ((lab - mean) / std).unsqueeze(0)
+
+
+Y4M_MAGIC = b"YUV4MPEG2"
+_Y4M_SITING = {"420jpeg": "center", "420mpeg2": "left", "420": "left"}
+
+
+def read_y4m(path, max_frames=None):
+    """A YUV4MPEG2 file of progressive 8-bit 4:2:0 frames -> (frames (T, 3 h / 2, w) uint8 tensor, packed I420 as the file holds them; info =
+    dict(width, height, fps=(num, den), siting, range)).  C420jpeg and no C tag: siting 'center'; C420mpeg2 and C420: 'left'.
+    XCOLORRANGE=FULL | LIMITED: range 'full' | 'limited', absent 'limited'.  ValueError that names the tag or the fact for any other chroma
+    tag, interlaced material (It / Ib / Im), an odd size and a truncated frame.  `max_frames`: stop after that many."""
+    with open(path, "rb") as fh:
+        head = fh.readline(4096)
+        tags = head.rstrip(b"\n").split(b" ")
+        if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
+            raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
+        w = h = None
+        fps, chroma, rng = (0, 0), "420jpeg", "limited"
+        for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
+            k, val = tag[0], tag[1:]
+            if k == "W":
+                w = int(val)
+            elif k == "H":
+                h = int(val)
+            elif k == "F":
+                num, _, den = val.partition(":")
+                fps = (int(num), int(den or 1))
+            elif k == "I" and val not in ("p", "?"):
+                raise ValueError(f"{path}: interlaced material (I{val}) is not supported; deinterlace it first")
+            elif k == "C":
+                chroma = val
+            elif k == "X" and val.upper().startswith("COLORRANGE="):
+                rng = val[11:].lower()
+                if rng not in ("full", "limited"):
+                    raise ValueError(f"{path}: XCOLORRANGE={val[11:]} (FULL or LIMITED)")
+        if chroma not in _Y4M_SITING:
+            raise ValueError(f"{path}: chroma tag C{chroma} is not supported (8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420)")
+        if w is None or h is None or w < 1 or h < 1:
+            raise ValueError(f"{path}: the header gives no frame size (W, H)")
+        if w % 2 or h % 2:
+            raise ValueError(f"{path}: odd size {w} x {h}; a 4:2:0 frame with an odd side has no packed form")
+        n = w * h * 3 // 2
+        frames = []
+        while max_frames is None or len(frames) < max_frames:
+            line = fh.readline(4096)
+            if not line:
+                break
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise ValueError(f"{path}: frame {len(frames)}: expected a FRAME header")
+            data = fh.read(n)
+            if len(data) != n:
+                raise ValueError(f"{path}: frame {len(frames)} is truncated ({len(data)} of {n} bytes)")
+            frames.append(np.frombuffer(data, np.uint8))
+    arr = np.stack(frames).reshape(len(frames), h * 3 // 2, w) if frames else np.zeros((0, h * 3 // 2, w), np.uint8)
+    return torch.from_numpy(arr.copy()), dict(width=w, height=h, fps=fps, siting=_Y4M_SITING[chroma], range=rng)
+
+
+def write_y4m(path, frames, fps=(30, 1), siting: str = "left", range: str = "limited") -> None:
+    """Packed I420 frames (T, 3 h / 2, w) uint8 (tensor or array) -> a YUV4MPEG2 file: progressive, square pixels, C420mpeg2 ('left') or
+    C420jpeg ('center'), XCOLORRANGE=LIMITED | FULL."""
+    f = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if f.ndim != 3 or f.dtype != np.uint8 or f.shape[1] % 3 or (f.shape[1] // 3 * 2) % 2 or f.shape[2] % 2:
+        raise ValueError(f"write_y4m: packed I420 frames (T, 3 h / 2, w) uint8 with h and w even, got {f.dtype} {f.shape}")
+    if siting not in ("left", "center") or range not in ("limited", "full"):
+        raise ValueError(f"write_y4m: siting={siting!r} ('left' | 'center'), range={range!r} ('limited' | 'full')")
+    h, w = f.shape[1] // 3 * 2, f.shape[2]
+    chroma = "420mpeg2" if siting == "left" else "420jpeg"
+    with open(path, "wb") as fh:
+        fh.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{chroma} XCOLORRANGE={range.upper()}\n".encode("ascii"))
+        for frame in f:
+            fh.write(b"FRAME\n")
+            fh.write(np.ascontiguousarray(frame).tobytes())

@@ -747,34 +747,65 @@ def parse_occlusion(spec, default_radius: int) -> Optional[OcclusionConfig]:
 
 @dataclass
 class InputConfig:
-    """test_cfg.input = dict(type='rgb8', size=(h, w) | None, layout='thwc' | 'tchw'), parsed (an extension key): the
-    trackers then take uint8 RGB frames wherever they take float ones and convert them with ops.frames_to_lab.  `size`: the network size
-    the frames are resized to (None: their own); `layout`: where the frame tensor keeps its channels."""
+    """test_cfg.input, parsed (an extension key, DESIGN.md sections 14 and 19): the trackers then take uint8 frames wherever they take float
+    ones.  dict(type='rgb8', size=(h, w) | None, layout='thwc' | 'tchw'): RGB bytes, converted with ops.frames_to_lab.
+    dict(type='nv12' | 'i420', size=, matrix='bt601' | 'bt709', range='limited' | 'full', siting='left' | 'center'): packed 8-bit YUV 4:2:0
+    frames (T, 3 h0 / 2, w0), converted with ops.yuv_frames_to_lab.  `size`: the network size the frames are resized to (None: their own);
+    `layout`: where an RGB frame tensor keeps its channels."""
     size: Optional[Tuple[int, int]] = None
     layout: str = "thwc"
+    type: str = "rgb8"
+    matrix: str = "bt601"
+    range: str = "limited"
+    siting: str = "left"
+
+    @property
+    def yuv(self) -> bool:
+        return self.type != "rgb8"
+
+
+INPUT_TYPES = ("rgb8",) + ops.YUV_FORMATS
 
 
 def parse_input(spec) -> Optional[InputConfig]:
-    """None -> None (the option is off: float frames only).  A mapping with type='rgb8' -> InputConfig; any other `type` (or none), an
-    unknown `layout` or key, or a size that is not two positive integers raises ValueError, a non-mapping TypeError."""
+    """None -> None (the option is off: float frames only).  A mapping with type='rgb8' | 'nv12' | 'i420' -> InputConfig; any other `type`
+    (or none), a key its type does not have (`layout` with a YUV type; `matrix`, `range`, `siting` with 'rgb8'), an unknown value, or a size
+    that is not two positive integers raises ValueError, a non-mapping TypeError."""
     if spec is None:
         return None
     if not hasattr(spec, "keys"):
         raise TypeError(f"test_cfg.input: a dict such as dict(type='rgb8', size=(256, 256), layout='thwc'), got {type(spec).__name__}")
     spec = dict(spec)
     typ = spec.pop("type", None)
-    if typ != "rgb8":
-        raise ValueError(f"test_cfg.input: type={typ!r} (only 'rgb8': uint8 RGB frames)")
-    size, layout = spec.pop("size", None), spec.pop("layout", "thwc")
-    if spec:
-        raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, layout)")
-    if layout not in ops.INPUT_LAYOUTS:
-        raise ValueError(f"test_cfg.input: layout={layout!r} (one of {ops.INPUT_LAYOUTS})")
+    if typ not in INPUT_TYPES:
+        raise ValueError(f"test_cfg.input: type={typ!r} (one of {INPUT_TYPES}: uint8 RGB frames, packed 8-bit YUV 4:2:0 frames)")
+    size = spec.pop("size", None)
+    if typ == "rgb8":
+        layout = spec.pop("layout", "thwc")
+        if spec:
+            raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, layout)")
+        if layout not in ops.INPUT_LAYOUTS:
+            raise ValueError(f"test_cfg.input: layout={layout!r} (one of {ops.INPUT_LAYOUTS})")
+        ic = InputConfig(None, layout)
+    else:
+        matrix, rng, siting = spec.pop("matrix", "bt601"), spec.pop("range", "limited"), spec.pop("siting", "left")
+        if "layout" in spec:
+            raise ValueError(f"test_cfg.input: layout= belongs to type='rgb8'; {typ!r} frames are packed (T, 3 h0 / 2, w0)")
+        if spec:
+            raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, matrix, range, siting)")
+        if matrix not in ops.YUV_MATRICES:
+            raise ValueError(f"test_cfg.input: matrix={matrix!r} (one of {tuple(ops.YUV_MATRICES)})")
+        if rng not in ops.YUV_RANGES:
+            raise ValueError(f"test_cfg.input: range={rng!r} (one of {tuple(ops.YUV_RANGES)})")
+        if siting not in ops.YUV_SITINGS:
+            raise ValueError(f"test_cfg.input: siting={siting!r} (one of {ops.YUV_SITINGS})")
+        ic = InputConfig(None, "thwc", typ, matrix, rng, siting)
     if size is not None:
         size = tuple(int(v) for v in size)
         if len(size) != 2 or min(size) < 1:
             raise ValueError(f"test_cfg.input: size={size} (two positive integers (h, w), or None for the frames' own size)")
-    return InputConfig(size, layout)
+    ic.size = size
+    return ic
 
 
 MASK_FORMS = ("numpy", "device")

@@ -309,7 +309,9 @@ class VanillaTracker(BaseTracker):
             raise ValueError(f"fgvc_amd: test_cfg.chain walks frame by frame; test_cfg.flow has step={fc.step} (set step=1)")
         if cc.visibility == "consistency" and fc.occlusion is None:
             fc.occlusion = "consistency"
-        if rgbs.dim() != 5 or rgbs.shape[0] != 1:
+        # packed YUV frames are (1, T, 3 h0 / 2, w0); without the key, uint8 frames of either form go on to the flow call's TypeError
+        packed = rgbs.dtype == torch.uint8 and (self.input_cfg is None or self.input_cfg.yuv) and rgbs.dim() == 4
+        if (not packed and rgbs.dim() != 5) or rgbs.shape[0] != 1:
             raise ValueError(f"rgbs: frames of shape (1, T, 3, h, w), or uint8 ones as test_cfg.input lays them out, got {tuple(rgbs.shape)}")
         if query_points.dim() != 3 or query_points.shape[0] != 1 or query_points.shape[2] != 3:
             raise ValueError(f"query_points: (1, P, 3) = (t, x, y), got {tuple(query_points.shape)}")
@@ -362,9 +364,23 @@ class VanillaTracker(BaseTracker):
         ic = self._raw_input(rgbs, "rgbs")
         if ic is None:
             return rgbs
+        if ic.yuv:
+            if rgbs.dim() != 4 or rgbs.shape[0] != 1:
+                raise ValueError(f"rgbs: uint8 {ic.type} frames of shape (1, T, 3 h0 / 2, w0), got {tuple(rgbs.shape)}")
+            return self._yuv_to_lab(ic, rgbs[0], "rgbs", ic.size).unsqueeze(0)
         if rgbs.dim() != 5 or rgbs.shape[0] != 1:
             raise ValueError(f"rgbs: uint8 frames of shape (1, T, h0, w0, 3) ('thwc') or (1, T, 3, h0, w0) ('tchw'), got {tuple(rgbs.shape)}")
         return ops.frames_to_lab(rgbs[0], ic.size, layout=ic.layout).unsqueeze(0)
+
+    def _yuv_to_lab(self, ic, packed: torch.Tensor, name: str, size, pad=(0, 0, 0, 0)) -> torch.Tensor:
+        """Packed NV12 / I420 frames (T, 3 h0 / 2, w0) of test_cfg.input's type -> ops.yuv_frames_to_lab of their planes (T, 3, hp, wp)."""
+        try:
+            y, u, v = ops.yuv420_planes(packed, ic.type)
+        except ValueError as e:
+            lead = "1, " if name == "rgbs" else "1, 1, "
+            raise ValueError(f"{name}: uint8 {ic.type} frames of shape ({lead}T, 3 h0 / 2, w0) with h0 and w0 even, got the frames "
+                             f"{tuple(packed.shape)} ({e})") from None
+        return ops.yuv_frames_to_lab(y, u, v, size, pad, ic.matrix, ic.range, ic.siting)
 
     def _label_frames(self, imgs: torch.Tensor):
         """The label-map call's imgs -> the frames padded to a multiple of _pad_unit() (T, 3, hp, wp), the network size (h, w), the pad.
@@ -375,6 +391,13 @@ class VanillaTracker(BaseTracker):
             h, w = imgs.shape[-2:]
             _, pad = engine.pad_divide_by(h, w, self._pad_unit())
             return torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1), (h, w), pad
+        if ic.yuv:
+            if imgs.dim() != 5 or imgs.shape[0] != 1 or imgs.shape[1] != 1:
+                raise ValueError(f"imgs: uint8 {ic.type} frames of shape (1, 1, T, 3 h0 / 2, w0), got {tuple(imgs.shape)}")
+            v = imgs[0, 0]
+            h, w = ic.size if ic.size is not None else (v.shape[1] // 3 * 2, v.shape[2])
+            _, pad = engine.pad_divide_by(h, w, self._pad_unit())
+            return self._yuv_to_lab(ic, v, "imgs", (h, w), pad), (h, w), pad
         if imgs.dim() != 6:
             raise ValueError(f"imgs: uint8 frames of shape (1, 1, T, h0, w0, 3) ('thwc') or (1, 1, T, 3, h0, w0) ('tchw'), got {tuple(imgs.shape)}")
         v = imgs[0, 0]
@@ -726,7 +749,11 @@ class HRVanillaTracker(VanillaTracker):
         from .common import bilinear_sample
         self._refuse_occlusion("forward_test_forward (forward warping)")
         ic = self._raw_input(imgs, "imgs")
-        if ic is not None:                                                             # uint8 (B, 1, T, h0, w0, 3) | (B, 1, T, 3, h0, w0): test_cfg.input
+        if ic is not None and ic.yuv:                                                  # uint8 (1, 1, T, 3 h0 / 2, w0): packed NV12 / I420
+            if imgs.dim() != 5 or imgs.shape[0] != 1 or imgs.shape[1] != 1:
+                raise ValueError(f"imgs: uint8 {ic.type} frames of shape (1, 1, T, 3 h0 / 2, w0), got {tuple(imgs.shape)}")
+            frames = self._yuv_to_lab(ic, imgs[0, 0], "imgs", ic.size)                 # (T, 3, h, w)
+        elif ic is not None:                                                           # uint8 (B, 1, T, h0, w0, 3) | (B, 1, T, 3, h0, w0): test_cfg.input
             assert imgs.dim() == 6 and imgs.shape[0] * imgs.shape[1] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"
             frames = ops.frames_to_lab(imgs[0, 0], ic.size, layout=ic.layout)         # (T, 3, h, w)
         else:

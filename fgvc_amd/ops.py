@@ -1502,6 +1502,116 @@ def frames_to_lab(frames_u8: torch.Tensor, size: Optional[Tuple[int, int]] = Non
     return out
 
 
+# ---- the input stage for 8-bit YUV 4:2:0 video: NV12 / I420 -> the network input, or RGB bytes --------------------
+
+YUV_FORMATS = ("nv12", "i420")
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
+YUV_RANGES = {"limited": (16.0, 255.0 / 219.0, 255.0 / 224.0), "full": (0.0, 1.0, 1.0)}    # (y_off, cy, sc)
+YUV_SITINGS = ("left", "center")                                            # = FGVC_YUV_SITING_LEFT, FGVC_YUV_SITING_CENTER
+
+
+def yuv_coefficients(matrix: str = "bt601", range: str = "limited") -> Tuple[float, float, float, float, float, float]:
+    """(y_off, cy, crv, cgu, cgv, cbu) of R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with yy = cy (Y - y_off), cb = U - 128,
+    cr = V - 128: computed in float64 from Kr, Kb of `matrix` ('bt601' | 'bt709') and the scales of `range` ('limited': 16..235 / 16..240;
+    'full'), as Python floats.  The kernels take them rounded to f32 once."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix={matrix!r}: one of {tuple(YUV_MATRICES)}")
+    if range not in YUV_RANGES:
+        raise ValueError(f"range={range!r}: one of {tuple(YUV_RANGES)}")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    y_off, cy, sc = YUV_RANGES[range]
+    return (y_off, cy, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
+
+
+def yuv420_planes(frames: torch.Tensor, fmt: str):
+    """Packed 4:2:0 frames (T, 3 h0 / 2, w0) uint8 -- h0 luma rows, then NV12's h0 / 2 rows of interleaved (u, v) pairs or I420's u plane
+    and v plane -- -> the views (y (T, h0, w0), u, v (T, h0 / 2, w0 / 2)); nothing is copied.  ValueError unless the rows are a multiple of
+    3 and h0, w0 are even (an odd frame has no packed form: pass its planes)."""
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"fmt={fmt!r}: one of {YUV_FORMATS}")
+    if frames.dim() != 3:
+        raise ValueError(f"frames: packed {fmt} frames of shape (T, 3 h0 / 2, w0), got {tuple(frames.shape)}")
+    T, rows, w0 = frames.shape
+    h0 = rows // 3 * 2
+    if rows % 3 or h0 % 2 or w0 % 2 or h0 == 0 or w0 == 0:
+        raise ValueError(f"frames: packed {fmt} frames of shape (T, 3 h0 / 2, w0) with h0 and w0 even, got {tuple(frames.shape)}")
+    y, c = frames[:, :h0], frames[:, h0:]
+    if fmt == "nv12":
+        uv = c.unflatten(2, (w0 // 2, 2))                                             # (T, h0 / 2, w0 / 2, 2)
+        return y, uv[..., 0], uv[..., 1]
+    if T > 0 and (c.stride(1), c.stride(2)) != (w0, 1):                               # (a row of the u plane is half a packed row)
+        raise ValueError(f"frames: the bytes of a packed i420 frame must be adjacent (strides (.., {w0}, 1)), got {frames.stride()}; "
+                         "pass the planes of a crop instead")
+    pl = c.as_strided((T, 2, h0 // 2, w0 // 2), (c.stride(0), (h0 // 2) * (w0 // 2), w0 // 2, 1), c.storage_offset())
+    return y, pl[:, 0], pl[:, 1]
+
+
+def _yuv_args(y, u, v, matrix, range, siting):
+    """The checks the two YUV calls share -> (T, h0, w0, the kernel's stride and coefficient arguments)."""
+    for name, p in (("y", y), ("u", u), ("v", v)):
+        if not p.is_cuda:
+            raise _lib.FgvcHipError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
+        if p.dtype != torch.uint8:
+            raise TypeError(f"{name}: expected torch.uint8, got {p.dtype}")
+        if p.dim() != 3:
+            raise ValueError(f"{name}: 3 dimensions ({'T, h0, w0' if name == 'y' else 'T, (h0 + 1) // 2, (w0 + 1) // 2'}), got {tuple(p.shape)}")
+    if siting not in YUV_SITINGS:
+        raise ValueError(f"siting={siting!r}: one of {YUV_SITINGS}")
+    coef = yuv_coefficients(matrix, range)
+    T, h0, w0 = y.shape
+    want = (T, (h0 + 1) // 2, (w0 + 1) // 2)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)}, got {tuple(u.shape)} and {tuple(v.shape)}")
+    if u.device != y.device or v.device != y.device:
+        raise ValueError(f"y, u, v: one device, got {y.device}, {u.device}, {v.device}")
+    if w0 > 1 and y.stride(2) != 1:
+        raise ValueError(f"y: luma columns must be adjacent (last stride 1), got strides {y.stride()}")
+    if any(n > 1 and su != sv for n, su, sv in zip(want, u.stride(), v.stride())):    # (an axis of one sample: its stride is never used)
+        raise ValueError(f"u, v: the same strides (the kernel takes one set for both planes), got {u.stride()} and {v.stride()}")
+    return T, h0, w0, (y.stride(0), y.stride(1), u.stride(0), u.stride(1), u.stride(2)), coef, YUV_SITINGS.index(siting)
+
+
+def yuv_frames_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size: Optional[Tuple[int, int]] = None,
+                      pad: Tuple[int, int, int, int] = (0, 0, 0, 0), matrix: str = "bt601", range: str = "limited", siting: str = "left",
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """8-bit YUV 4:2:0 planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> (T, 3, hp, wp) f32: per frame exactly
+    datasets.preprocess_yuv420_frames (chroma bilinear at the luma pixel by `siting`; R'G'B' by `matrix` and `range`, unclamped; then
+    frames_to_lab's steps) at (top, left) of a border of exact zeros -- one launch of fgvc_frames_yuv420_to_lab_f32.  The planes are read
+    through their strides (yuv420_planes' views of packed NV12 / I420 frames, crops, time slices): nothing is copied; the luma columns
+    must be adjacent and u, v share their strides.  NV21 / YV12: pass the planes swapped.  `size`, `pad`, `out`: as frames_to_lab's."""
+    T, h0, w0, strides, coef, sit = _yuv_args(y, u, v, matrix, range, siting)
+    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
+    left, right, top, bottom = (int(p) for p in pad)
+    shape = (T, 3, top + h + bottom, left + w + right)
+    if out is None:
+        out = torch.empty(shape, device=y.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    _lib.call("fgvc_frames_yuv420_to_lab_f32", _ptr(y), _ptr(u), _ptr(v), T, h0, w0, *strides, *coef, sit, h, w, left, right, top, bottom,
+              _ptr(out), _stream(y))
+    return out
+
+
+def yuv_frames_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                       siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same planes -> (T, h0, w0, 3) uint8 RGB: rint (half to even) of the unclamped R'G'B' clamped to [0, 255], exactly
+    datasets.yuv420_to_rgb8 -- one launch of fgvc_frames_yuv420_to_rgb8.  What render_frames draws on.  `out`: a contiguous uint8 tensor
+    of that shape on the planes' device."""
+    T, h0, w0, strides, coef, sit = _yuv_args(y, u, v, matrix, range, siting)
+    shape = (T, h0, w0, 3)
+    if out is None:
+        out = torch.empty(shape, device=y.device, dtype=torch.uint8)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != y.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous uint8 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    _lib.call("fgvc_frames_yuv420_to_rgb8", _ptr(y), _ptr(u), _ptr(v), T, h0, w0, *strides, *coef, sit, _ptr(out), _stream(y))
+    return out
+
+
 # ---- DAVIS J&F on the device: the integer counts metrics.db_eval_iou / f_measure divide (DESIGN.md section 15) ------------------------
 
 JF_TILE = 32            # rows one workgroup of fgvc_jf_counts_u8 owns (= fgvc_jf_tile_rows(); the tests put mask edges on its multiples)

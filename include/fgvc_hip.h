@@ -399,6 +399,31 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
                                 int64_t stride_c, int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out,
                                 void* stream);
 
+/* ---- The input stage for 8-bit YUV 4:2:0 video: what decoders hand out (NV12, I420; NV21 / YV12 with u and v
+ * swapped) -> the network's planar f32 input, or packed RGB bytes, one launch each.  Per frame what datasets.preprocess_yuv420_frames and
+ * datasets.yuv420_to_rgb8 define.
+ *   y [T][h0][w0] bytes by two BYTE strides (frame, row; columns adjacent); u, v [T][ch][cw] bytes, ch = (h0 + 1) / 2, cw = (w0 + 1) / 2, by
+ *           three strides (frame, row, pixel), the same for both: pixel stride 1 for I420's planes, 2 for NV12's pairs (v = u + 1).
+ *   Chroma at luma pixel (x, y): bilinear and edge clamped at sx = x / 2 (FGVC_YUV_SITING_LEFT: MPEG-2, H.264, HEVC) or x / 2 - 0.25
+ *           (FGVC_YUV_SITING_CENTER: JPEG, MPEG-1), sy = y / 2 - 0.25 for both; exact in f32 (quarter weights, byte samples).
+ *   Decode, every f32 operation rounded and none fused: yy = cy (Y - y_off), cb = U' - 128, cr = V' - 128, R = yy + crv cr,
+ *           G = (yy + cgu cb) + cgv cr, B = yy + cbu cb -- on the 0..255 scale, neither clamped nor rounded.  The six coefficients come by
+ *           value (ops.yuv_coefficients computes them in double from the matrix and the range and rounds once).
+ *   ..._to_lab_f32: then exactly fgvc_frames_rgb8_to_lab_f32's steps in its arithmetic (resize of the unclamped R'G'B' with double
+ *           coordinates, / 255 and clamp, sRGB -> Lab, normalise, zero border); out as there.  The sRGB transfer is evaluated per value.
+ *   ..._to_rgb8: rint (half to even) of clamp(R'G'B', 0, 255); out [T][h0][w0][3] bytes, contiguous.
+ * FGVC_ERR_INVALID_ARG for a null pointer, a non-positive size, a negative pad, a siting other than the two, and a shape beyond the launch
+ * grid (as fgvc_frames_rgb8_to_lab_f32; source sides below 2^30) -- all before any launch.  No workspace, no atomics, no LDS. */
+#define FGVC_YUV_SITING_LEFT 0
+#define FGVC_YUV_SITING_CENTER 1
+int fgvc_frames_yuv420_to_lab_f32(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
+                                  int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy,
+                                  float crv, float cgu, float cgv, float cbu, int siting, int h, int w, int pad_left, int pad_right,
+                                  int pad_top, int pad_bottom, float* out, void* stream);
+int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
+                               int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy, float crv,
+                               float cgu, float cgv, float cbu, int siting, uint8_t* out, void* stream);
+
 /* ---- DAVIS J&F on the device: the integer pixel counts that metrics.db_eval_iou and metrics.f_measure divide.
  *   gt, pred [T][h][w] uint8 object ids, 0 = background.  For object o = 1 .. n_objects: G = (gt == o), S = (pred == o); an id above
  *           n_objects belongs to no object (metrics.davis_masks_to_objects).

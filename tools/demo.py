@@ -7,6 +7,7 @@ mediapy: frames come and go through PIL).
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
+    python tools/demo.py CLIP.y4m --task points --query-points t x y ... [--yuv-matrix bt601|bt709] --out OUT
 
 FRAMES_DIR holds the clip's frames as JPEG / PNG files, taken in name order.  The frames go to the model as they are decoded -- uint8 RGB, on
 the device -- through test_cfg.input = dict(type='rgb8'); the mask task keeps its id maps on the device
@@ -14,6 +15,9 @@ the device -- through test_cfg.input = dict(type='rgb8') (DESIGN.md section 14);
 (section 16) and OUT gets frame_%05d.png and demo.gif.  --host-render paints with the numpy backend instead (the same bytes, for comparison).
 --task flow writes the dense forward flow of every frame pair (test_cfg.flow, section 17) as flow_%05d.flo and, coloured by
 fgvc_amd.viz.flow_to_rgb on the host, flow_%05d.png.
+CLIP.y4m (what `ffmpeg -i clip.mp4 clip.y4m` writes: uncompressed 8-bit 4:2:0) goes to the model as the file holds it -- packed I420, through
+test_cfg.input = dict(type='i420', ...) with the file's chroma siting and range -- and is painted on
+ops.yuv_frames_to_rgb8's bytes.  A Y4M file does not say which matrix made its YUV: --yuv-matrix, by default bt709 from 720 rows up, else bt601.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -59,6 +63,46 @@ def synthetic_frames(T: int, H: int, W: int, seed: int = 0) -> np.ndarray:
     return np.clip(np.rint(np.stack(out)), 0, 255).astype(np.uint8)
 
 
+def is_y4m(path) -> bool:
+    return bool(path) and os.path.isfile(path) and path.lower().endswith(".y4m")
+
+
+def yuv_matrix_default(height: int) -> str:
+    """What a file that does not say is taken to be: HD material (720 rows and up) BT.709, anything smaller BT.601."""
+    return "bt709" if height >= 720 else "bt601"
+
+
+def load_y4m(a, dev):
+    """CLIP.y4m -> (packed I420 frames (T, 3 H / 2, W) uint8 on the device, their RGB bytes (T, H, W, 3) on the device,
+    test_cfg.input for them without its size)."""
+    from fgvc_amd import datasets, ops
+    packed, info = datasets.read_y4m(a.frames)
+    if packed.shape[0] == 0:
+        raise ValueError(f"{a.frames}: no frames")
+    matrix = a.yuv_matrix or yuv_matrix_default(info["height"])
+    print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, siting {info['siting']}, {info['range']} range; matrix {matrix} "
+          f"({'--yuv-matrix' if a.yuv_matrix else 'by the height: the file does not say'})")
+    packed = packed.to(dev)
+    kw = dict(matrix=matrix, range=info["range"], siting=info["siting"])
+    rgb = ops.yuv_frames_to_rgb8(*ops.yuv420_planes(packed, "i420"), **kw)
+    return packed, rgb, dict(type="i420", **kw)
+
+
+def _input(a, size):
+    """test_cfg.input of the clip at hand: RGB bytes, or what load_y4m made of the file."""
+    if getattr(a, "yuv_input", None):
+        return dict(a.yuv_input, size=size)
+    return dict(type="rgb8", size=size, layout="thwc")
+
+
+def _raw(a, frames, dev) -> torch.Tensor:
+    """The clip as the model takes it, on the device: (T, H, W, 3) RGB bytes, or the Y4M file's packed frames."""
+    packed = getattr(a, "yuv_packed", None)
+    if packed is not None:
+        return packed
+    return frames.to(dev) if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev)
+
+
 def build_model(a, dev, **extra):
     cfg = dict(precede_frames=a.precede_frames, topk=a.topk, temperature=0.07, neighbor_range=a.neighbor_range, with_first=True,
                with_first_neighbor=True, batch_step=a.batch_step, **extra)
@@ -84,11 +128,11 @@ def run_points(a, frames: np.ndarray, dev):
     size = tuple(a.size) if a.size else (H, W)
     q[:, 1:] = viz.scale_tracks(q[:, 1:], (H, W), size)
     chain = dict(chain=dict(type="flow", visibility=a.chain_visibility)) if a.chain else {}
-    model = build_model(a, dev, input=dict(type="rgb8", size=tuple(a.size) if a.size else None, layout="thwc"), **chain)
+    model = build_model(a, dev, input=_input(a, tuple(a.size) if a.size else None), **chain)
     qp = torch.from_numpy(q).float()[None].to(dev)
     P = q.shape[0]
     with torch.no_grad():
-        out = model(test_mode=True, rgbs=torch.from_numpy(frames).to(dev)[None], query_points=qp,
+        out = model(test_mode=True, rgbs=_raw(a, frames, dev)[None], query_points=qp,
                     trajectories=torch.zeros(1, T, P, 2, device=dev), visibilities=torch.ones(1, T, P, device=dev))
     traj, qp_out = out[2][0], out[4][0]                                  # (T, P, 2) at the model's size; the points in the order of its columns
     tracks = viz.scale_tracks(traj.permute(1, 0, 2), size, (H, W))
@@ -106,9 +150,9 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     mask = np.asarray(Image.open(a.first_mask))
     if mask.ndim != 2 or mask.shape != (H, W):
         raise ValueError(f"--first-mask: a palette or grey PNG of object ids, {H} x {W} as the frames, got an array of shape {mask.shape}")
-    model = build_model(a, dev, input=dict(type="rgb8", size=None, layout="thwc"), masks="device")
+    model = build_model(a, dev, input=_input(a, None), masks="device")
     with torch.no_grad():
-        out = model(test_mode=True, imgs=torch.from_numpy(frames).to(dev)[None, None], ref_seg_map=torch.from_numpy(mask.astype(np.uint8))[None].to(dev),
+        out = model(test_mode=True, imgs=_raw(a, frames, dev)[None, None], ref_seg_map=torch.from_numpy(mask.astype(np.uint8))[None].to(dev),
                     img_meta=[dict(original_shape=(H, W))])
     return out[0]
 
@@ -116,9 +160,9 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
 def run_flow(a, frames: np.ndarray, dev) -> dict:
     """-> forward_test_flow's dict of device tensors at the clip's own size (test_cfg.flow)."""
     flow = dict(type="window", step=a.flow_step, occlusion=a.flow_occlusion)
-    model = build_model(a, dev, input=dict(type="rgb8", size=None, layout="thwc"), flow=flow)
+    model = build_model(a, dev, input=_input(a, None), flow=flow)
     with torch.no_grad():
-        return model(test_mode=True, imgs=torch.from_numpy(frames).to(dev)[None, None])
+        return model(test_mode=True, imgs=_raw(a, frames, dev)[None, None])
 
 
 def write_flow(out_dir: str, out: dict) -> int:
@@ -146,9 +190,11 @@ def write(out_dir: str, rendered: np.ndarray, fps: float):
     images[0].save(os.path.join(out_dir, "demo.gif"), save_all=True, append_images=images[1:], duration=int(round(1000.0 / fps)), loop=0)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("frames", nargs="?", help="a directory of JPEG / PNG frames")
+    ap.add_argument("frames", nargs="?", help="a directory of JPEG / PNG frames, or a .y4m file (8-bit 4:2:0)")
+    ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default=None,
+                    help="the matrix of a .y4m clip's YUV (the file does not say); default: bt709 from 720 rows up, else bt601")
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"), help="a generated clip instead of FRAMES_DIR")
     ap.add_argument("--task", choices=("points", "vos", "flow"), required=True)
     ap.add_argument("--flow-step", type=int, default=1, help="frame distance of a flow pair (--task flow)")
@@ -180,10 +226,21 @@ def main(argv=None):
         ap.error("--task points needs --query-points")
     if a.task == "vos" and not a.first_mask:
         ap.error("--task vos needs --first-mask")
+    if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
+        ap.error("--yuv-matrix goes with a .y4m clip")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("tools/demo.py runs the model on the GPU (fgvc_amd has no CPU path)")
     dev = torch.device("cuda:0")
-    frames = synthetic_frames(*a.synthetic, seed=a.seed) if a.synthetic else load_frames(a.frames)
+    a.yuv_packed = a.yuv_input = None
+    if is_y4m(a.frames):
+        a.yuv_packed, frames, a.yuv_input = load_y4m(a, dev)             # frames: the RGB bytes, on the device
+    else:
+        frames = synthetic_frames(*a.synthetic, seed=a.seed) if a.synthetic else load_frames(a.frames)
     tracks = visibles = ids = points = None
     if a.task == "flow":
         n = write_flow(a.out, run_flow(a, frames, dev))
@@ -195,9 +252,12 @@ def main(argv=None):
         ids = run_vos(a, frames, dev)
     kw = dict(ids=ids, tracks=tracks, visibles=visibles, radius=a.radius, alpha=a.alpha, contour=not a.no_contour)
     if a.host_render:
+        frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
         rendered = viz.render(frames, backend="host", **kw)
     else:
-        rendered = viz.render(torch.from_numpy(frames).to(dev), backend="hip", **kw).cpu().numpy()
+        on_dev = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev)
+        rendered = viz.render(on_dev, backend="hip", **kw).cpu().numpy()
+    frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
     write(a.out, rendered, a.fps)
     print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}, {'host' if a.host_render else 'hip'} renderer)")
     return dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
