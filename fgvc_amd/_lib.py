@@ -96,6 +96,10 @@ SIGNATURES = {
                                            _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_frames_yuv420_to_rgb8": (_i, [_p, _p, _p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f,
                                         _i, _p, _p]),
+    "fgvc_frames_rgb8_to_yuv420": (_i, [_p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _p, _p,
+                                        C.c_int64, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f, _f, _i, _p]),
+    "fgvc_yuv_out_tile_rows": (_i, []),
+    "fgvc_yuv_out_tile_cols": (_i, []),
     "fgvc_jf_tile_rows": (_i, []),
     "fgvc_jf_counts_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_render_frames_u8": (_i, [_p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _i, _i, _i, _p, C.c_int64, C.c_int64, _p, _i, _i,

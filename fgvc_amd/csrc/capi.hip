@@ -50,6 +50,9 @@ int frames_yuv420_to_lab_launch(const uint8_t*, const uint8_t*, const uint8_t*, 
                                 long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
 int frames_yuv420_to_rgb8_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
                                  long long, const float*, int, uint8_t*, hipStream_t);
+int frames_rgb8_to_yuv420_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, uint8_t*, long long, long long,
+                                 uint8_t*, uint8_t*, long long, long long, long long, const float*, int, hipStream_t);
+void yuv_out_tile(int*, int*);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
 int render_frames_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
@@ -690,6 +693,45 @@ int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t
   const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
   return frames_yuv420_to_rgb8_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, out,
                                       (hipStream_t)stream);
+}
+
+int fgvc_yuv_out_tile_rows(void) {
+  int rows, cols;
+  yuv_out_tile(&rows, &cols);
+  return rows;
+}
+
+int fgvc_yuv_out_tile_cols(void) {
+  int rows, cols;
+  yuv_out_tile(&rows, &cols);
+  return cols;
+}
+
+int fgvc_frames_rgb8_to_yuv420(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                               int64_t stride_c, uint8_t* y, int64_t y_stride_t, int64_t y_stride_y, uint8_t* u, uint8_t* v,
+                               int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float kr, float kg, float kb, float y_off, float sy,
+                               float cu, float cv, int siting, void* stream) {
+  FGVC_REQUIRE(T >= 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "fgvc_frames_rgb8_to_yuv420: T=%d negative or a non-positive size (%d x %d)", T,
+               h0, w0);
+  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_yuv420: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", siting);
+  const int rows = fgvc_yuv_out_tile_rows();
+  // grid.z = T and grid.y = ceil(h0 / rows) are 16-bit; a lane's column index stays inside an int
+  FGVC_REQUIRE(T <= 65535 && h0 <= rows * 65535ll && w0 < (1 << 30), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_yuv420: shape beyond the launch grid (T <= 65535, rows <= %lld, columns < 2^30)", rows * 65535ll);
+  const long long ch = (h0 + 1) / 2, cw = (w0 + 1) / 2;
+  FGVC_REQUIRE(y_stride_y >= w0 && (T <= 1 || y_stride_t >= (h0 - 1) * (long long)y_stride_y + w0), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_yuv420: luma rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
+               (long long)y_stride_t, (long long)y_stride_y, h0, w0);
+  const long long crow = (cw - 1) * (long long)c_stride_x + 1;        // the bytes a chroma row spans
+  FGVC_REQUIRE(c_stride_x >= 1 && c_stride_y >= crow && (T <= 1 || c_stride_t >= (ch - 1) * (long long)c_stride_y + crow), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_rgb8_to_yuv420: chroma samples, rows and frames must not overlap (strides %lld, %lld, %lld bytes for %lld x %lld)",
+               (long long)c_stride_t, (long long)c_stride_y, (long long)c_stride_x, ch, cw);
+  if (T == 0) return FGVC_OK;                                         // no pixel exists
+  FGVC_REQUIRE(frames && y && u && v, FGVC_ERR_INVALID_ARG, "fgvc_frames_rgb8_to_yuv420: null pointer");
+  const float coef[7] = {kr, kg, kb, y_off, sy, cu, cv};
+  return frames_rgb8_to_yuv420_launch(frames, T, h0, w0, stride_t, stride_y, stride_x, stride_c, y, y_stride_t, y_stride_y, u, v, c_stride_t,
+                                      c_stride_y, c_stride_x, coef, siting, (hipStream_t)stream);
 }
 
 int fgvc_jf_tile_rows(void) { return jf_tile_rows(); }

@@ -730,6 +730,71 @@ def preprocess_yuv420_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, 
     return ((lab - mean) / std).unsqueeze(0)
 
 
+# ---- the way out: RGB bytes -> 8-bit YUV 4:2:0, the output contract as torch ops -----------------------------------
+def _chroma_filter(p: torch.Tensor, siting: str) -> torch.Tensor:
+    """One channel (T, h0, w0) f32 of byte values -> its value at every chroma sample (T, (h0 + 1) // 2, (w0 + 1) // 2): vertically midway
+    between the luma rows 2 j and 2 j + 1 (the position yuv420_chroma_at_luma assumes), horizontally midway between the columns 2 i and
+    2 i + 1 ('center': the four added, x 0.25) or on column 2 i ('left': weights 1, 2, 1 over 2 i - 1 .. 2 i + 1 per row, the two rows added,
+    x 0.125); rows and columns off the frame repeat the edge.  Exact: eighths on bytes."""
+    T, h0, w0 = p.shape
+    r0 = torch.arange((h0 + 1) // 2, device=p.device) * 2
+    r1 = (r0 + 1).clamp(max=h0 - 1)
+    c0 = torch.arange((w0 + 1) // 2, device=p.device) * 2
+    cp, cm = (c0 + 1).clamp(max=w0 - 1), (c0 - 1).clamp(min=0)
+    a, b = p[:, r0], p[:, r1]
+    if siting == "center":
+        return ((a[:, :, c0] + a[:, :, cp]) + (b[:, :, c0] + b[:, :, cp])) * 0.25
+    top = (a[:, :, cm] + 2.0 * a[:, :, c0]) + a[:, :, cp]
+    bot = (b[:, :, cm] + 2.0 * b[:, :, c0]) + b[:, :, cp]
+    return (top + bot) * 0.125
+
+
+def rgb8_to_yuv420(frames: torch.Tensor, matrix: str = "bt601", range: str = "limited", siting: str = "left"):
+    """uint8 RGB frames (T, h0, w0, 3) -> (y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2)) uint8, odd sizes included: with
+    ops.rgb_to_yuv_coefficients rounded to f32 and lum(R, G, B) = (kr R + kg G) + kb B, Y = y_off + sy lum(R, G, B) at every pixel; the R, G, B
+    bytes filtered to the chroma sample (_chroma_filter) give L = lum(Rm, Gm, Bm), U = 128 + cu (Bm - L), V = 128 + cv (Rm - L); each byte is
+    the value clamped to [0, 255] and rounded half to even.  One rounded f32 operation after another, nothing fused: the order
+    ops.rgb_frames_to_yuv420 keeps and equals byte for byte.  CPU or GPU tensors."""
+    from .ops import rgb_to_yuv_coefficients
+    if siting not in ("left", "center"):
+        raise ValueError(f"siting={siting!r}: 'left' or 'center'")
+    kr, kg, kb, y_off, sy, cu, cv = (float(np.float32(c)) for c in rgb_to_yuv_coefficients(matrix, range))
+    if frames.dtype != torch.uint8:
+        raise TypeError(f"frames: expected torch.uint8, got {frames.dtype}")
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[1] == 0 or frames.shape[2] == 0:
+        raise ValueError(f"frames: (T, h0, w0, 3) with h0, w0 > 0, got {tuple(frames.shape)}")
+    R, G, B = (frames[..., c].to(torch.float32) for c in (0, 1, 2))
+
+    def lum(r, g, b):
+        return (kr * r + kg * g) + kb * b
+
+    def byte(x):
+        return x.clamp(0, 255).round().to(torch.uint8)
+    y = y_off + sy * lum(R, G, B)
+    Rm, Gm, Bm = (_chroma_filter(p, siting) for p in (R, G, B))
+    L = lum(Rm, Gm, Bm)
+    return byte(y), byte(128.0 + cu * (Bm - L)), byte(128.0 + cv * (Rm - L))
+
+
+def pack_yuv420(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: str = "i420") -> torch.Tensor:
+    """Planes y (T, h0, w0), u, v (T, h0 / 2, w0 / 2) uint8 -> packed frames (T, 3 h0 / 2, w0): the luma rows, then NV12's rows of
+    interleaved (u, v) pairs or I420's u plane and v plane -- the inverse of ops.yuv420_planes.  ValueError for an odd size (no packed form)."""
+    if fmt not in ("nv12", "i420"):
+        raise ValueError(f"fmt={fmt!r}: one of ('nv12', 'i420')")
+    if y.dim() != 3 or y.shape[1] == 0 or y.shape[2] == 0:
+        raise ValueError(f"y: (T, h0, w0) with h0, w0 > 0, got {tuple(y.shape)}")
+    T, h0, w0 = y.shape
+    if h0 % 2 or w0 % 2:
+        raise ValueError(f"y: a {h0} x {w0} frame has no packed {fmt} form (an odd side)")
+    want = (T, h0 // 2, w0 // 2)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)}, got {tuple(u.shape)} and {tuple(v.shape)}")
+    if any(p.dtype != torch.uint8 for p in (y, u, v)):
+        raise TypeError(f"y, u, v: expected torch.uint8, got {y.dtype}, {u.dtype}, {v.dtype}")
+    c = torch.stack([u, v], -1 if fmt == "nv12" else 1).reshape(T, h0 // 2, w0)
+    return torch.cat([y, c], 1).contiguous()
+
+
 Y4M_MAGIC = b"YUV4MPEG2"
 _Y4M_SITING = {"420jpeg": "center", "420mpeg2": "left", "420": "left"}
 

@@ -1612,6 +1612,100 @@ def yuv_frames_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix
     return out
 
 
+# ---- the output stage for 8-bit YUV 4:2:0 video: RGB bytes -> NV12 / I420 ------------------------------------------
+
+YUV_OUT_TILE = (8, 512)  # luma rows, columns one workgroup of fgvc_frames_rgb8_to_yuv420 owns (= fgvc_yuv_out_tile_rows/_cols(); the tests go one past them)
+
+
+def rgb_to_yuv_coefficients(matrix: str = "bt601", range: str = "limited") -> Tuple[float, float, float, float, float, float, float]:
+    """(kr, kg, kb, y_off, sy, cu, cv) of Y = y_off + sy lum, U = 128 + cu (B - lum), V = 128 + cv (R - lum) with lum = (kr R + kg G) + kb B:
+    the inverse of yuv_coefficients' matrix, computed in float64 from the same tables -- kg = 1 - kr - kb, sy = 1 / cy,
+    cu = 1 / (2 (1 - kb) sc), cv = 1 / (2 (1 - kr) sc) -- as Python floats.  The kernel takes them rounded to f32 once."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix={matrix!r}: one of {tuple(YUV_MATRICES)}")
+    if range not in YUV_RANGES:
+        raise ValueError(f"range={range!r}: one of {tuple(YUV_RANGES)}")
+    kr, kb = YUV_MATRICES[matrix]
+    y_off, cy, sc = YUV_RANGES[range]
+    return (kr, 1.0 - kr - kb, kb, y_off, 1.0 / cy, 1.0 / (2.0 * (1.0 - kb) * sc), 1.0 / (2.0 * (1.0 - kr) * sc))
+
+
+def rgb_frames_to_yuv420(frames_u8: torch.Tensor, fmt: str = "i420", layout: str = "thwc", matrix: str = "bt601", range: str = "limited",
+                         siting: str = "left", out: Optional[torch.Tensor] = None, planes=None):
+    """uint8 RGB frames (T, h0, w0, 3) ('thwc') or (T, 3, h0, w0) ('tchw') -> 8-bit Y'CbCr 4:2:0, exactly datasets.rgb8_to_yuv420 (Y' at
+    every pixel; the R, G, B bytes filtered to the chroma position of `siting`, edge clamped, then Cb, Cr; rint half to even of the clamped
+    value) -- one launch of fgvc_frames_rgb8_to_yuv420 on the current stream.  The frames are read through their own strides: a view (a
+    crop, a permuted tensor, a time slice) is not copied.
+    Without `planes`: returns the packed (T, 3 h0 / 2, w0) frames of `fmt` ('i420' | 'nv12', what yuv420_planes takes apart and
+    datasets.write_y4m writes), into `out` when given (a contiguous uint8 tensor of that shape on the frames' device); h0 and w0 must be even.
+    With planes=(y, u, v): writes into those uint8 views -- y (T, h0, w0) with adjacent columns, u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) with
+    the same strides; odd sizes, row strides wider than the rows, yuv420_planes' views of a packed buffer -- and returns them; `fmt` and
+    `out` do not apply.  NV21 / YV12: pass u and v swapped.  The outputs must not overlap the frames."""
+    if layout not in INPUT_LAYOUTS:
+        raise ValueError(f"layout={layout!r}: one of {INPUT_LAYOUTS}")
+    if siting not in YUV_SITINGS:
+        raise ValueError(f"siting={siting!r}: one of {YUV_SITINGS}")
+    coef = rgb_to_yuv_coefficients(matrix, range)
+    if not frames_u8.is_cuda:
+        raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f"frames_u8: expected torch.uint8, got {frames_u8.dtype}")
+    if frames_u8.dim() != 4:
+        raise ValueError(f"frames_u8: 4 dimensions ({'T, h0, w0, 3' if layout == 'thwc' else 'T, 3, h0, w0'}), got {tuple(frames_u8.shape)}")
+    f = frames_u8 if layout == "thwc" else frames_u8.permute(0, 2, 3, 1)              # (T, h0, w0, 3) view either way
+    T, h0, w0, ch = f.shape
+    if ch != 3:
+        raise ValueError(f"frames_u8: 3 channels (RGB) in layout {layout!r}, got {ch} (shape {tuple(frames_u8.shape)})")
+    if h0 == 0 or w0 == 0:
+        raise ValueError(f"frames_u8: empty frames ({h0} x {w0})")
+    dev = f.device
+    if planes is None:
+        if fmt not in YUV_FORMATS:
+            raise ValueError(f"fmt={fmt!r}: one of {YUV_FORMATS}")
+        if h0 % 2 or w0 % 2:
+            raise ValueError(f"frames_u8: {h0} x {w0} frames have no packed {fmt} form (an odd side); pass planes=(y, u, v) instead")
+        shape = (T, h0 // 2 * 3, w0)
+        if out is None:
+            out = torch.empty(shape, device=dev, dtype=torch.uint8)
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous uint8 tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        y, u, v = yuv420_planes(out, fmt)
+        result = out
+    else:
+        if out is not None:
+            raise ValueError("out: goes with the packed form; with planes=(y, u, v) the planes are the output")
+        if len(planes) != 3:
+            raise ValueError(f"planes: (y, u, v), got {len(planes)} tensors")
+        y, u, v = planes
+        want = (T, (h0 + 1) // 2, (w0 + 1) // 2)
+        for name, p, shp in (("y", y, (T, h0, w0)), ("u", u, want), ("v", v, want)):
+            if not p.is_cuda or p.device != dev:
+                raise ValueError(f"planes: {name} on {dev} with the frames, got {p.device}")
+            if p.dtype != torch.uint8:
+                raise TypeError(f"planes: {name}: expected torch.uint8, got {p.dtype}")
+            if tuple(p.shape) != shp:
+                raise ValueError(f"planes: {name} of shape {shp} for frames {tuple(frames_u8.shape)} in layout {layout!r}, got {tuple(p.shape)}")
+        if w0 > 1 and y.stride(2) != 1:
+            raise ValueError(f"planes: luma columns must be adjacent (last stride 1), got strides {y.stride()}")
+        if any(n > 1 and su != sv for n, su, sv in zip(want, u.stride(), v.stride())):    # (an axis of one sample: its stride is never used)
+            raise ValueError(f"planes: u, v: the same strides (the kernel takes one set for both planes), got {u.stride()} and {v.stride()}")
+        result = (y, u, v)
+    if T == 0:
+        return result
+
+    def stride(p, d, n, least):
+        """an axis of one sample has no stride to speak of: the least the kernel's overlap check accepts"""
+        return p.stride(d) if n > 1 else max(p.stride(d), least)
+    cw, chh = (w0 + 1) // 2, (h0 + 1) // 2
+    csx = stride(u, 2, cw, 1)
+    csy = stride(u, 1, chh, (cw - 1) * csx + 1)
+    ysy = stride(y, 1, h0, w0)
+    st, sy, sx, sc = f.stride()                                                       # (uint8: elements are bytes)
+    _lib.call("fgvc_frames_rgb8_to_yuv420", _ptr(f), T, h0, w0, st, sy, sx, sc, _ptr(y), y.stride(0), ysy, _ptr(u), _ptr(v), u.stride(0), csy, csx,
+              *coef, YUV_SITINGS.index(siting), _stream(f))
+    return result
+
+
 # ---- DAVIS J&F on the device: the integer counts metrics.db_eval_iou / f_measure divide (DESIGN.md section 15) ------------------------
 
 JF_TILE = 32            # rows one workgroup of fgvc_jf_counts_u8 owns (= fgvc_jf_tile_rows(); the tests put mask edges on its multiples)

@@ -3,6 +3,7 @@
     paint_point_track(frames, point_tracks, visibles, colors)    the reference's dot painter (flyingthingsplus/utils/visualize.py:85-155)
     overlay_masks(frames, ids, palette, alpha, contour)          object ids blended in, integer arithmetic, optional contour
     render(frames, ids=..., tracks=..., visibles=...)            overlay, then points
+    frames_to_yuv420(frames, fmt, matrix, range, siting)         the painted frames as packed 8-bit 4:2:0 video
 
 backend='host' is plain numpy: it is the contract, the default, and works without a GPU.  backend='hip' is ONE launch of
 fgvc_render_frames_u8 (ops.render_frames) and is held to the host backend with `==`.  The per-pixel arithmetic, both backends:
@@ -341,3 +342,33 @@ def flow_to_rgb(flow, max_mag: Optional[float] = None) -> np.ndarray:
     out = np.floor(255.0 * col).astype(np.uint8)
     out[~fin] = 0
     return out
+
+
+# ---- results as video: RGB bytes -> packed 8-bit YUV 4:2:0 frames ----------------------------------------------------------
+def frames_to_yuv420(frames, fmt: str = "i420", matrix: str = "bt601", range: str = "limited", siting: str = "left", backend: str = "host"):
+    """frames (T, H, W, 3) uint8 with H and W even -> packed (T, 3 H / 2, W) uint8 frames of `fmt` ('i420', what datasets.write_y4m takes, or
+    'nv12'): Y'CbCr by `matrix` ('bt601' | 'bt709') and `range` ('limited' | 'full'), chroma filtered to `siting` ('left' | 'center').
+    backend='host': datasets.rgb8_to_yuv420 on the CPU, the contract; numpy in, numpy out (a tensor in, a CPU tensor out).
+    backend='hip': one launch of fgvc_frames_rgb8_to_yuv420 (ops.rgb_frames_to_yuv420), the same bytes; returns a CUDA tensor when
+    `frames` is one, numpy otherwise."""
+    import torch
+    from . import datasets
+    hip = _backend(backend)
+    if fmt not in ("i420", "nv12"):
+        raise ValueError(f"fmt={fmt!r}: one of ('i420', 'nv12')")
+    is_tensor = isinstance(frames, torch.Tensor)
+    f = frames if is_tensor else torch.from_numpy(np.ascontiguousarray(frames))
+    if f.dtype != torch.uint8:
+        raise TypeError(f"frames: expected uint8, got {f.dtype}")
+    if f.dim() != 4 or f.shape[3] != 3:
+        raise ValueError(f"frames: (T, H, W, 3), got {tuple(f.shape)}")
+    if f.shape[1] % 2 or f.shape[2] % 2 or f.shape[1] == 0 or f.shape[2] == 0:
+        raise ValueError(f"frames: {f.shape[1]} x {f.shape[2]} frames have no packed 4:2:0 form (an odd or empty side)")
+    if hip:
+        from . import ops
+        on_device = f.is_cuda
+        dev = f.device if on_device else torch.device("cuda", torch.cuda.current_device())
+        out = ops.rgb_frames_to_yuv420(f.to(dev), fmt, "thwc", matrix, range, siting)
+        return out if on_device else out.cpu().numpy()
+    packed = datasets.pack_yuv420(*datasets.rgb8_to_yuv420(f.cpu(), matrix, range, siting), fmt)
+    return packed if is_tensor else packed.numpy()

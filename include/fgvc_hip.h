@@ -424,6 +424,31 @@ int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t
                                int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy, float crv,
                                float cgu, float cgv, float cbu, int siting, uint8_t* out, void* stream);
 
+/* ---- The output stage for 8-bit YUV 4:2:0 video, the mirror image of fgvc_frames_yuv420_to_rgb8: RGB bytes -> Y'CbCr
+ * planes in one launch for all T frames; per frame what datasets.rgb8_to_yuv420 defines, byte for byte.
+ *   frames [T][h0][w0][3] bytes by four BYTE strides (frame, row, pixel, channel): packed pixels are (.., .., 3, 1), planar frames
+ *           (.., w0, 1, h0 w0); a time slice or a cropped window is read in place.
+ *   y [T][h0][w0] by two strides (frame, row; columns adjacent); u, v [T][ch][cw], ch = (h0 + 1) / 2, cw = (w0 + 1) / 2, by three strides
+ *           (frame, row, pixel), the same for both: pixel stride 1 for I420's planes, 2 for NV12's pairs (v = u + 1; NV21: u = v + 1).
+ *   Every f32 operation rounded, none fused, all values on the 0..255 scale; lum(R, G, B) = (kr R + kg G) + kb B:
+ *           Y = y_off + sy lum(R, G, B) at every pixel;
+ *           chroma sample (j, i) from the R, G, B bytes filtered first (exact: eighths on bytes) over the rows 2 j and min(2 j + 1, h0 - 1) --
+ *           FGVC_YUV_SITING_CENTER: columns 2 i and min(2 i + 1, w0 - 1), the four added and x 0.25; FGVC_YUV_SITING_LEFT: columns
+ *           max(2 i - 1, 0), 2 i, min(2 i + 1, w0 - 1) with weights 1, 2, 1, the two rows added and x 0.125 --
+ *           L = lum(Rm, Gm, Bm), U = 128 + cu (Bm - L), V = 128 + cv (Rm - L);
+ *           each byte rint (half to even) of the value clamped to [0, 255].
+ *           The seven coefficients come by value (ops.rgb_to_yuv_coefficients computes them in double and rounds once).
+ * The outputs must not overlap the frames or each other.  With T = 0 nothing is launched.  FGVC_ERR_INVALID_ARG for a null pointer, T < 0, a
+ * non-positive size, a siting other than the two, output rows, samples or frames that overlap by their strides, and a shape beyond the launch
+ * grid (T <= 65535, rows <= 65535 fgvc_yuv_out_tile_rows(), columns < 2^30) -- all before any launch.  No workspace, no atomics, no LDS.  The
+ * two tile functions give the luma rows and columns one workgroup owns (tests place shapes one past them). */
+int fgvc_frames_rgb8_to_yuv420(const uint8_t* frames, int T, int h0, int w0, int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                               int64_t stride_c, uint8_t* y, int64_t y_stride_t, int64_t y_stride_y, uint8_t* u, uint8_t* v,
+                               int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float kr, float kg, float kb, float y_off, float sy,
+                               float cu, float cv, int siting, void* stream);
+int fgvc_yuv_out_tile_rows(void);
+int fgvc_yuv_out_tile_cols(void);
+
 /* ---- DAVIS J&F on the device: the integer pixel counts that metrics.db_eval_iou and metrics.f_measure divide.
  *   gt, pred [T][h][w] uint8 object ids, 0 = background.  For object o = 1 .. n_objects: G = (gt == o), S = (pred == o); an id above
  *           n_objects belongs to no object (metrics.davis_masks_to_objects).

@@ -8,6 +8,7 @@ mediapy: frames come and go through PIL).
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
     python tools/demo.py CLIP.y4m --task points --query-points t x y ... [--yuv-matrix bt601|bt709] --out OUT
+    python tools/demo.py CLIP.y4m --task points --query-points t x y ... --out OUT --out-video OUT.y4m [--out-matrix bt601|bt709] [--out-range limited|full]
 
 FRAMES_DIR holds the clip's frames as JPEG / PNG files, taken in name order.  The frames go to the model as they are decoded -- uint8 RGB, on
 the device -- through test_cfg.input = dict(type='rgb8'); the mask task keeps its id maps on the device
@@ -18,6 +19,12 @@ fgvc_amd.viz.flow_to_rgb on the host, flow_%05d.png.
 CLIP.y4m (what `ffmpeg -i clip.mp4 clip.y4m` writes: uncompressed 8-bit 4:2:0) goes to the model as the file holds it -- packed I420, through
 test_cfg.input = dict(type='i420', ...) with the file's chroma siting and range -- and is painted on
 ops.yuv_frames_to_rgb8's bytes.  A Y4M file does not say which matrix made its YUV: --yuv-matrix, by default bt709 from 720 rows up, else bt601.
+--out-video OUT.y4m also writes the result as video, for all three tasks (for --task flow the coloured flow frames): the painted frames go
+through fgvc_amd.viz.frames_to_yuv420 -- one launch of fgvc_frames_rgb8_to_yuv420 on the device unless --host-render is given (DESIGN.md
+section 20) -- and only the packed I420 frames, 1.5 bytes a pixel, cross to the host, where datasets.write_y4m writes them with the clip's frame
+rate: `ffmpeg -i OUT.y4m out.mp4` takes the file.  Matrix, range and chroma siting are those the clip was decoded with for a .y4m input, else
+yuv_matrix_default(height), 'limited' and 'left'; --out-matrix and --out-range override.  A Y4M header has no matrix tag: the printed line says
+which one was used.  Frames with an odd side are refused (Y4M 4:2:0 has no odd form).
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -82,6 +89,7 @@ def load_y4m(a, dev):
     matrix = a.yuv_matrix or yuv_matrix_default(info["height"])
     print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, siting {info['siting']}, {info['range']} range; matrix {matrix} "
           f"({'--yuv-matrix' if a.yuv_matrix else 'by the height: the file does not say'})")
+    a.yuv_info = dict(info, matrix=matrix)
     packed = packed.to(dev)
     kw = dict(matrix=matrix, range=info["range"], siting=info["siting"])
     rgb = ops.yuv_frames_to_rgb8(*ops.yuv420_planes(packed, "i420"), **kw)
@@ -165,9 +173,9 @@ def run_flow(a, frames: np.ndarray, dev) -> dict:
         return model(test_mode=True, imgs=_raw(a, frames, dev)[None, None])
 
 
-def write_flow(out_dir: str, out: dict) -> int:
+def write_flow(out_dir: str, out: dict) -> np.ndarray:
     """flow_%05d.flo (Middlebury) and flow_%05d.png (viz.flow_to_rgb, one colour scale for the clip) of the forward flow; with a check,
-    occ_%05d.png (white = consistent)."""
+    occ_%05d.png (white = consistent).  -> the coloured frames (n, H, W, 3) uint8."""
     from PIL import Image
     from fgvc_amd import datasets
     os.makedirs(out_dir, exist_ok=True)
@@ -178,7 +186,7 @@ def write_flow(out_dir: str, out: dict) -> int:
         Image.fromarray(rgb[t]).save(os.path.join(out_dir, f"flow_{t:05d}.png"))
         if "occ_fw" in out:
             Image.fromarray((out["occ_fw"][t, 0].cpu().numpy() * 255).astype(np.uint8)).save(os.path.join(out_dir, f"occ_{t:05d}.png"))
-    return fw.shape[0]
+    return rgb
 
 
 def write(out_dir: str, rendered: np.ndarray, fps: float):
@@ -188,6 +196,44 @@ def write(out_dir: str, rendered: np.ndarray, fps: float):
     for t, im in enumerate(images):
         im.save(os.path.join(out_dir, f"frame_{t:05d}.png"))
     images[0].save(os.path.join(out_dir, "demo.gif"), save_all=True, append_images=images[1:], duration=int(round(1000.0 / fps)), loop=0)
+
+
+def video_settings(a, height: int) -> dict:
+    """How --out-video encodes: dict(matrix, range, siting, fps=(num, den)).  A .y4m input hands on the matrix it was decoded with, its range,
+    its chroma siting and its frame rate; anything else gets yuv_matrix_default(height), 'limited', 'left' and --fps.  --out-matrix and
+    --out-range override."""
+    from fractions import Fraction
+    info = getattr(a, "yuv_info", None) or {}
+    fps = tuple(info.get("fps", (0, 0)))
+    if fps[0] <= 0 or fps[1] <= 0:                                        # (a Y4M header may leave the rate out)
+        fr = Fraction(a.fps).limit_denominator(1001)
+        fps = (fr.numerator, fr.denominator)
+    return dict(matrix=a.out_matrix or info.get("matrix") or yuv_matrix_default(height), range=a.out_range or info.get("range", "limited"),
+                siting=info.get("siting", "left"), fps=fps)
+
+
+def check_video_size(height: int, width: int) -> None:
+    if height % 2 or width % 2:
+        raise ValueError(f"--out-video: {height} x {width} frames have an odd side, and Y4M 4:2:0 has no odd form; crop or pad the clip to even sides")
+
+
+def write_video(path: str, rendered, settings: dict, dev, host: bool = False) -> torch.Tensor:
+    """The painted frames (T, H, W, 3) uint8 (numpy or a tensor on either device) -> a Y4M file of 8-bit 4:2:0 frames.  Encoded on `dev` by
+    fgvc_frames_rgb8_to_yuv420 (frames already there stay there: only the packed frames come to the host), or with host=True by
+    datasets.rgb8_to_yuv420 on the CPU -- the same bytes.  -> the packed I420 frames (T, 3 H / 2, W) as written, a CPU tensor."""
+    from fgvc_amd import datasets
+    kw = dict(matrix=settings["matrix"], range=settings["range"], siting=settings["siting"])
+    f = rendered if isinstance(rendered, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rendered))
+    check_video_size(f.shape[1], f.shape[2])
+    if host:
+        packed = viz.frames_to_yuv420(f.cpu(), "i420", backend="host", **kw)
+    else:
+        packed = viz.frames_to_yuv420(f.to(dev), "i420", backend="hip", **kw).cpu()
+    datasets.write_y4m(path, packed, fps=settings["fps"], siting=kw["siting"], range=kw["range"])
+    print(f"{path}: {packed.shape[0]} frames of {f.shape[1]} x {f.shape[2]} as 8-bit 4:2:0 ({'host' if host else 'hip'} encoder), matrix {kw['matrix']}, "
+          f"{kw['range']} range, siting {kw['siting']}, {settings['fps'][0]}:{settings['fps'][1]} fps -- the Y4M header has no matrix tag: tell the "
+          f"next tool (ffmpeg: -colorspace {'bt709' if kw['matrix'] == 'bt709' else 'smpte170m'})")
+    return packed
 
 
 def parse_args(argv=None):
@@ -205,7 +251,11 @@ def parse_args(argv=None):
     ap.add_argument("--query-points", type=float, nargs="+", default=[], metavar="V", help="t x y [t x y ...], pixels of the clip")
     ap.add_argument("--first-mask", help="PNG of object ids for frame 0 (--task vos)")
     ap.add_argument("--out", required=True)
-    ap.add_argument("--host-render", action="store_true", help="paint with viz's numpy backend instead of the kernel")
+    ap.add_argument("--host-render", action="store_true", help="paint (and, with --out-video, encode) with viz's numpy backend instead of the kernels")
+    ap.add_argument("--out-video", default=None, metavar="OUT.y4m", help="also write the result as a YUV4MPEG2 file of 8-bit 4:2:0 frames")
+    ap.add_argument("--out-matrix", choices=("bt601", "bt709"), default=None,
+                    help="the matrix of --out-video; default: the one a .y4m clip was decoded with, else bt709 from 720 rows up, else bt601")
+    ap.add_argument("--out-range", choices=("limited", "full"), default=None, help="the range of --out-video; default: a .y4m clip's own, else limited")
     ap.add_argument("--size", type=int, nargs=2, metavar=("h", "w"), help="run the points model at this size")
     ap.add_argument("--radius", type=int, default=None)
     ap.add_argument("--alpha", type=int, default=128)
@@ -228,6 +278,8 @@ def parse_args(argv=None):
         ap.error("--task vos needs --first-mask")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
         ap.error("--yuv-matrix goes with a .y4m clip")
+    if (a.out_matrix or a.out_range) and not a.out_video:
+        ap.error("--out-matrix and --out-range go with --out-video")
     return a
 
 
@@ -236,15 +288,21 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise RuntimeError("tools/demo.py runs the model on the GPU (fgvc_amd has no CPU path)")
     dev = torch.device("cuda:0")
-    a.yuv_packed = a.yuv_input = None
+    a.yuv_packed = a.yuv_input = a.yuv_info = None
     if is_y4m(a.frames):
         a.yuv_packed, frames, a.yuv_input = load_y4m(a, dev)             # frames: the RGB bytes, on the device
     else:
         frames = synthetic_frames(*a.synthetic, seed=a.seed) if a.synthetic else load_frames(a.frames)
     tracks = visibles = ids = points = None
+    video = None
+    if a.out_video:
+        check_video_size(frames.shape[1], frames.shape[2])               # before the model runs
+        video = video_settings(a, frames.shape[1])
     if a.task == "flow":
-        n = write_flow(a.out, run_flow(a, frames, dev))
-        print(f"{a.out}: {n} flow fields of {frames.shape[1]} x {frames.shape[2]} as flow_%05d.flo and flow_%05d.png")
+        coloured = write_flow(a.out, run_flow(a, frames, dev))
+        print(f"{a.out}: {len(coloured)} flow fields of {frames.shape[1]} x {frames.shape[2]} as flow_%05d.flo and flow_%05d.png")
+        if video:
+            write_video(a.out_video, coloured, video, dev, host=a.host_render)
         return
     if a.task == "points":
         tracks, visibles, points = run_points(a, frames, dev)
@@ -254,13 +312,19 @@ def main(argv=None):
     if a.host_render:
         frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
         rendered = viz.render(frames, backend="host", **kw)
+        packed = write_video(a.out_video, rendered, video, dev, host=True) if video else None
     else:
         on_dev = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev)
-        rendered = viz.render(on_dev, backend="hip", **kw).cpu().numpy()
+        rendered = viz.render(on_dev, backend="hip", **kw)
+        packed = write_video(a.out_video, rendered, video, dev) if video else None       # render -> encode on the device
+        rendered = rendered.cpu().numpy()
     frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
     write(a.out, rendered, a.fps)
     print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}, {'host' if a.host_render else 'hip'} renderer)")
-    return dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
+    r = dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
+    if video:
+        r.update(video=packed.numpy(), video_settings=video)
+    return r
 
 
 if __name__ == "__main__":
