@@ -59,6 +59,9 @@ int render_frames_launch(const uint8_t*, long long, long long, uint8_t*, long lo
                          const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
                          int, const double*, hipStream_t);
 void render_tile(int*, int*);
+int render_trails_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
+                         const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
+                         int, const double*, int, int, double, double, const double*, const uint8_t*, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -791,6 +794,54 @@ int fgvc_render_frames_u8(const uint8_t* frames, int64_t frames_stride_t, int64_
   return render_frames_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
                               palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
                               visibles_stride_t, colors, P, radius, icon, (hipStream_t)stream);
+}
+
+int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                          int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                          const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                          int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                          const uint8_t* colors, int P, int radius, const double* icon, int trail, double linewidth, double ro2, double g,
+                          const double* fade, const uint8_t* time_colors, void* stream) {
+  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: negative size (T=%d, %d x %d)", T, h, w);
+  FGVC_REQUIRE(P >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: P=%d", P);
+  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
+  FGVC_REQUIRE(trail >= 1 && trail <= 64, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: trail=%d (1 .. 64)", trail);
+  FGVC_REQUIRE(linewidth >= 1.0 && linewidth <= 16.0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: linewidth=%g (1 .. 16)", linewidth);
+  FGVC_REQUIRE((long long)P * trail < (1ll << 30), FGVC_ERR_UNSUPPORTED, "fgvc_render_trails_u8: P * trail = %lld items, 2^30 or more",
+               (long long)P * trail);
+  if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
+  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: null pointer");
+  const long long row = 3ll * w;
+  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_trails_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
+  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_trails_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
+               (long long)out_stride_t, (long long)out_stride_y, h, w);
+  if (ids) {
+    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: ids without a palette");
+    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: alpha=%d (0 .. 256)", alpha);
+    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_trails_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
+  }
+  if (P > 0) {
+    FGVC_REQUIRE(tracks && fade, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: null tracks or fade table");
+    FGVC_REQUIRE(colors || (time_colors && !icon), FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: neither colors nor time_colors");
+    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: tracks: a negative frame stride (%lld)",
+                 (long long)tracks_stride_t);
+    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_trails_u8: visibles: a negative frame stride (%lld)", (long long)visibles_stride_t);
+    FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: ro2=%g, g=%g (both positive, ro2 <= 81)", ro2, g);
+    if (icon) {
+      FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: radius=%d (at least 1)", radius);
+      FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_trails_u8: radius=%d beyond 31", radius);
+    }
+    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon) | reinterpret_cast<uintptr_t>(fade)) & 7u) == 0,
+                 FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: tracks, icon and fade must be 8-byte aligned");
+  }
+  const int reach = (int)ceil(linewidth / 2.0 + 0.5);                 // ceil(ro): what a segment's box is grown by
+  return render_trails_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                              palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
+                              visibles_stride_t, colors, P, radius, icon, trail, reach, ro2, g, fade, time_colors, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

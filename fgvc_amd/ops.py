@@ -1771,6 +1771,11 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
     Frames, ids and `out` are read and written through their own frame and row strides (a time slice or a cropped window is not copied;
     pixels must be packed); tracks of another float type are converted to float64 first (exact).  `out`: a (T, H, W, 3) uint8 tensor to write
     into, `frames_u8` itself included; neither ids nor tracks: a copy."""
+    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, None)
+
+
+def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, trails):
+    """render_frames (trails None) and render_trails (trails = (L, linewidth, fade, time_colors, dots)): one set of checks, one launch."""
     from . import viz
     if not frames_u8.is_cuda:
         raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
@@ -1820,7 +1825,8 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
         if tracks.dtype == torch.bool or tracks.dtype.is_complex:
             raise TypeError(f"tracks: a real number type, got {tracks.dtype}")
         P = tracks.shape[0]
-        r = viz.check_radius(radius, H, W)
+        dots = trails is None or trails[4]
+        r = viz.check_radius(radius, H, W) if dots else 0
         tr = tracks.to(torch.float64)
         if tr.stride(2) != 1 or tr.data_ptr() % 8:
             tr = tr.contiguous()
@@ -1838,7 +1844,7 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
         if tuple(colors.shape) != (P, 3) or colors.device != dev:
             raise ValueError(f"colors: {(P, 3)} on {dev} to go with the tracks, got {tuple(colors.shape)} on {colors.device}")
         colors = colors.contiguous()
-        icon = _render_table(("icon", r), dev, lambda: viz.icon_table(r))
+        icon = _render_table(("icon", r), dev, lambda: viz.icon_table(r)) if dots else None
         args_pts = (tr, tr.stride(0), tr.stride(1), vis, 0 if vis is None else vis.stride(0), 0 if vis is None else vis.stride(1), colors, P, r,
                     icon)
     if T == 0 or H == 0 or W == 0:
@@ -1848,7 +1854,46 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
 
     def ptr(x):
         return None if x is None else _ptr(x)
-    _lib.call("fgvc_render_frames_u8", _ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W,
-              ptr(m), m_st, m_sy, ptr(pal), al, ct, ptr(tr), tr_sp, tr_st, ptr(vis), v_sp, v_st, ptr(col), int(P or 0), int(r or 0), ptr(icon),
-              _stream(f))
+    head = (_ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W, ptr(m), m_st, m_sy, ptr(pal), al, ct,
+            ptr(tr), tr_sp, tr_st, ptr(vis), v_sp, v_st, ptr(col), int(P or 0), int(r or 0), ptr(icon))
+    if trails is None:
+        _lib.call("fgvc_render_frames_u8", *head, _stream(f))
+        return out
+    L, lw, fade, tcol = trails[:4]
+    ro2, g, _ = viz.trail_consts(lw)
+    _lib.call("fgvc_render_trails_u8", *head, L, lw, ro2, g, _ptr(fade), ptr(tcol) if T > 1 else None, _stream(f))
     return out
+
+
+def render_trails(frames_u8: torch.Tensor, tracks: torch.Tensor, visibles: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None,
+                  trail: int = 8, linewidth: float = 2.0, fade: Optional[torch.Tensor] = None, time_colors: Optional[torch.Tensor] = None,
+                  ids: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, alpha: int = 128, contour: bool = True,
+                  radius: Optional[int] = None, dots: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """render_frames with motion trails: the overlay, then every point's last `trail` (1 .. 64) steps as line segments
+    `linewidth` (1 .. 16) pixels wide, then (dots=True) the dots -- viz.render(trail=...)'s host backend bit for bit, in one launch of
+    fgvc_render_trails_u8 on the current stream.  fade: (trail,) float64 in [0, 1] on the frames' device, the opacity by age (None:
+    viz.trail_fade(trail)); time_colors: (T - 1, 3) uint8, the colour of step s (viz.spring_colors(T) is the reference's), None: the point's
+    own `colors`.  Every other argument is render_frames'; with dots=False `radius` is not used."""
+    from . import viz
+    if tracks is None:
+        raise ValueError("tracks: (P, T, 2), got None (trails need tracks)")
+    dev = frames_u8.device
+    L, lw, _ = viz._check_trails(trail, linewidth, None, "track")
+    if fade is None:
+        fade = _render_table(("fade", L), dev, lambda: viz.trail_fade(L))
+    else:
+        if not isinstance(fade, torch.Tensor) or fade.device != dev:
+            raise ValueError(f"fade: a tensor on {dev} with the frames")
+        if fade.dtype.is_complex or fade.dtype == torch.bool or tuple(fade.shape) != (L,):
+            raise ValueError(f"fade: ({L},) real numbers to go with trail={L}, got {fade.dtype} {tuple(fade.shape)}")
+        fade = fade.to(torch.float64).contiguous()
+        if not bool(((fade >= 0) & (fade <= 1)).all()):
+            raise ValueError("fade: values in [0, 1]")
+    if time_colors is not None:
+        T = frames_u8.shape[0] if frames_u8.dim() == 4 else 0
+        if time_colors.dtype != torch.uint8:
+            raise TypeError(f"time_colors: expected torch.uint8, got {time_colors.dtype}")
+        if tuple(time_colors.shape) != (max(T - 1, 0), 3) or time_colors.device != dev:
+            raise ValueError(f"time_colors: {(max(T - 1, 0), 3)} on {dev}, got {tuple(time_colors.shape)} on {time_colors.device}")
+        time_colors = time_colors.contiguous()
+    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, (L, lw, fade, time_colors, bool(dots)))

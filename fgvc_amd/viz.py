@@ -2,7 +2,8 @@
 
     paint_point_track(frames, point_tracks, visibles, colors)    the reference's dot painter (flyingthingsplus/utils/visualize.py:85-155)
     overlay_masks(frames, ids, palette, alpha, contour)          object ids blended in, integer arithmetic, optional contour
-    render(frames, ids=..., tracks=..., visibles=...)            overlay, then points
+    render(frames, ids=..., tracks=..., visibles=...)            overlay, then points; with trail=L: overlay, trails, points
+    paint_trails(frames, point_tracks, visibles, trail=8)        every point's last L steps as a fading poly-line
     frames_to_yuv420(frames, fmt, matrix, range, siting)         the painted frames as packed 8-bit 4:2:0 video
 
 backend='host' is plain numpy: it is the contract, the default, and works without a GPU.  backend='hip' is ONE launch of
@@ -15,6 +16,17 @@ fgvc_render_frames_u8 (ops.render_frames) and is held to the host backend with `
               patch = I(a, b) (x2 - x) (y2 - y) + I(a - 1, b) (x2 - x) (y - y1) + I(a, b - 1) (x - x1) (y2 - y) + I(a - 1, b - 1) (x - x1) (y - y1)
               v_c   = (1 - patch) v_c + patch colour[i][c], truncated to uint8 -- after EVERY point, as the reference's assignment into its
             uint8 image does; float64 throughout, each product left to right.  A point with a non-finite coordinate is skipped.
+  trails    (trail=L; between the overlay and the points; backend='hip': ONE launch of fgvc_render_trails_u8, ops.render_trails)  on frame t,
+            for every point i in index order and every step s = max(0, t - L) .. t - 1, oldest first: the segment from A = track[i, s] + 0.5
+            to B = track[i, s + 1] + 0.5 (pixel (px, py) is the point (px, py); the + 0.5 is the dots' own shift), drawn only if both ends
+            are visible and all four coordinates are below 2**20 in magnitude (NaN and the infinities are not); ends are not clamped.
+            With d = B - A, L2 = dx dx + dy dy, ro = linewidth / 2 + 0.5, ri = max(linewidth / 2 - 0.5, 0), ro2 = ro ro, g = 1 / (ro2 - ri ri):
+              u   = 0 if L2 == 0 else min(max(((px - ax) dx + (py - ay) dy) / L2, 0), 1)
+              ex  = px - (ax + u dx), ey = py - (ay + u dy), d2 = ex ex + ey ey
+              cov = min(max((ro2 - d2) g, 0), 1), op = cov fade[t - 1 - s]
+              v_c = (1 - op) v_c + op colour_c, truncated to uint8 after EVERY segment; cov <= 0: the pixel keeps its value
+            float64, every product and sum left to right, no square root, one (correctly rounded) division.  Not OpenCV's LINE_AA rasteriser
+            (the reference's draw_traj_on_image_py), whose bytes nothing here can pin; the joint of two consecutive segments is blended twice.
 Tracks are (x, y) in the pixel frame of `frames` (scale_tracks for tracks predicted at another size) and are converted to float64 first.
 """
 from __future__ import annotations
@@ -27,6 +39,10 @@ import numpy as np
 
 BACKENDS = ("host", "hip")
 MAX_RADIUS = 31
+MAX_TRAIL = 64
+LINEWIDTHS = (1.0, 16.0)
+TRAIL_LIMIT = float(2 ** 20)    # a segment with a coordinate at or beyond it (or NaN) is not drawn
+TRAIL_COLOR_BY = ("track", "time")
 DOT_FRACTION = 0.015          # the reference's dot_size_as_fraction_of_min_edge
 SHARPNESS = 0.15
 
@@ -93,6 +109,42 @@ def _icon_table(radius: int) -> np.ndarray:
 def icon_table(radius: int) -> np.ndarray:
     """(2 r + 1, 2 r + 1) float64, read-only: the dot's opacity."""
     return _icon_table(int(radius))
+
+@functools.lru_cache(maxsize=None)
+def _trail_fade(length: int) -> np.ndarray:
+    L = int(length)
+    fade = (L - np.arange(L, dtype=np.float64)) / L
+    fade.setflags(write=False)
+    return fade
+
+
+def trail_fade(length: int) -> np.ndarray:
+    """(L,) float64, read-only: the default opacity of a trail segment by its age in frames, (L - age) / L -- 1 for the newest step."""
+    L = int(length)
+    if not 1 <= L <= MAX_TRAIL:
+        raise ValueError(f"trail={length!r}: an integer in 1 .. {MAX_TRAIL}")
+    return _trail_fade(L)
+
+
+def spring_colors(num_frames: int) -> np.ndarray:
+    """(T - 1, 3) uint8: the colour of step s by time, matplotlib's 'spring' map through its 256-entry table as the reference's trajectory
+    drawing samples it (improc.py draw_traj_on_image_py): (255, k, 255 - k) with k = min(int(s / max(1, T - 2) * 256), 255)."""
+    T = int(num_frames)
+    out = np.zeros((max(T - 1, 0), 3), np.uint8)
+    for s in range(T - 1):
+        k = min(int(s / max(1, T - 2) * 256), 255)
+        out[s] = (255, k, 255 - k)
+    return out
+
+
+def trail_consts(linewidth: float):
+    """(ro2, g, reach) of a line width: the two doubles of the coverage ramp, made ONCE here for both backends, and ceil(ro), what a
+    segment's box is grown by."""
+    lw = float(linewidth)
+    ro = lw / 2 + 0.5
+    ri = max(lw / 2 - 0.5, 0.0)
+    ro2 = ro * ro
+    return ro2, 1.0 / (ro2 - ri * ri), int(np.ceil(ro))
 
 
 def scale_tracks(tracks, from_size: Tuple[int, int], to_size: Tuple[int, int]) -> np.ndarray:
@@ -167,6 +219,32 @@ def _check_points(frames, tracks, visibles, colors, radius):
         raise ValueError("colors: integers in 0 .. 255")
     return tracks, visibles, colors.astype(np.uint8), check_radius(radius, H, W)
 
+def _check_trails(trail, linewidth, fade, color_by):
+    """-> (L, linewidth, fade (L,) float64)"""
+    if isinstance(trail, (bool, np.bool_)) or not isinstance(trail, (int, np.integer)) or not 1 <= int(trail) <= MAX_TRAIL:
+        raise ValueError(f"trail={trail!r}: an integer in 1 .. {MAX_TRAIL}")
+    L = int(trail)
+    try:
+        lw = float(linewidth)
+    except (TypeError, ValueError):
+        raise ValueError(f"linewidth={linewidth!r}: a number in {list(LINEWIDTHS)}") from None
+    if not LINEWIDTHS[0] <= lw <= LINEWIDTHS[1]:
+        raise ValueError(f"linewidth={linewidth!r}: a number in {list(LINEWIDTHS)}")
+    if color_by not in TRAIL_COLOR_BY:
+        raise ValueError(f"trail_color_by={color_by!r}: one of {TRAIL_COLOR_BY}")
+    if fade is None:
+        fade = _trail_fade(L)
+    else:
+        fade = np.asarray(_numpy(fade))
+        if fade.dtype.kind not in "fiu":
+            raise ValueError(f"trail_fade: ({L},) real numbers in [0, 1], got {fade.dtype}")
+        fade = np.ascontiguousarray(fade, dtype=np.float64)
+        if fade.shape != (L,):
+            raise ValueError(f"trail_fade: ({L},) to go with trail={L}, got {fade.shape}")
+        if not bool(((fade >= 0.0) & (fade <= 1.0)).all()):
+            raise ValueError("trail_fade: values in [0, 1]")
+    return L, lw, fade
+
 
 def _backend(backend: str) -> bool:
     """True for 'hip' (after its refusal), False for 'host'."""
@@ -227,17 +305,64 @@ def _paint_host(video, tracks, visibles, colors, radius):
     return video
 
 
+def _trails_host(video, t, tracks, visibles, colors, L, ro2, g, reach, fade, time_colors):
+    """Frame t's trails into video[t] (H, W, 3) uint8: the module text's rule, a segment at a time on the part of its box (grown by
+    ceil(ro): outside it cov is exactly 0) inside the image."""
+    image = video[t]
+    H, W = image.shape[:2]
+    s0 = max(0, t - L)
+    if s0 >= t or tracks.shape[0] == 0:
+        return
+    with np.errstate(invalid="ignore"):
+        ok = visibles[:, s0:t + 1] & (np.abs(tracks[:, s0:t + 1]) < TRAIL_LIMIT).all(-1)
+    for i, k in np.argwhere(ok[:, :-1] & ok[:, 1:]):                                   # in point order, oldest step first
+        s = s0 + int(k)
+        ax, ay = tracks[i, s] + 0.5
+        bx, by = tracks[i, s + 1] + 0.5
+        x_lo, x_hi = max(int(np.floor(min(ax, bx))) - reach, 0), min(int(np.ceil(max(ax, bx))) + reach, W - 1)
+        y_lo, y_hi = max(int(np.floor(min(ay, by))) - reach, 0), min(int(np.ceil(max(ay, by))) + reach, H - 1)
+        if x_lo > x_hi or y_lo > y_hi:
+            continue
+        px = np.arange(x_lo, x_hi + 1, dtype=np.float64)[np.newaxis, :]
+        py = np.arange(y_lo, y_hi + 1, dtype=np.float64)[:, np.newaxis]
+        dx, dy = bx - ax, by - ay
+        L2 = dx * dx + dy * dy
+        u = 0.0 if L2 == 0 else np.minimum(np.maximum(((px - ax) * dx + (py - ay) * dy) / L2, 0.0), 1.0)
+        ex, ey = px - (ax + u * dx), py - (ay + u * dy)
+        d2 = ex * ex + ey * ey
+        cov = np.minimum(np.maximum((ro2 - d2) * g, 0.0), 1.0)
+        op = (cov * fade[t - 1 - s])[:, :, np.newaxis]
+        col = (time_colors[s] if time_colors is not None else colors[i]).astype(np.float64)[np.newaxis, np.newaxis, :]
+        ys, xs = slice(y_lo, y_hi + 1), slice(x_lo, x_hi + 1)
+        image[ys, xs] = ((1 - op) * image[ys, xs] + op * col).astype(np.uint8)
+
+
 # ---- the public functions -----------------------------------------------------------------------------------------------------------------
 def render(frames, ids=None, tracks=None, visibles=None, colors=None, palette=None, alpha: int = 128, contour: bool = True,
-           radius: Optional[int] = None, backend: str = "host"):
+           radius: Optional[int] = None, backend: str = "host", *, trail: Optional[int] = None, linewidth: float = 2.0, trail_fade=None,
+           trail_color_by: str = "track"):
     """Overlay (when `ids` is given), then points (when `tracks` is given) onto frames (T, H, W, 3) uint8; neither: a copy.  ids (T, H, W)
     uint8, palette (256, 3) uint8 (None: davis_palette()), alpha 0 .. 256; tracks (P, T, 2) as (x, y), visibles (P, T) bool (None: all),
     colors (P, 3) integers 0 .. 255 (None: track_colors(P)), radius 1 .. 31 (None: the reference's round(min(H, W) * 0.015)).
+    trail=L (1 .. 64, needs tracks; None: no trails): between the overlay and the points, every point's last L steps as line segments
+    `linewidth` (1 .. 16) pixels wide, of opacity trail_fade[age] ((L,) in [0, 1]; None: trail_fade(L)), in the point's colour
+    (trail_color_by='track') or the step's (='time': spring_colors(T)) -- the module text has the rule.
     backend='hip': numpy arrays or CUDA tensors, one launch; returns a CUDA uint8 tensor when `frames` is one, numpy otherwise."""
+    return _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, trail_fade,
+                   trail_color_by, True)
+
+
+def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, fade, color_by, dots):
     hip = _backend(backend)
     on_device = hip and _is_cuda(frames)
+    trails = None
+    if trail is not None:
+        if tracks is None:
+            raise ValueError("trail: needs tracks (P, T, 2), got None")
+        L, lw, fd = _check_trails(trail, linewidth, fade, color_by)
+        trails = dict(L=L, linewidth=lw, fade=fd, by_time=color_by == "time", dots=bool(dots))
     if hip:
-        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device)
+        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails)
     f = _numpy(frames)
     _check_frames(f)
     out = f.copy()
@@ -246,12 +371,20 @@ def render(frames, ids=None, tracks=None, visibles=None, colors=None, palette=No
         pal, a = _check_overlay(f, m, _numpy(palette), alpha)
         out = _overlay_host(out, m, pal, a, bool(contour))
     if tracks is not None:
-        tr, vis, col, r = _check_points(f, _numpy(tracks), _numpy(visibles), _numpy(colors), radius)
-        out = _paint_host(np.ascontiguousarray(out), tr, vis, col, r)
+        with_dots = trails is None or trails["dots"]
+        tr, vis, col, r = _check_points(f, _numpy(tracks), _numpy(visibles), _numpy(colors), radius if with_dots else 1)
+        out = np.ascontiguousarray(out)
+        if trails is not None:
+            ro2, g, reach = trail_consts(trails["linewidth"])
+            tcol = spring_colors(f.shape[0]) if trails["by_time"] else None
+            for t in range(f.shape[0]):
+                _trails_host(out, t, tr, vis, col, trails["L"], ro2, g, reach, trails["fade"], tcol)
+        if with_dots:
+            out = _paint_host(out, tr, vis, col, r)
     return out
 
 
-def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device):
+def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails=None):
     import torch
     from . import ops
     dev = frames.device if on_device else torch.device("cuda", torch.cuda.current_device())
@@ -280,8 +413,25 @@ def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, 
                 raise ValueError("colors: integers in 0 .. 255")
             col = up(c.astype(np.uint8))
         kw.update(tracks=up(tr, torch.float64), visibles=up(visibles), colors=col, radius=radius)
-    out = ops.render_frames(f, **kw)
+    if trails is not None:
+        tcol = up(spring_colors(f.shape[0])) if trails["by_time"] and f.dim() == 4 else None
+        out = ops.render_trails(f, trail=trails["L"], linewidth=trails["linewidth"], fade=up(trails["fade"]), time_colors=tcol,
+                                dots=trails["dots"], **kw)
+    else:
+        out = ops.render_frames(f, **kw)
     return out if on_device else out.cpu().numpy()
+
+
+def paint_trails(frames, point_tracks, visibles=None, colors=None, trail: int = 8, linewidth: float = 2.0, fade=None, color_by: str = "track",
+                 dots: bool = True, radius: Optional[int] = None, backend: str = "host"):
+    """frames (T, H, W, 3) uint8 with every point's last `trail` steps drawn as a fading poly-line (see render and the module text) and,
+    with dots=True, the dots of paint_point_track on top.  What the reference's second demo video shows (Summ_writer.summ_traj2ds_on_rgbs);
+    color_by='time' is its colouring."""
+    if point_tracks is None:
+        raise ValueError("point_tracks: (P, T, 2), got None")
+    if trail is None:
+        raise ValueError("trail=None: an integer in 1 .. 64 (paint_point_track draws the dots alone)")
+    return _render(frames, None, point_tracks, visibles, colors, None, 128, True, radius, backend, trail, linewidth, fade, color_by, dots)
 
 
 def paint_point_track(frames, point_tracks, visibles, colors=None, radius: Optional[int] = None, backend: str = "host"):

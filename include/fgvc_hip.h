@@ -491,6 +491,29 @@ int fgvc_render_frames_u8(const uint8_t* frames, int64_t frames_stride_t, int64_
 int fgvc_render_tile_rows(void);
 int fgvc_render_tile_cols(void);
 
+/* ---- Motion trails: the renderer above with every point's last `trail` steps drawn as anti-aliased line segments
+ * between the overlay and the dots, still one launch; fgvc_amd/viz.py's host backend bit for bit.  Every argument up to `icon` is the
+ * renderer's, except: tracks must not be null when P > 0, and icon == null leaves the dots out (radius is then ignored).
+ *   trail   L, 1 .. 64.  On frame t point i has the segments s = max(0, t - L) .. t - 1, drawn oldest first, points in index order;
+ *           segment s joins A = tracks[i][s] + 0.5 and B = tracks[i][s + 1] + 0.5 (pixel (px, py) is the point (px, py)) and is drawn only
+ *           if both ends are visible and all four track coordinates are below 2^20 in magnitude (NaN and the infinities are not).
+ *           Ends are not clamped to the image.
+ *   linewidth 1 .. 16; ro2 = ro ro and g = 1 / (ro2 - ri ri) with ro = linewidth / 2 + 0.5, ri = max(linewidth / 2 - 0.5, 0), made once by
+ *           the caller (viz.trail_consts) so that both backends use the same two doubles.
+ *   fade    [trail] float64 in [0, 1], by age t - 1 - s;  time_colors [T - 1][3] uint8, the colour of segment s, or null: colors[i].
+ *           Per pixel, float64 without contraction, products and sums left to right, d = B - A, L2 = dx dx + dy dy:
+ *             u = 0 if L2 == 0 else min(max(((px - ax) dx + (py - ay) dy) / L2, 0), 1)
+ *             ex = px - (ax + u dx), ey = py - (ay + u dy), cov = min(max((ro2 - (ex ex + ey ey)) g, 0), 1), op = cov fade[t - 1 - s]
+ *             v_c = (1 - op) v_c + op colour_c, truncated towards zero to uint8 after every segment; cov <= 0: unchanged.
+ * Errors as the renderer's, and FGVC_ERR_INVALID_ARG for trail or linewidth out of range, a null fade table, neither colour table, negative
+ * frame strides of tracks or visibles, fade not 8-byte aligned; FGVC_ERR_UNSUPPORTED for P trail >= 2^30.  No workspace, no atomics. */
+int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                          int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                          const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                          int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                          const uint8_t* colors, int P, int radius, const double* icon, int trail, double linewidth, double ro2, double g,
+                          const double* fade, const uint8_t* time_colors, void* stream);
+
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage
  *                             (fgvc_pair_topk_f32 with topk=1 on the coarse features)

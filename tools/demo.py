@@ -6,6 +6,7 @@ mediapy: frames come and go through PIL).
     python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
+    python tools/demo.py FRAMES_DIR --task points --query-points t x y ... --trails [L] [--trail-width X] [--trail-color track|time] --out OUT
     python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
     python tools/demo.py CLIP.y4m --task points --query-points t x y ... [--yuv-matrix bt601|bt709] --out OUT
     python tools/demo.py CLIP.y4m --task points --query-points t x y ... --out OUT --out-video OUT.y4m [--out-matrix bt601|bt709] [--out-range limited|full]
@@ -25,6 +26,10 @@ section 20) -- and only the packed I420 frames, 1.5 bytes a pixel, cross to the 
 rate: `ffmpeg -i OUT.y4m out.mp4` takes the file.  Matrix, range and chroma siting are those the clip was decoded with for a .y4m input, else
 yuv_matrix_default(height), 'limited' and 'left'; --out-matrix and --out-range override.  A Y4M header has no matrix tag: the printed line says
 which one was used.  Frames with an odd side are refused (Y4M 4:2:0 has no odd form).
+--trails [L] (--task points; L = 8 when left out) also draws every point's last L steps as a fading poly-line under the dots, what the reference
+demo's second video shows: viz.render(trail=L), still one launch (fgvc_render_trails_u8).  --trail-width is the line
+width in pixels, --trail-color time the reference's colouring by time in place of the point's own colour.  It goes with --chain (a trail stops
+where a chained track ends or is not visible), with --out-video and with --host-render.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -258,6 +263,11 @@ def parse_args(argv=None):
     ap.add_argument("--out-range", choices=("limited", "full"), default=None, help="the range of --out-video; default: a .y4m clip's own, else limited")
     ap.add_argument("--size", type=int, nargs=2, metavar=("h", "w"), help="run the points model at this size")
     ap.add_argument("--radius", type=int, default=None)
+    ap.add_argument("--trails", type=int, nargs="?", const=8, default=None, metavar="L",
+                    help="--task points: draw every point's last L steps (1 .. 64, 8 when L is left out) as a fading line under the dots")
+    ap.add_argument("--trail-width", type=float, default=2.0, metavar="X", help="with --trails: the line width in pixels (1 .. 16)")
+    ap.add_argument("--trail-color", choices=("track", "time"), default="track",
+                    help="with --trails: the point's own colour, or the reference's colouring by time ('spring')")
     ap.add_argument("--alpha", type=int, default=128)
     ap.add_argument("--no-contour", action="store_true")
     ap.add_argument("--fps", type=float, default=10.0)
@@ -278,6 +288,10 @@ def parse_args(argv=None):
         ap.error("--task vos needs --first-mask")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
         ap.error("--yuv-matrix goes with a .y4m clip")
+    if a.trails is not None and a.task != "points":
+        ap.error("--trails goes with --task points")
+    if a.trails is None and (a.trail_width != 2.0 or a.trail_color != "track"):
+        ap.error("--trail-width and --trail-color go with --trails")
     if (a.out_matrix or a.out_range) and not a.out_video:
         ap.error("--out-matrix and --out-range go with --out-video")
     return a
@@ -309,6 +323,8 @@ def main(argv=None):
     else:
         ids = run_vos(a, frames, dev)
     kw = dict(ids=ids, tracks=tracks, visibles=visibles, radius=a.radius, alpha=a.alpha, contour=not a.no_contour)
+    if a.trails is not None:
+        kw.update(trail=a.trails, linewidth=a.trail_width, trail_color_by=a.trail_color)
     if a.host_render:
         frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
         rendered = viz.render(frames, backend="host", **kw)
@@ -320,7 +336,8 @@ def main(argv=None):
         rendered = rendered.cpu().numpy()
     frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
     write(a.out, rendered, a.fps)
-    print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}, {'host' if a.host_render else 'hip'} renderer)")
+    print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}{'' if a.trails is None else f', trails of {a.trails}'}, "
+          f"{'host' if a.host_render else 'hip'} renderer)")
     r = dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
     if video:
         r.update(video=packed.numpy(), video_settings=video)
