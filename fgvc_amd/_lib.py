@@ -120,6 +120,9 @@ SIGNATURES = {
     "fgvc_seg_hard_onehot_f32": (_i, [_p, _i, _i, _p, _p]),
     "fgvc_seg_readout_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fgvc_seg_readout_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "fgvc_seg_label_set_u8": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_inject_labels_u8": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "fgvc_seg_readout_conf_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "fgvc_seg_soft_labels_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_seg_soft_labels_f64": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_heatmap_coords_workspace_bytes": (C.c_size_t, [_i, _i]),

@@ -151,6 +151,51 @@ __global__ __launch_bounds__(256) void seg_onehot_kernel(const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------
+// annotations at any frame: the 256-bit presence set of a map sampled to the feature grid (bit id of word id / 32), and the injection of
+// the cells whose sampled id is in a given set into a (HfWf, C) row block, in place
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void seg_label_set_kernel(const uint8_t* __restrict__ map, int hp, int wp, int Hf, int Wf,
+                                                            uint32_t* __restrict__ out) {
+  extern __shared__ int tab[];  // [Hf] rows | [Wf] columns
+  __shared__ uint32_t bits[8];
+  int* ry = tab;
+  int* rx = tab + Hf;
+  if (threadIdx.x == 0) pil_nearest_table(hp, Hf, ry);
+  if (threadIdx.x == 64) pil_nearest_table(wp, Wf, rx);
+  if (threadIdx.x >= 128 && threadIdx.x < 136) bits[threadIdx.x - 128] = 0u;
+  __syncthreads();
+  for (int i = threadIdx.x; i < Hf * Wf; i += 256) {
+    const int y = i / Wf, x = i - y * Wf;
+    const uint32_t id = map[(size_t)ry[y] * wp + rx[x]];
+    const uint32_t bit = 1u << (id & 31);
+    if (!(bits[id >> 5] & bit)) atomicOr(&bits[id >> 5], bit);
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) out[threadIdx.x] = bits[threadIdx.x];
+}
+
+// rows [Hf*Wf][C]: a cell whose sampled id is in `set` becomes one_hot(id, C) (an id >= C: a zero row, as seg_onehot_kernel); every
+// other cell is left alone
+__global__ __launch_bounds__(256) void seg_inject_kernel(const uint8_t* __restrict__ map, int hp, int wp, int Hf, int Wf, int C,
+                                                         const uint32_t* __restrict__ set, float* __restrict__ rows) {
+  extern __shared__ int tab[];
+  __shared__ uint32_t bits[8];
+  int* ry = tab;
+  int* rx = tab + Hf;
+  if (threadIdx.x == 0) pil_nearest_table(hp, Hf, ry);
+  if (threadIdx.x == 64) pil_nearest_table(wp, Wf, rx);
+  if (threadIdx.x >= 128 && threadIdx.x < 136) bits[threadIdx.x - 128] = set[threadIdx.x - 128];
+  __syncthreads();
+  const long long n = (long long)Hf * Wf * C;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const int pix = (int)(i / C), c = (int)(i - (long long)pix * C);
+    const int y = pix / Wf, x = pix - y * Wf;
+    const int id = (int)map[(size_t)ry[y] * wp + rx[x]];
+    if ((bits[id >> 5] >> (id & 31)) & 1u) rows[i] = id == c ? 1.f : 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // hard propagation: row r of `in` (rows, C) -> one_hot(argmax) in `out` (may alias `in`); the first maximum wins
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void seg_hard_onehot_kernel(const float* in, int rows, int C, float* out) {
@@ -223,62 +268,32 @@ __global__ __launch_bounds__(SEG_BLOCK) void seg_minmax_kernel(const float* __re
   }
 }
 
-// read-out phase 2: fold the slab into per-channel (min, max) in LDS, then per pixel normalise, argmax (first maximum wins) and
-// store SEG_PX index bytes per lane in one 4-byte store where the destination is aligned.
+// read-out phase 2 (seg_argmax_body.inc): fold the slab into per-channel (min, max) in LDS, then per pixel normalise, argmax (first
+// maximum wins) and store SEG_PX index bytes per lane in one 4-byte store where the destination is aligned.
+// seg_readout_conf_kernel is the same body with CONF: the runner-up value rides along in a second register per pixel, conf = rint(255 *
+// clamp(best - second, 0, 1)) goes out as a second byte plane (C == 1: second stays -inf, the byte is 255), each pixel adds (1, conf) to
+// its winner's slot of the LDS counters cnt[C] | sum[C] behind mm, and the workgroup adds its non-zero slots to stats [n][C][2] (zero on
+// entry) with 64-bit integer atomics: integer sums, so the result does not depend on the order.
+struct SegConfOut {
+  uint8_t* conf;
+  unsigned long long* stats;
+};
+
 template <bool COMPOSED>
 __global__ __launch_bounds__(SEG_BLOCK) void seg_argmax_kernel(const float* __restrict__ labels, ReadoutGeom g,
                                                                const float* __restrict__ part, int norm,
                                                                uint8_t* __restrict__ masks) {
-  extern __shared__ float mm[];  // [C][2]: min, max
-  const int f = blockIdx.y, C = g.C;
-  const int HW = g.h0 * g.w0;
-  const float* lab = labels + (size_t)f * g.Hf * g.Wf * C;
-  const float* src = part + (size_t)f * SEG_NB * C * 2;
-  for (int c = threadIdx.x; c < C; c += SEG_BLOCK) {
-    float mn = INFINITY, mx = -INFINITY;
-    for (int b = 0; b < SEG_NB; ++b) {
-      mn = fminf(mn, src[(b * C + c) * 2]);
-      mx = fmaxf(mx, src[(b * C + c) * 2 + 1]);
-    }
-    mm[2 * c] = mn;
-    mm[2 * c + 1] = mx;
-  }
-  __syncthreads();
-  const int p = blockIdx.x * SEG_CHUNK + threadIdx.x * SEG_PX;
-  if (p >= HW) return;
-  Taps<COMPOSED> ty[SEG_PX], tx[SEG_PX];
-  lane_taps<COMPOSED>(g, p, HW, ty, tx);
-  float best[SEG_PX];
-  int bi[SEG_PX];
-#pragma unroll
-  for (int k = 0; k < SEG_PX; ++k) {
-    best[k] = -INFINITY;
-    bi[k] = 0;
-  }
-  for (int c = 0; c < C; ++c) {
-    const float mn = mm[2 * c], mx = mm[2 * c + 1];
-    // torch.where(max > 0, (x - min) / (max - min + 1e-12), x)
-    const bool nrm = norm && mx > 0.f;
-    const float den = (mx - mn) + 1e-12f;
-#pragma unroll
-    for (int k = 0; k < SEG_PX; ++k) {
-      float v = field_value<COMPOSED>(lab + c, ty[k], tx[k]);
-      if (nrm) v = (v - mn) / den;
-      if (c == 0 || v > best[k]) {
-        best[k] = v;
-        bi[k] = c;
-      }
-    }
-  }
-  uint8_t* dst = masks + (size_t)f * HW + p;
-  if (p + SEG_PX <= HW && (reinterpret_cast<uintptr_t>(dst) & 3) == 0) {
-    const uint32_t word = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
-    *reinterpret_cast<uint32_t*>(dst) = word;
-  } else {
-#pragma unroll
-    for (int k = 0; k < SEG_PX; ++k)
-      if (p + k < HW) dst[k] = (uint8_t)bi[k];
-  }
+  constexpr bool CONF = false;
+  [[maybe_unused]] const SegConfOut extra{nullptr, nullptr};
+#include "seg_argmax_body.inc"
+}
+
+template <bool COMPOSED>
+__global__ __launch_bounds__(SEG_BLOCK) void seg_readout_conf_kernel(const float* __restrict__ labels, ReadoutGeom g,
+                                                                     const float* __restrict__ part, int norm,
+                                                                     uint8_t* __restrict__ masks, SegConfOut extra) {
+  constexpr bool CONF = true;
+#include "seg_argmax_body.inc"
 }
 
 size_t seg_readout_workspace_bytes(int n, int C) { return (size_t)n * SEG_NB * C * 2 * sizeof(float); }
@@ -732,6 +747,29 @@ int fgvc_seg_onehot_labels_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf
   return FGVC_OK;
 }
 
+int fgvc_seg_label_set_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, uint32_t* out, void* stream) {
+  FGVC_REQUIRE(map && out, FGVC_ERR_INVALID_ARG, "fgvc_seg_label_set_u8: null pointer");
+  FGVC_REQUIRE(hp > 0 && wp > 0 && Hf > 0 && Wf > 0, FGVC_ERR_INVALID_ARG, "fgvc_seg_label_set_u8: bad shape");
+  FGVC_REQUIRE(Hf + Wf <= SEG_MAX_TABLE - 8 && (long long)Hf * Wf < (1ll << 31), FGVC_ERR_UNSUPPORTED,
+               "fgvc_seg_label_set_u8: Hf + Wf > %d", SEG_MAX_TABLE - 8);
+  seg_label_set_kernel<<<1, 256, (Hf + Wf) * sizeof(int), (hipStream_t)stream>>>(map, hp, wp, Hf, Wf, out);
+  FGVC_CHECK_LAUNCH("fgvc_seg_label_set_u8");
+  return FGVC_OK;
+}
+
+int fgvc_seg_inject_labels_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int C, const uint32_t* set, float* rows, void* stream) {
+  FGVC_REQUIRE(map && set && rows, FGVC_ERR_INVALID_ARG, "fgvc_seg_inject_labels_u8: null pointer");
+  FGVC_REQUIRE(hp > 0 && wp > 0 && Hf > 0 && Wf > 0 && C >= 1 && C <= 256, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_inject_labels_u8: bad shape (1 <= C <= 256)");
+  FGVC_REQUIRE(Hf + Wf <= SEG_MAX_TABLE - 8 && (long long)Hf * Wf < (1ll << 31), FGVC_ERR_UNSUPPORTED,
+               "fgvc_seg_inject_labels_u8: Hf + Wf > %d", SEG_MAX_TABLE - 8);
+  const long long n = (long long)Hf * Wf * C;
+  const int blocks = (int)(n < 256ll * 1024 ? (n + 255) / 256 : 1024);
+  seg_inject_kernel<<<blocks, 256, (Hf + Wf) * sizeof(int), (hipStream_t)stream>>>(map, hp, wp, Hf, Wf, C, set, rows);
+  FGVC_CHECK_LAUNCH("fgvc_seg_inject_labels_u8");
+  return FGVC_OK;
+}
+
 int fgvc_seg_hard_onehot_f32(const float* in, int rows, int C, float* out, void* stream) {
   FGVC_REQUIRE(in && out, FGVC_ERR_INVALID_ARG, "fgvc_seg_hard_onehot_f32: null pointer");
   FGVC_REQUIRE(rows > 0 && C >= 1, FGVC_ERR_INVALID_ARG, "fgvc_seg_hard_onehot_f32: bad shape");
@@ -773,6 +811,40 @@ int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int h
     seg_argmax_kernel<false><<<g2, SEG_BLOCK, 2 * C * sizeof(float), s>>>(labels, g, part, norm, masks);
   }
   FGVC_CHECK_LAUNCH("fgvc_seg_readout_u8");
+  return FGVC_OK;
+}
+
+int fgvc_seg_readout_conf_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
+                             int w0, int norm, uint8_t* masks, uint8_t* conf, int64_t* stats, void* workspace, void* stream) {
+  FGVC_REQUIRE(labels && masks && conf && stats, FGVC_ERR_INVALID_ARG, "fgvc_seg_readout_conf_u8: null pointer");
+  FGVC_REQUIRE(n >= 0 && n <= 65535 && Hf > 0 && Wf > 0 && C >= 1 && C <= 256 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_conf_u8: bad shape (1 <= C <= 256, n <= 65535)");
+  FGVC_REQUIRE(h > 0 && w > 0 && top >= 0 && left >= 0 && top + h <= hp && left + w <= wp, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_conf_u8: the unpadded window must lie inside the padded frame");
+  FGVC_REQUIRE((long long)h0 * w0 < (1ll << 31) - SEG_CHUNK, FGVC_ERR_UNSUPPORTED, "fgvc_seg_readout_conf_u8: h0*w0 out of range");
+  FGVC_REQUIRE(workspace != nullptr || n == 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_seg_readout_conf_u8: workspace of fgvc_seg_readout_workspace_bytes() bytes required");
+  if (n == 0) return FGVC_OK;
+  ReadoutGeom g;
+  g.Hf = Hf; g.Wf = Wf; g.C = C; g.h = h; g.w = w; g.h0 = h0; g.w0 = w0; g.top = top; g.left = left;
+  g.s1y = (float)Hf / (float)hp; g.s1x = (float)Wf / (float)wp;
+  g.s2y = (float)h / (float)h0; g.s2x = (float)w / (float)w0;
+  const bool composed = !(h == h0 && w == w0);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  const int HW = h0 * w0;
+  const dim3 g1(SEG_NB, n), g2(cdiv(HW, SEG_CHUNK), n);
+  unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
+  FGVC_REQUIRE(hipMemsetAsync(stats, 0, (size_t)n * C * 2 * sizeof(int64_t), s) == hipSuccess, FGVC_ERR_LAUNCH,
+               "fgvc_seg_readout_conf_u8: clearing the statistics failed");
+  if (composed) {
+    seg_minmax_kernel<true><<<g1, SEG_BLOCK, 8 * C * sizeof(float), s>>>(labels, g, part);
+    seg_readout_conf_kernel<true><<<g2, SEG_BLOCK, 4 * C * sizeof(float), s>>>(labels, g, part, norm, masks, SegConfOut{conf, st});
+  } else {
+    seg_minmax_kernel<false><<<g1, SEG_BLOCK, 8 * C * sizeof(float), s>>>(labels, g, part);
+    seg_readout_conf_kernel<false><<<g2, SEG_BLOCK, 4 * C * sizeof(float), s>>>(labels, g, part, norm, masks, SegConfOut{conf, st});
+  }
+  FGVC_CHECK_LAUNCH("fgvc_seg_readout_conf_u8");
   return FGVC_OK;
 }
 

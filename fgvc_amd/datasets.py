@@ -635,7 +635,90 @@ def davis_evaluate(model, dataset: "Davis2017", backend: str = "host") -> dict:
     return metrics.davis_jf(seqs, backend=backend)
 
 
-FLO_MAGIC = 202021.25       # 'PIEH' read as a little-endian float32: the Middlebury .flo header
+class YoutubeVos:
+    """YouTube-VOS semi-supervised VOS, where an object is annotated at the frame it first appears in (parity unpinned: the data is not
+    available offline, the layout is restated from the format's public description).
+
+    Files under `root`: `JPEGImages/<video>/<frame>.jpg`, `Annotations/<video>/<frame>.png` (palette PNGs: index = object id) at least at
+    the frames where objects first appear, and `meta.json` with videos.<video>.objects.<id>.frames = the frame names the object is asked
+    for, the first of them its first appearance.  Item i = (data, meta): data = dict(imgs (1,1,3,T,h,w) -- or the uint8 frames with raw=True,
+    as Davis2017 --, ref_seg_map = {frame index: (h, w) uint8 map} for a tracker whose test_cfg.refs is set, img_meta); meta = dict(name,
+    frames = the frame names, gt (T, h, w) uint8 = every annotation on disk, zero elsewhere, has_gt (T,) bool, n_objects).
+    A first frame of meta.json without a PNG, or whose PNG lacks the object, raises ValueError naming the video."""
+
+    def __init__(self, root: str, device="cpu", max_frames: int = -1, raw=False):
+        import json
+        self.root, self.device, self.max_frames, self.raw = root, device, int(max_frames), bool(raw)
+        with open(os.path.join(root, "meta.json")) as f:
+            self.meta = json.load(f)["videos"]
+        self.videos = sorted(self.meta)
+
+    def __len__(self):
+        return len(self.videos)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        vid = self.videos[i]
+        jdir, adir = os.path.join(self.root, "JPEGImages", vid), os.path.join(self.root, "Annotations", vid)
+        names = sorted(os.path.splitext(n)[0] for n in os.listdir(jdir) if n.endswith(".jpg"))
+        if self.max_frames > 0:
+            names = names[:self.max_frames]
+        frames = torch.from_numpy(np.stack([np.asarray(Image.open(os.path.join(jdir, n + ".jpg")).convert("RGB")) for n in names]))
+        h, w = frames.shape[1:3]
+        gt, has_gt = np.zeros((len(names), h, w), np.uint8), np.zeros(len(names), bool)
+        for t, n in enumerate(names):
+            p = os.path.join(adir, n + ".png")
+            if os.path.exists(p):
+                im = Image.open(p)
+                gt[t], has_gt[t] = np.asarray(im if im.mode in ("P", "L") else im.convert("L")), True
+        refs, n_objects = {}, 0
+        for oid, obj in sorted(self.meta[vid]["objects"].items(), key=lambda kv: int(kv[0])):
+            first, oid = obj["frames"][0], int(oid)
+            if first not in names:
+                if self.max_frames > 0:
+                    continue                                      # the object enters after the frames that were kept
+                raise ValueError(f"YoutubeVos: video {vid!r}: meta.json puts object {oid}'s first frame at {first!r}, which has no JPEG")
+            t = names.index(first)
+            if not has_gt[t] or not (gt[t] == oid).any():
+                raise ValueError(f"YoutubeVos: video {vid!r}: meta.json puts object {oid}'s first frame at {first!r}, but "
+                                 f"Annotations/{vid}/{first}.png {'does not show it' if has_gt[t] else 'does not exist'}")
+            refs[t] = torch.from_numpy(gt[t].copy()).to(self.device)
+            n_objects = max(n_objects, oid)
+        if not refs:
+            raise ValueError(f"YoutubeVos: video {vid!r} has no annotated object")
+        imgs = _label_imgs(frames, (h, w), self.device, self.raw)
+        data = dict(imgs=imgs, ref_seg_map=refs, img_meta=[dict(original_shape=(h, w))])
+        return data, dict(name=vid, frames=names, gt=gt, has_gt=has_gt, n_objects=n_objects)
+
+
+def ytvos_run(model, dataset: "YoutubeVos", out_dir: Optional[str] = None) -> dict:
+    """Run the mask path (a tracker with test_cfg.refs) over the set.  out_dir: one palette PNG (the DAVIS palette) per frame in the
+    submission layout, out_dir/Annotations/<video>/<frame>.png.  Videos whose every frame has an annotation on disk are scored with
+    metrics.davis_jf (its frame rule); the returned dict holds `videos` (the names), and `jf` (that score, None when no video has
+    ground truth beyond the given frames)."""
+    from PIL import Image
+    from . import metrics
+    from .viz import davis_palette
+    scored, done = {}, []
+    for i in range(len(dataset)):
+        data, meta = dataset[i]
+        pred = model(test_mode=True, **data)[0]
+        pred = pred.cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
+        ids = np.rint(pred).astype(np.uint8)
+        if out_dir is not None:
+            vdir = os.path.join(out_dir, "Annotations", meta["name"])
+            os.makedirs(vdir, exist_ok=True)
+            for t, n in enumerate(meta["frames"]):
+                im = Image.fromarray(ids[t], mode="P")
+                im.putpalette(davis_palette().tobytes())
+                im.save(os.path.join(vdir, n + ".png"))
+        if bool(meta["has_gt"].all()):
+            scored[meta["name"]] = (meta["gt"], ids)
+        done.append(meta["name"])
+    return dict(videos=done, jf=metrics.davis_jf(scored) if scored else None)
+
+
+FLO_MAGIC = 202021.25      # 'PIEH' read as a little-endian float32: the Middlebury .flo header
 
 
 def write_flo(path, flow) -> None:

@@ -658,6 +658,251 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     return masks
 
 
+# ---- index maps annotated at any frame (test_cfg.refs, an extension key) -------------------------------------------
+#
+# The rule, stated once in sweep_refs_host (float64, on given top-k lists) and run on the device by propagate_masks_refs.  s0 = the earliest
+# annotated frame.  The forward pass is the ordinary sweep of the sub-clip s0 .. T-1 (plan_clip(T, [s0], cfg) with its frames renumbered from
+# 0: key slots [s0] + the preceding frames); an annotated frame t > s0 is injected after its propagation.  direction='both' labels frames
+# s0-1 .. 0 by the same sweep of the time-reversed sub-clip s0, s0-1, .., 0 (a reversed copy of those frames' features, the ordinary forward
+# plan of length s0 + 1).  The lists depend on the features only: a LabelSweep per (s0, 'fw' | 'bw') is what a LabelSession keeps.
+
+REFS_DIRECTIONS = ("forward", "both")
+REFS_OVERRIDES = ("new", "all")
+
+
+@dataclass
+class RefsConfig:
+    """test_cfg.refs = dict(direction='forward' | 'both', override='new' | 'all', confidence=False), parsed."""
+    direction: str = "forward"
+    override: str = "new"
+    confidence: bool = False
+
+
+def parse_refs(spec) -> Optional[RefsConfig]:
+    """None -> None (the option is off: ref_seg_map is one tensor for frame 0).  A mapping -> RefsConfig; an unknown key or value raises
+    ValueError, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.refs: a dict such as dict(direction='forward', override='new'), got {type(spec).__name__}")
+    spec = dict(spec)
+    direction, override, confidence = spec.pop("direction", "forward"), spec.pop("override", "new"), spec.pop("confidence", False)
+    if spec:
+        raise ValueError(f"test_cfg.refs: unknown key(s) {sorted(spec)} (direction, override, confidence)")
+    if direction not in REFS_DIRECTIONS:
+        raise ValueError(f"test_cfg.refs: direction={direction!r} (one of {REFS_DIRECTIONS})")
+    if override not in REFS_OVERRIDES:
+        raise ValueError(f"test_cfg.refs: override={override!r} (one of {REFS_OVERRIDES})")
+    if not isinstance(confidence, bool):
+        raise ValueError(f"test_cfg.refs: confidence={confidence!r} (True or False)")
+    return RefsConfig(direction, override, confidence)
+
+
+def check_ref_maps(refs, n_frames: int, shape: Tuple[int, int]) -> Dict[int, torch.Tensor]:
+    """The mapping form of ref_seg_map, checked: {frame index: integer map (h, w) or (1, h, w)} -> {int frame: (h, w) uint8 tensor} in
+    ascending frame order (each on the device it came from).  A tensor means {0: tensor}.  TypeError for anything else; ValueError for an
+    empty mapping, a frame index outside the clip, a map of another size than `shape`, a negative id; NotImplementedError for an id above 255
+    (today's ref_seg_map rules)."""
+    if torch.is_tensor(refs):
+        refs = {0: refs}
+    if not hasattr(refs, "keys"):
+        raise TypeError(f"ref_seg_map: with test_cfg.refs a mapping {{frame index: index map}} or one tensor, got {type(refs).__name__}")
+    if len(refs) == 0:
+        raise ValueError("ref_seg_map: the mapping is empty (at least one annotated frame)")
+    out = {}
+    for key in sorted(refs.keys(), key=int):
+        t, m = int(key), refs[key]
+        if t != key or not 0 <= t < n_frames:
+            raise ValueError(f"ref_seg_map: frame index {key!r} outside the clip's {n_frames} frames")
+        if not torch.is_tensor(m):
+            m = torch.as_tensor(m)
+        if m.dim() == 3 and m.shape[0] == 1:
+            m = m[0]
+        if m.dim() != 2 or tuple(m.shape) != tuple(shape):
+            raise ValueError(f"ref_seg_map[{t}]: a map of size {tuple(shape)} (the frames'), got {tuple(m.shape)}")
+        if m.is_floating_point() or m.dtype == torch.bool:
+            raise TypeError(f"ref_seg_map[{t}]: integer ids, got {m.dtype}")
+        if m.dtype != torch.uint8:
+            lo, hi = int(m.min()), int(m.max())
+            if hi > 255:
+                raise NotImplementedError(f"fgvc_amd: the mask path takes at most 255 object ids (largest id {hi} at frame {t}); split the "
+                                          "objects over several calls")
+            if lo < 0:
+                raise ValueError(f"ref_seg_map[{t}]: negative id {lo}")
+            m = m.to(torch.uint8)
+        out[t] = m
+    return out
+
+
+def sweep_refs_host(small: Dict[int, torch.Tensor], n_frames: int, fw=None, bw=None, direction: str = "forward", override: str = "new",
+                    hard_prop: bool = False) -> torch.Tensor:
+    """The contract of test_cfg.refs in float64 torch, on given top-k lists.  small = {frame: (HW,) integer ids}, each annotated map
+    already sampled to the feature grid; fw / bw: the lists of the forward sub-clip s0 .. T-1 and of the reversed sub-clip s0, s0-1, .., 0,
+    each with `slot_frame` (n-1, t_max), `idx` (n-1, HW, k) = slot * HW + pixel and `weight` (n-1, HW, k) in the SUB-CLIP's own frame
+    numbering (row j - 1 belongs to sub-clip frame j, a LabelSweep's layout; None where the sub-clip has one frame or is not swept).
+    Returns the soft rows (T, HW, C) float64, C = 1 + the largest id of any map: what the read-out sees.  Frame s0 holds one_hot(M_s0);
+    frames before s0 under 'forward' hold the background's one-hot."""
+    if direction not in REFS_DIRECTIONS or override not in REFS_OVERRIDES:
+        raise ValueError(f"sweep_refs_host: direction={direction!r}, override={override!r}")
+    frames = sorted(small)
+    s0, T = frames[0], int(n_frames)
+    small = {t: small[t].reshape(-1).long() for t in frames}
+    HW = small[s0].numel()
+    C = 1 + max(int(m.max()) for m in small.values())
+
+    def one_hot(m):
+        return torch.nn.functional.one_hot(m, C).double()
+
+    def sweep(lists, first, n, inject):
+        bank = torch.zeros(n, HW, C, dtype=torch.float64)
+        soft = torch.zeros_like(bank)
+        bank[0] = soft[0] = first
+        seen = set(small[s0].unique().tolist())
+        for j in range(1, n):
+            sf, idx, w = lists.slot_frame[j - 1].cpu().long(), lists.idx[j - 1].cpu().long(), lists.weight[j - 1].cpu().double()
+            slot, pix = idx // HW, idx % HW
+            soft[j] = (w[..., None] * bank[sf[slot], pix]).sum(1)
+            hard = one_hot(soft[j].argmax(-1)) if hard_prop else None
+            t = s0 + j
+            if inject and t in small:
+                ids = set(small[t].unique().tolist())
+                chosen = ids if override == "all" else ids - seen
+                seen |= ids
+                sel = torch.isin(small[t], torch.tensor(sorted(chosen), dtype=torch.long))
+                soft[j][sel] = one_hot(small[t])[sel]
+                if hard_prop:
+                    hard[sel] = one_hot(small[t])[sel]
+            bank[j] = hard if hard_prop else soft[j]
+        return soft
+
+    out = torch.zeros(T, HW, C, dtype=torch.float64)
+    out[:s0, :, 0] = 1.0
+    out[s0:] = sweep(fw, one_hot(small[s0]), T - s0, True)
+    if direction == "both" and s0 > 0:
+        out[:s0] = sweep(bw, one_hot(small[s0]), s0 + 1, False)[1:].flip(0)
+    return out
+
+
+def next_frame_to_annotate(frame_score, annotated) -> Optional[int]:
+    """The un-annotated frame with the lowest score, the lowest index among equals; None when every frame is annotated."""
+    scores = [float(v) for v in (frame_score.tolist() if hasattr(frame_score, "tolist") else frame_score)]
+    done = set(int(t) for t in annotated)
+    best = None
+    for f, s in enumerate(scores):
+        if f not in done and (best is None or s < scores[best]):
+            best = f
+    return best
+
+
+def refs_sweeps(feats_hwc: torch.Tensor, Hf: int, Wf: int, s0: int, both: bool, cfg: TrackerConfig, channels: Optional[int] = None,
+                stats_out: Optional[list] = None, sweeps: Optional[dict] = None, counters: Optional[dict] = None):
+    """(fw, bw): the LabelSweeps of the forward sub-clip s0 .. T-1 and (both, s0 > 0) of the reversed sub-clip s0 .. 0; None where the
+    sub-clip has one frame.  `sweeps`: a cache keyed (s0, 'fw' | 'bw') that is read and filled; `counters['affinity_runs']` goes up by one
+    when this call had to compute a part."""
+    if isinstance(cfg, LocalConfig):
+        raise NotImplementedError("test_cfg.refs: the local-window affinity (plan_local_clip has no start frame)")
+    T = feats_hwc.shape[0]
+    sweeps = {} if sweeps is None else sweeps
+    ran = False
+    if (s0, "fw") not in sweeps:
+        sweeps[(s0, "fw")] = label_affinity(feats_hwc[s0:], Hf, Wf, T - s0, cfg, channels, stats_out) if T - s0 > 1 else None
+        ran = ran or T - s0 > 1
+    if both and s0 > 0 and (s0, "bw") not in sweeps:
+        rev = feats_hwc[:s0 + 1].flip(0).contiguous()
+        sweeps[(s0, "bw")] = label_affinity(rev, Hf, Wf, s0 + 1, cfg, channels, stats_out)
+        ran = True
+    if ran and counters is not None:
+        counters["affinity_runs"] = counters.get("affinity_runs", 0) + 1
+    return sweeps[(s0, "fw")], (sweeps[(s0, "bw")] if both and s0 > 0 else None)
+
+
+def _sweep_refs(bank: torch.Tensor, soft: torch.Tensor, sw: Optional[LabelSweep], Hf: int, Wf: int, hard_prop: bool, inject: dict) -> None:
+    """_sweep_labels with injections: inject = {sub-clip frame j: (padded map, id set (8,) int32 on the device)}, applied to soft[j] (and
+    bank[j] under hard_prop) after frame j's propagation."""
+    C = bank.shape[2]
+    for f in range(1, bank.shape[0]):
+        ops.propagate_topk(bank, sw.slot_frame[f - 1], sw.idx[f - 1], sw.weight[f - 1], Hf, Wf, Hf, Wf, window_L=sw.window_L, out=soft[f])
+        if hard_prop:
+            ops.seg_hard_onehot(soft[f], out=bank[f])
+        if f in inject:
+            seg, ids = inject[f]
+            ops.seg_inject_labels(seg, Hf, Wf, C, ids, soft[f])
+            if hard_prop:
+                ops.seg_inject_labels(seg, Hf, Wf, C, ids, bank[f])
+
+
+def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Dict[int, torch.Tensor], pad: Tuple[int, int, int, int],
+                         out_shape: Tuple[int, int], cfg, rc: RefsConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
+                         confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None):
+    """propagate_masks with index maps at any frames: seg_maps = {frame: padded (hp, wp) uint8 map on the device}; rc names the direction and
+    the override rule (sweep_refs_host is the contract).  Returns (T, h0, w0) uint8 on the device; frame s0 (the earliest annotated one) is
+    its given map, unpadded and nearest-resized, every other frame the read-out of its rows, frames before s0 under 'forward' zero.
+    confidence: (masks, conf (T, h0, w0) uint8, stats (T, C, 2) int64) as ops.seg_readout_conf gives them; frame s0 has conf 255, frames
+    that are not labelled at all conf 0.  One host read: the presence sets of all maps (C = 1 + the largest id present in any).
+    sweeps / counters: refs_sweeps' cache and counter; counters['sweeps'] counts these calls."""
+    if isinstance(cfg, LocalConfig):
+        raise NotImplementedError("test_cfg.refs: the local-window affinity (plan_local_clip has no start frame)")
+    T, dev = feats_hwc.shape[0], feats_hwc.device
+    frames = sorted(seg_maps)
+    s0 = frames[0]
+    sets_dev = torch.empty((len(frames), 8), device=dev, dtype=torch.int32)
+    for i, t in enumerate(frames):
+        ops.seg_label_set(seg_maps[t], Hf, Wf, out=sets_dev[i])
+    present = [set(ops.label_set_ids(row)) for row in sets_dev.cpu()]                     # the call's one host read
+    C = 1 + max(max(p) for p in present)
+    inject, seen = {}, set(present[0])
+    for t, ids in zip(frames[1:], present[1:]):
+        chosen = ids if rc.override == "all" else ids - seen
+        seen |= ids
+        if chosen:
+            inject[t - s0] = (seg_maps[t], ops.label_set_words(sorted(chosen)).to(dev))
+    both = rc.direction == "both"
+    fw, bw = refs_sweeps(feats_hwc, Hf, Wf, s0, both, cfg, channels, stats_out, sweeps, counters)
+    if counters is not None:
+        counters["sweeps"] = counters.get("sweeps", 0) + 1
+    hp, wp = seg_maps[s0].shape
+    lw, uw, lh, uh = pad
+    masks = torch.zeros((T, *out_shape), device=dev, dtype=torch.uint8)
+    conf = torch.zeros_like(masks) if confidence else None
+    stats = torch.zeros((T, C, 2), device=dev, dtype=torch.int64) if confidence else None
+
+    def run(n, sw, inj, dst):
+        """one sub-clip of n frames from one_hot(M_s0); the read-out of its frames 1.. goes to the clip frames `dst` (a slice or an index)"""
+        bank = torch.zeros((n, Hf * Wf, C), device=dev, dtype=torch.float32)
+        ops.seg_onehot_labels(seg_maps[s0], Hf, Wf, C, out=bank[0])
+        soft = torch.empty_like(bank) if cfg.hard_prop else bank
+        _sweep_refs(bank, soft, sw, Hf, Wf, cfg.hard_prop, inj)
+        if n < 2:
+            return
+        if confidence:
+            m, c, st = ops.seg_readout_conf(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
+            masks[dst], conf[dst], stats[dst] = m, c, st
+        elif isinstance(dst, slice):
+            ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[dst])
+        else:
+            masks[dst] = ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
+
+    run(T - s0, fw, inject, slice(s0 + 1, T))
+    if both and s0 > 0:
+        run(s0 + 1, bw, {}, torch.arange(s0 - 1, -1, -1, device=dev))
+    ref = seg_maps[s0][lh:hp - uh, lw:wp - uw].float()[None, None]
+    masks[s0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
+    if not confidence:
+        return masks
+    conf[s0] = 255
+    given = [s0] if both else list(range(s0 + 1))                     # frames whose statistics no read-out wrote: counts by id, conf as above
+    for f in given:
+        cnt = torch.bincount(masks[f].flatten().long(), minlength=C)[:C]
+        stats[f, :, 0] = cnt
+        stats[f, :, 1] = cnt * (255 if f == s0 else 0)
+    return masks, conf, stats
+
+
+def frame_scores(stats: torch.Tensor, out_shape: Tuple[int, int]) -> torch.Tensor:
+    """stats (T, C, 2) int64 -> (T,) float64 on the host: the mean conf byte of every frame / 255, from the integer sums."""
+    return stats[..., 1].sum(1).cpu().double() / (255.0 * int(out_shape[0]) * int(out_shape[1]))
+
+
 def propagate_soft_bank(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int], cfg,
                         channels: Optional[int] = None, stats_out: Optional[list] = None, events: Optional[dict] = None,
                         affinity_stats: Optional[dict] = None) -> Tuple[torch.Tensor, LabelSweep]:

@@ -11,4 +11,4 @@ from .builder import (build, build_backbone, build_components, build_drop_layer,
                       build_operators)
 from .config import Config, ConfigDict  # noqa: F401
 from .registry import BACKBONES, COMPONENTS, DROP_LAYERS, LOSSES, MODELS, OPERATORS, Registry, build_from_cfg  # noqa: F401
-from .trackers import BaseModel, BaseTracker, HRVanillaTracker, VanillaTracker  # noqa: F401
+from .trackers import BaseModel, BaseTracker, HRVanillaTracker, LabelSession, VanillaTracker  # noqa: F401

@@ -82,6 +82,60 @@ class BaseTracker(BaseModel):
         return x
 
 
+class LabelSession:
+    """A clip encoded once, index maps propagated any number of times (model.open_label_session).  The affinity lists depend on the
+    features only, so the session keeps one engine.LabelSweep per (first annotated frame, time direction): a second propagate with the
+    same first frame launches no encoder, no pair kernel and no merge -- only the sweep and the read-out.
+    counters: encodes (1), affinity_runs (propagate calls that had to compute lists), sweeps (propagate calls)."""
+
+    def __init__(self, model, imgs, img_meta):
+        if imgs is None or img_meta is None:
+            raise TypeError("open_label_session needs imgs and img_meta")
+        model._raw_input(imgs, "imgs")
+        model._refuse_occlusion("the mask call (imgs= / ref_seg_map=)")
+        model._refuse_refs()
+        if imgs.shape[0] != 1 or imgs.shape[1] != 1:
+            raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
+        if not imgs.is_cuda:
+            raise RuntimeError(f"fgvc_amd.{type(model).__name__} runs on the GPU only (no CPU fallback)")
+        self.model = model
+        self.cfg = model._label_config()
+        self.out_shape = tuple(int(v) for v in img_meta[0]["original_shape"][:2])
+        frames, self.size, self.pad = model._label_frames(imgs)                               # (T, 3, hp, wp)
+        self.n_frames, self.device = frames.shape[0], frames.device
+        self.feats, self.Hf, self.Wf = model._label_feats(frames, index_map=True)
+        self._sweeps = {}
+        self.counters = dict(encodes=1, affinity_runs=0, sweeps=0)
+
+    def propagate(self, refs, direction=None, override=None, confidence=False):
+        """refs: {frame index: index map (h, w) | (1, h, w)} at the network size, or one tensor for frame 0.  direction / override default to
+        test_cfg.refs' (else 'forward' / 'new').  Returns what the mask call returns, [masks] with masks (T, h0, w0) float64 on the host or
+        the uint8 device tensor (test_cfg.masks='device'); confidence=True: (masks, conf, stats) in the same form, conf (T, h0, w0) uint8,
+        stats (T, C, 2) int64 (ops.seg_readout_conf)."""
+        if self.feats is None:
+            raise RuntimeError("LabelSession: propagate after close()")
+        base = self.model.refs_cfg or engine.RefsConfig()
+        rc = engine.parse_refs(dict(direction=base.direction if direction is None else direction,
+                                    override=base.override if override is None else override))
+        maps = engine.check_ref_maps(refs, self.n_frames, self.size)
+        segs = {t: torch.nn.functional.pad(m.to(self.device, torch.uint8), self.pad).contiguous() for t, m in maps.items()}
+        stats = []
+        out = engine.propagate_masks_refs(self.feats, self.Hf, self.Wf, segs, self.pad, self.out_shape, self.cfg, rc,
+                                          channels=self.model.feat_channels, stats_out=stats, confidence=bool(confidence),
+                                          sweeps=self._sweeps, counters=self.counters)
+        self.model._refine_stats = stats or None
+        self.model._check_kernels()
+        device = self.model.masks_form == "device"
+        if not confidence:
+            return [out] if device else [out.cpu().numpy().astype("float64")]
+        masks, conf, st = out
+        return (masks, conf, st) if device else (masks.cpu().numpy().astype("float64"), conf.cpu().numpy(), st.cpu().numpy())
+
+    def close(self):
+        """Drop the features and the cached lists."""
+        self.feats, self._sweeps = None, {}
+
+
 @MODELS.register_module()
 class VanillaTracker(BaseTracker):
     """Label propagation with a dense (disc-masked) affinity and top-k softmax."""
@@ -96,6 +150,8 @@ class VanillaTracker(BaseTracker):
         self.masks_form = engine.parse_masks(self.test_cfg.get("masks", None))     # test_cfg.masks: 'numpy' (default) | 'device'; the index-map call only
         self.chain_cfg = engine.parse_chain(self.test_cfg.get("chain", None))      # test_cfg.chain (None: the points call propagates labels, as ever)
         self.last_flow = None              # forward_test_flow's dict of the last points call with test_cfg.chain set, else None
+        self.refs_cfg = engine.parse_refs(self.test_cfg.get("refs", None))         # test_cfg.refs (None: ref_seg_map is one tensor for frame 0)
+        self.last_confidence = None        # dict(conf, stats, frame_score) of the last mask call with test_cfg.refs.confidence=True, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -490,6 +546,11 @@ class VanillaTracker(BaseTracker):
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
         self._raw_input(imgs, "imgs")                      # uint8 frames: TypeError without test_cfg.input, the GPU-only rule with it
         self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
+        if self.refs_cfg is None and hasattr(ref_seg_map, "keys"):
+            raise TypeError("ref_seg_map: a mapping {frame index: index map} is taken with the extension key test_cfg.refs = "
+                            "dict(direction='forward' | 'both', override='new' | 'all'); without it ref_seg_map is frame 0's tensor")
+        if self.refs_cfg is not None:
+            return self._forward_test_refs(imgs, ref_seg_map, img_meta)
         return_maps = bool(g("return_maps", False))        # extension key: the propagated soft maps themselves (the reference's coords=False output)
         if return_maps and g("coords", False):
             raise ValueError("fgvc_amd: return_maps=True and coords=True ask for two read-outs of one call; set one of them")
@@ -534,6 +595,40 @@ class VanillaTracker(BaseTracker):
         if self.masks_form == "device":
             return [masks]
         return [masks.cpu().numpy().astype("float64")]
+
+    # ---- index maps at any frame: test_cfg.refs (an extension key) ----------------------------------------------------
+    def _refuse_refs(self):
+        """What test_cfg.refs does not cover, each refused by name before any work."""
+        g = self.test_cfg.get
+        if isinstance(self._label_config(), engine.LocalConfig):
+            raise NotImplementedError(f"fgvc_amd: test_cfg.refs with {type(self).__name__}: the local-window plan (plan_local_clip) has no start "
+                                      "frame; annotate frame 0 and remove the key, or use VanillaTracker")
+        if g("coords", False) or g("return_maps", False):
+            raise NotImplementedError("fgvc_amd: test_cfg.refs takes index maps only; coords=True / return_maps=True (soft labels) start at "
+                                      "frame 0 -- remove one of the keys")
+        if g("save_np", False):
+            raise NotImplementedError("fgvc_amd: save_np=True is not supported; the masks are returned (save them with numpy.save)")
+
+    def open_label_session(self, imgs, img_meta):
+        """Encode the clip once for any number of mask propagations: LabelSession.  imgs / img_meta as the mask call takes them (float
+        frames, or raw ones with test_cfg.input)."""
+        return LabelSession(self, imgs, img_meta)
+
+    def _forward_test_refs(self, imgs, ref_seg_map, img_meta):
+        """The index-map call with test_cfg.refs set: one LabelSession, one propagate.  Returns [masks] as the call without the key does;
+        with refs.confidence=True the confidence bytes, statistics and frame scores stay in self.last_confidence."""
+        rc = self.refs_cfg
+        self.last_confidence = None
+        session = LabelSession(self, imgs, img_meta)
+        try:
+            out = session.propagate(ref_seg_map, confidence=rc.confidence)
+        finally:
+            session.close()
+        if not rc.confidence:
+            return out
+        masks, conf, stats = out
+        self.last_confidence = dict(conf=conf, stats=stats, frame_score=engine.frame_scores(torch.as_tensor(stats), session.out_shape))
+        return [masks]
 
     def _forward_test_heatmap(self, imgs, heat, img_meta, return_maps=False):
         """forward_test_seg with soft first-frame labels and test_cfg.coords=True (the JHMDB / BADJA heat-map form): heat (1, K, hm, wm)

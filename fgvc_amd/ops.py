@@ -12,7 +12,7 @@ import ctypes as C
 import functools
 import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -1380,6 +1380,69 @@ def seg_readout(labels: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, in
     _lib.call("fgvc_seg_readout_u8", _ptr(labels), n, Hf, Wf, C, hp, wp, lh, lw, hp - lh - uh, wp - lw - uw, h0, w0, int(bool(norm)),
               _ptr(out), _ptr(ws), _stream(labels))
     return out
+
+
+def seg_label_set(seg_map: torch.Tensor, Hf: int, Wf: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """seg_map (hp, wp) uint8 -> (8,) int32 on the device: the 256-bit set of the ids present in the map sampled to (Hf, Wf) by Pillow's
+    NEAREST rule (bit id % 32 of word id // 32; label_set_ids turns a host copy into a list)."""
+    seg_map = _chk(seg_map, torch.uint8, "seg_map")
+    hp, wp = seg_map.shape
+    if out is None:
+        out = torch.empty((8,), device=seg_map.device, dtype=torch.int32)
+    else:
+        assert out.is_contiguous() and out.shape == (8,) and out.dtype == torch.int32
+    _lib.call("fgvc_seg_label_set_u8", _ptr(seg_map), hp, wp, Hf, Wf, _ptr(out), _stream(seg_map))
+    return out
+
+
+def label_set_ids(words) -> List[int]:
+    """The ids of a 256-bit set given as 8 int32 / uint32 words (a host tensor or a sequence), ascending."""
+    ws = [int(w) & 0xFFFFFFFF for w in (words.tolist() if hasattr(words, "tolist") else words)]
+    return [32 * j + b for j, w in enumerate(ws) for b in range(32) if (w >> b) & 1]
+
+
+def label_set_words(ids) -> torch.Tensor:
+    """ids (each 0..255) -> the (8,) int32 host tensor of their 256-bit set (label_set_ids' inverse)."""
+    ws = [0] * 8
+    for i in ids:
+        if not 0 <= int(i) <= 255:
+            raise ValueError(f"label_set_words: id {i} outside 0..255")
+        ws[int(i) >> 5] |= 1 << (int(i) & 31)
+    return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in ws], dtype=torch.int32)
+
+
+def seg_inject_labels(seg_map: torch.Tensor, Hf: int, Wf: int, C: int, ids: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """rows (HfWf, C) f32, written in place: every cell whose id in pil_nearest(seg_map, (Hf, Wf)) is in the set `ids` ((8,) int32 on the
+    device, seg_label_set's layout) becomes one_hot(id, C); every other cell keeps its row.  Returns rows."""
+    seg_map = _chk(seg_map, torch.uint8, "seg_map")
+    ids = _chk(ids, torch.int32, "ids")
+    hp, wp = seg_map.shape
+    if not rows.is_cuda:
+        raise _lib.FgvcHipError("rows must be on the GPU (fgvc_amd has no CPU path)")
+    assert ids.shape == (8,) and rows.is_contiguous() and rows.shape == (Hf * Wf, C) and rows.dtype == torch.float32
+    _lib.call("fgvc_seg_inject_labels_u8", _ptr(seg_map), hp, wp, Hf, Wf, C, _ptr(ids), _ptr(rows), _stream(seg_map))
+    return rows
+
+
+def seg_readout_conf(labels: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, int], pad: Tuple[int, int, int, int],
+                     out_shape: Tuple[int, int], norm: bool = True, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """seg_readout with the confidence of every pixel: (masks (n, h0, w0) uint8 -- seg_readout's bytes --, conf (n, h0, w0) uint8 =
+    rint(255 * clamp(best - second, 0, 1)) of the two largest (normalised) channel values, 255 where C == 1, stats (n, C, 2) int64 = per
+    frame and id the pixel count and the sum of that id's conf bytes).  `out` = (masks, conf) to write into."""
+    labels = _chk(labels, torch.float32, "labels")
+    n, C = labels.shape[0], labels.shape[2]
+    assert labels.shape[1] == Hf * Wf
+    (hp, wp), (lw, uw, lh, uh), (h0, w0) = pad_shape, pad, out_shape
+    if out is None:
+        out = (torch.empty((n, h0, w0), device=labels.device, dtype=torch.uint8), torch.empty((n, h0, w0), device=labels.device, dtype=torch.uint8))
+    masks, conf = out
+    for t in (masks, conf):
+        assert t.is_cuda and t.is_contiguous() and t.shape == (n, h0, w0) and t.dtype == torch.uint8
+    stats = torch.empty((n, C, 2), device=labels.device, dtype=torch.int64)
+    ws = torch.empty((max(_lib.load().fgvc_seg_readout_workspace_bytes(n, C), 4) + 3) // 4, device=labels.device, dtype=torch.float32)
+    _lib.call("fgvc_seg_readout_conf_u8", _ptr(labels), n, Hf, Wf, C, hp, wp, lh, lw, hp - lh - uh, wp - lw - uw, h0, w0, int(bool(norm)),
+              _ptr(masks), _ptr(conf), _ptr(stats), _ptr(ws), _stream(labels))
+    return masks, conf, stats
 
 
 # ---- soft first-frame labels read out as joint coordinates (JHMDB / BADJA heat maps, vanilla_tracker.py:663-830 with coords=True) ----

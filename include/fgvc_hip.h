@@ -714,6 +714,20 @@ size_t fgvc_seg_readout_workspace_bytes(int n, int C);
 int fgvc_seg_readout_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
                         int w0, int norm, uint8_t* masks, void* workspace, void* stream);
 
+/* Annotations at any frame (test_cfg.refs).  fgvc_seg_label_set_u8: the ids present in the map sampled to (Hf, Wf) by the same Pillow
+ * NEAREST rule, as a 256-bit set out[8] (uint32: bit id % 32 of word id / 32); one launch, one workgroup.
+ * fgvc_seg_inject_labels_u8: rows [Hf*Wf][C] f32, in place: a cell whose sampled id is in `set` (8 uint32 on the device) becomes
+ * one_hot(id, C) (an id >= C: a zero row); every other cell keeps its values.  1 <= C <= 256. */
+int fgvc_seg_label_set_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, uint32_t* out, void* stream);
+int fgvc_seg_inject_labels_u8(const uint8_t* map, int hp, int wp, int Hf, int Wf, int C, const uint32_t* set, float* rows, void* stream);
+
+/* fgvc_seg_readout_u8 with the confidence of every pixel: masks are fgvc_seg_readout_u8's bytes (one device function computes both);
+ * conf [n][h0][w0] uint8 = rint(255 * clamp(best - second, 0, 1)) with best / second the two largest of the values the argmax compares
+ * (normalised where norm applies; C == 1 gives 255); stats [n][C][2] int64 = per frame and id the pixel count and the sum of its conf
+ * bytes (integer atomics: order-independent; cleared here).  workspace as fgvc_seg_readout_u8's. */
+int fgvc_seg_readout_conf_u8(const float* labels, int n, int Hf, int Wf, int C, int hp, int wp, int top, int left, int h, int w, int h0,
+                             int w0, int norm, uint8_t* masks, uint8_t* conf, int64_t* stats, void* workspace, void* stream);
+
 /* ---- Soft first-frame labels read out as joint coordinates (the JHMDB / BADJA heat-map form: vanilla_tracker.py:700-716 with a 4-D
  * map, :770-784, img2coord :172-191, :814-818).  The map (K, hm, wm) f32 or f64 lies at (top, left) of its zero padding to (hp, wp)
  * (its own pad_divide_by, :672); the padding is implicit, no padded copy is made.  Propagation is fgvc_propagate_topk_f32 with P = K.

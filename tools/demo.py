@@ -156,17 +156,45 @@ def run_points(a, frames: np.ndarray, dev):
     return tracks, visibles, qp_out.cpu().numpy()
 
 
-def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
-    """-> (T, H, W) uint8 object ids on the device, frame 0 the given mask."""
+def _mask_png(path, H, W, flag) -> np.ndarray:
     from PIL import Image
-    T, H, W = frames.shape[:3]
-    mask = np.asarray(Image.open(a.first_mask))
+    mask = np.asarray(Image.open(path))
     if mask.ndim != 2 or mask.shape != (H, W):
-        raise ValueError(f"--first-mask: a palette or grey PNG of object ids, {H} x {W} as the frames, got an array of shape {mask.shape}")
-    model = build_model(a, dev, input=_input(a, None), masks="device")
+        raise ValueError(f"{flag}: a palette or grey PNG of object ids, {H} x {W} as the frames, got an array of shape {mask.shape}")
+    return mask.astype(np.uint8)
+
+
+def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
+    """-> (T, H, W) uint8 object ids on the device, frame 0 the given mask.  With --mask T PNG (test_cfg.refs): masks at any frames, the
+    first annotated frame the given one; --confidence also writes conf_%05d.png into --out and prints the frame scores."""
+    T, H, W = frames.shape[:3]
+    imgs, meta = _raw(a, frames, dev)[None, None], [dict(original_shape=(H, W))]
+    if not a.mask:
+        mask = _mask_png(a.first_mask, H, W, "--first-mask")
+        model = build_model(a, dev, input=_input(a, None), masks="device")
+        with torch.no_grad():
+            out = model(test_mode=True, imgs=imgs, ref_seg_map=torch.from_numpy(mask)[None].to(dev), img_meta=meta)
+        return out[0]
+    refs = {}
+    if a.first_mask:
+        refs[0] = torch.from_numpy(_mask_png(a.first_mask, H, W, "--first-mask"))
+    for t, path in a.mask:
+        if not t.lstrip("-").isdigit() or not 0 <= int(t) < T or int(t) in refs:
+            raise ValueError(f"--mask {t} {path}: a frame index 0 .. {T - 1}, each frame once")
+        refs[int(t)] = torch.from_numpy(_mask_png(path, H, W, "--mask"))
+    model = build_model(a, dev, input=_input(a, None), masks="device",
+                        refs=dict(direction="both" if a.both_ways else "forward", override=a.override, confidence=a.confidence))
     with torch.no_grad():
-        out = model(test_mode=True, imgs=_raw(a, frames, dev)[None, None], ref_seg_map=torch.from_numpy(mask.astype(np.uint8))[None].to(dev),
-                    img_meta=[dict(original_shape=(H, W))])
+        out = model(test_mode=True, imgs=imgs, ref_seg_map=refs, img_meta=meta)
+    if a.confidence:
+        from PIL import Image
+        from fgvc_amd import engine
+        lc = model.last_confidence
+        os.makedirs(a.out, exist_ok=True)
+        for f, c in enumerate(lc["conf"].cpu().numpy()):
+            Image.fromarray(c).save(os.path.join(a.out, f"conf_{f:05d}.png"))
+        print("frame_score: " + " ".join(f"{v:.4f}" for v in lc["frame_score"].tolist()))
+        print(f"annotate next: frame {engine.next_frame_to_annotate(lc['frame_score'], refs)}")
     return out[0]
 
 
@@ -255,6 +283,13 @@ def parse_args(argv=None):
     ap.add_argument("--chain-visibility", choices=("frame", "consistency"), default="frame", help="with --chain: chain.visibility")
     ap.add_argument("--query-points", type=float, nargs="+", default=[], metavar="V", help="t x y [t x y ...], pixels of the clip")
     ap.add_argument("--first-mask", help="PNG of object ids for frame 0 (--task vos)")
+    ap.add_argument("--mask", nargs=2, action="append", default=[], metavar=("T", "PNG"),
+                    help="PNG of object ids for frame T, repeatable (--task vos; test_cfg.refs: objects may enter at any frame)")
+    ap.add_argument("--both-ways", action="store_true", help="with --mask: also label the frames before the first annotated one")
+    ap.add_argument("--override", choices=("new", "all"), default="new",
+                    help="with --mask: a later mask brings in its new objects only, or replaces the frame's labels (a correction)")
+    ap.add_argument("--confidence", action="store_true",
+                    help="with --mask: write conf_%%05d.png (the top-two gap per pixel) and print the frame scores and the frame to annotate next")
     ap.add_argument("--out", required=True)
     ap.add_argument("--host-render", action="store_true", help="paint (and, with --out-video, encode) with viz's numpy backend instead of the kernels")
     ap.add_argument("--out-video", default=None, metavar="OUT.y4m", help="also write the result as a YUV4MPEG2 file of 8-bit 4:2:0 frames")
@@ -284,8 +319,10 @@ def parse_args(argv=None):
         ap.error("give FRAMES_DIR or --synthetic T H W")
     if a.task == "points" and not a.query_points:
         ap.error("--task points needs --query-points")
-    if a.task == "vos" and not a.first_mask:
-        ap.error("--task vos needs --first-mask")
+    if a.task == "vos" and not (a.first_mask or a.mask):
+        ap.error("--task vos needs --first-mask (or --mask T PNG)")
+    if (a.both_ways or a.confidence or a.override != "new") and not a.mask:
+        ap.error("--both-ways, --override and --confidence go with --mask T PNG")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
         ap.error("--yuv-matrix goes with a .y4m clip")
     if a.trails is not None and a.task != "points":

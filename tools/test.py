@@ -3,6 +3,7 @@
 
     python tools/test.py CONFIG --task davis [--checkpoint CKPT] [--videos 4 --frames 8 --size 256 256]
     python tools/test.py CONFIG --task vos --data-root DAVIS_2017_DIR     # masks: J&F (test_cfg_vos, else test_cfg_davis's keys)
+    python tools/test.py CONFIG --task ytvos --data-root YOUTUBE_VOS_DIR [--out-dir DIR]   # masks from the frames where objects first appear
     python tools/test.py CONFIG --task vos --data-root DIR --eval-arc HRVanillaTracker    # the config's eval_arc overridden
     python tools/test.py CONFIG --task davis --occlusion [--cycle-thresh 1.0] [--occluder]   # predicted visibility: DESIGN.md section 13
     python tools/test.py CONFIG --task davis --chain [--chain-visibility frame|consistency] [--query-mode strided]   # flow chaining: section 18
@@ -28,7 +29,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fgvc_amd.mmpt_api as api  # noqa: E402
 from fgvc_amd import apis, metrics  # noqa: E402
-from fgvc_amd.datasets import Davis2017, davis_evaluate  # noqa: E402
+from fgvc_amd.datasets import Davis2017, YoutubeVos, davis_evaluate, ytvos_run  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
 from fgvc_amd.datasets import MapsAsCoords, badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
 
@@ -97,6 +98,10 @@ def main():
         if not a.data_root:
             raise SystemExit("--task vos needs --data-root (DAVIS-2017 layout: ImageSets/2017/val.txt, JPEGImages/480p, Annotations/480p)")
         dataset = None
+    elif a.task == "ytvos":
+        if not a.data_root:
+            raise SystemExit("--task ytvos needs --data-root (YouTube-VOS layout: JPEGImages/<video>, Annotations/<video>, meta.json)")
+        dataset = None
     elif a.task in ("jhmdb", "badja"):
         if not a.data_root:
             raise SystemExit("--task jhmdb needs --data-root (JHMDB frames + joint_positions + val_list.txt); --task badja the BADJA root "
@@ -108,11 +113,15 @@ def main():
         dataset = SyntheticTapVid(a.videos, a.frames, tuple(a.size), a.points, a.query_mode, device=dev, occluder=a.occluder, raw=a.raw_frames)
     loader = StridedLoader(dataset, rank, world) if dataset is not None else None          # :124-134
     key = "test_cfg_" + a.task                                                               # :135
-    if key not in cfg and a.task in ("jhmdb", "badja", "vos") and "test_cfg_davis" in cfg:
+    if key not in cfg and a.task in ("jhmdb", "badja", "vos", "ytvos") and "test_cfg_davis" in cfg:
         key = "test_cfg_davis"         # the pose task of DEFAULT_CFG (and of configs without a test_cfg_jhmdb) tracks with the TAP-Vid settings
+    if a.task == "ytvos" and key not in cfg and "test_cfg_vos" in cfg:
+        key = "test_cfg_vos"
     if key not in cfg:
         raise SystemExit(f"the config has no '{key}' (tasks it defines: {sorted(k[9:] for k in cfg if k.startswith('test_cfg_'))})")
     test_cfg = cfg[key]
+    if a.task == "ytvos" and test_cfg.get("refs", None) is None:
+        test_cfg = dict(test_cfg, refs=dict(direction="forward", override="new"))    # objects are annotated where they first appear
     heatmap = a.task in ("jhmdb", "badja") and a.pose_form in ("heatmap", "softmap")
     softmap = heatmap and a.pose_form == "softmap"
     if a.dump_maps and not softmap:
@@ -142,7 +151,7 @@ def main():
     if a.raw_frames:
         if distributed:
             raise SystemExit("--raw-frames runs on one GPU (--launcher none)")
-        net_size = {"vos": None, **POSE_SIZE}.get(a.task, tuple(a.size))                                  # what each dataset resizes to
+        net_size = {"vos": None, "ytvos": None, **POSE_SIZE}.get(a.task, tuple(a.size))                                  # what each dataset resizes to
         test_cfg = dict(test_cfg, input=dict(type="rgb8", size=net_size, layout="thwc"))
     if a.gpu_metrics:
         if a.task != "vos":
@@ -178,6 +187,15 @@ def main():
             if a.out:
                 with open(a.out, "w") as f:
                     json.dump(jf, f, indent=1)
+        outputs = None
+    elif a.task == "ytvos":    # YouTube-VOS: objects annotated at the frame they first appear in (test_cfg.refs); parity unpinned
+        if rank == 0:
+            res = ytvos_run(model, YoutubeVos(a.data_root, device=dev, raw=a.raw_frames), a.out_dir)
+            print(json.dumps({"videos": len(res["videos"]), "out_dir": a.out_dir,
+                              "J&F-Mean": None if res["jf"] is None else round(res["jf"]["J&F-Mean"], 4)}))
+            if a.out:
+                with open(a.out, "w") as f:
+                    json.dump(res, f, indent=1)
         outputs = None
     elif a.task == "badja":      # animal pose tracking: the 20 annotated SMAL joints of frame 0 are the query points (datasets.BadjaPoses)
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
