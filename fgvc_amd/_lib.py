@@ -107,6 +107,9 @@ SIGNATURES = {
     "fgvc_render_trails_u8": (_i, [_p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _i, _i, _i, _p, C.c_int64, C.c_int64, _p, _i, _i,
                                    _p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _p, _i, _i, _p, _i, C.c_double, C.c_double, C.c_double,
                                    _p, _p, _p]),
+    "fgvc_render_pose_u8": (_i, [_p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _i, _i, _i, _p, C.c_int64, C.c_int64, _p, _i, _i,
+                                 _p, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _p, _i, _i, _p, _p, _i, _p, C.c_double, C.c_double,
+                                 C.c_double, C.c_double, _p, _i, _i, C.c_int64, C.c_int64, C.c_int64, _p, C.c_double, C.c_double, _p]),
     "fgvc_render_tile_rows": (_i, []),
     "fgvc_render_tile_cols": (_i, []),
     "fgvc_c2f_refine_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
@@ -127,6 +130,7 @@ SIGNATURES = {
     "fgvc_seg_soft_labels_f64": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_heatmap_coords_workspace_bytes": (C.c_size_t, [_i, _i]),
     "fgvc_heatmap_coords_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "fgvc_heatmap_coords_peak_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fgvc_softmap_readout_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 

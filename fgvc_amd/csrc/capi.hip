@@ -62,6 +62,10 @@ void render_tile(int*, int*);
 int render_trails_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
                          const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
                          int, const double*, int, int, double, double, const double*, const uint8_t*, hipStream_t);
+int render_pose_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
+                       const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
+                       int, const double*, const int32_t*, int, const uint8_t*, int, double, double, double, const void*, int, int, long long,
+                       long long, long long, const uint8_t*, double, double, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -842,6 +846,71 @@ int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_
   return render_trails_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
                               palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
                               visibles_stride_t, colors, P, radius, icon, trail, reach, ro2, g, fade, time_colors, (hipStream_t)stream);
+}
+
+int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                        int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                        const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                        int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                        const uint8_t* colors, int P, int radius, const double* icon, const int32_t* skeleton, int E,
+                        const uint8_t* limb_colors, double limb_width, double ro2, double g, double limb_alpha, const void* heat, int heat_f64,
+                        int K, int64_t heat_stride_t, int64_t heat_stride_k, int64_t heat_stride_y, const uint8_t* heat_colors,
+                        double heat_gain, double heat_alpha, void* stream) {
+  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: negative size (T=%d, %d x %d)", T, h, w);
+  FGVC_REQUIRE(P >= 0 && E >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: P=%d, E=%d", P, E);
+  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
+  FGVC_REQUIRE(E < (1 << 30), FGVC_ERR_UNSUPPORTED, "fgvc_render_pose_u8: E = %d limbs, 2^30 or more", E);
+  FGVC_REQUIRE(!heat || (K >= 1 && K <= 256), FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: K=%d heat maps (1 .. 256)", K);
+  if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
+  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: null pointer");
+  const long long row = 3ll * w;
+  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_pose_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
+  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
+               "fgvc_render_pose_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
+               (long long)out_stride_t, (long long)out_stride_y, h, w);
+  if (ids) {
+    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: ids without a palette");
+    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: alpha=%d (0 .. 256)", alpha);
+    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_pose_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
+  }
+  if (heat) {
+    FGVC_REQUIRE(heat_colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat without heat_colors");
+    FGVC_REQUIRE(isfinite(heat_gain) && heat_gain > 0.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat_gain=%g (finite, > 0)", heat_gain);
+    FGVC_REQUIRE(heat_alpha >= 0.0 && heat_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat_alpha=%g (0 .. 1)", heat_alpha);
+    FGVC_REQUIRE(heat_stride_y >= w && (T == 1 || heat_stride_t >= 0) && (K == 1 || heat_stride_k >= 0), FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_pose_u8: heat: a row stride of at least w = %d elements and non-negative strides, got %lld, %lld, %lld", w,
+                 (long long)heat_stride_t, (long long)heat_stride_k, (long long)heat_stride_y);
+    FGVC_REQUIRE((reinterpret_cast<uintptr_t>(heat) & (heat_f64 ? 7u : 3u)) == 0, FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_pose_u8: heat must be aligned to its element size");
+  }
+  if (P > 0 && (E > 0 || icon)) {
+    FGVC_REQUIRE(tracks, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limbs or dots without tracks");
+    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: tracks: a negative frame stride (%lld)",
+                 (long long)tracks_stride_t);
+    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_pose_u8: visibles: a negative frame stride (%lld)", (long long)visibles_stride_t);
+    if (E > 0) {
+      FGVC_REQUIRE(skeleton && limb_colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limbs without a skeleton or limb_colors");
+      FGVC_REQUIRE(limb_width >= 1.0 && limb_width <= 16.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limb_width=%g (1 .. 16)", limb_width);
+      FGVC_REQUIRE(limb_alpha >= 0.0 && limb_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limb_alpha=%g (0 .. 1)", limb_alpha);
+      FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: ro2=%g, g=%g (both positive, ro2 <= 81)", ro2, g);
+      FGVC_REQUIRE((reinterpret_cast<uintptr_t>(skeleton) & 3u) == 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: skeleton must be 4-byte aligned");
+    }
+    if (icon) {
+      FGVC_REQUIRE(colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: dots without colors");
+      FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: radius=%d (at least 1)", radius);
+      FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_pose_u8: radius=%d beyond 31", radius);
+    }
+    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon)) & 7u) == 0, FGVC_ERR_INVALID_ARG,
+                 "fgvc_render_pose_u8: tracks and icon must be 8-byte aligned");
+  }
+  const int reach = E > 0 ? (int)ceil(limb_width / 2.0 + 0.5) : 0;    // ceil(ro): what a limb's box is grown by
+  return render_pose_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                            palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
+                            visibles_stride_t, colors, P, radius, icon, skeleton, E, limb_colors, reach, ro2, g, limb_alpha, heat, heat_f64 != 0,
+                            heat ? K : 0, heat_stride_t, heat_stride_k, heat_stride_y, heat_colors, heat_gain, heat_alpha, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

@@ -483,57 +483,20 @@ __global__ __launch_bounds__(HM_BLOCK) void heatmap_band0_kernel(const T* __rest
 // Read-out stage 2: one thread per (frame, joint) map merges its bands and writes x to coords[0][k][f], y to coords[1][k][f].
 // f64 != 0: img2coord on a float64 stack (the map was float64): top-5 normalisation in f64.  Else every value is an f32 and the
 // normalisation is f32, as post.hip's merge.  Sums in the ascending order of np.sum over argsort[-5:].
+// (heatmap_merge_body.inc: shared with heatmap_peak_merge_kernel, which also stores every map's largest value)
 __global__ __launch_bounds__(64) void heatmap_merge_kernel(const double* __restrict__ part_v, const int* __restrict__ part_i,
                                                            const double* __restrict__ part_sum, int nbands, int K, int T, int w0, int f64,
                                                            double* __restrict__ coords) {
-  const int m = blockIdx.x * 64 + threadIdx.x;
-  if (m >= T * K) return;
-  const int f = m / K, k = m - f * K;
-  Top5 top;
-  top.init();
-  double sum = 0.0;
-  for (int b = 0; b < nbands; ++b) {
-    const size_t o = (size_t)m * nbands + b;
-    sum += part_sum[o];
-    for (int j = 0; j < HM_K; ++j) {
-      const int id = part_i[o * HM_K + j];
-      const double v = part_v[o * HM_K + j];
-      if (id >= 0 && top.accepts(v, id)) top.insert(v, id);
-    }
-  }
-  double* ox = coords + (size_t)k * T + f;
-  double* oy = ox + (size_t)K * T;
-  if (sum == 0.0) {   // np.sum(map) == 0 (:189)
-    *ox = -1.0;
-    *oy = -1.0;
-    return;
-  }
-  double ax = 0.0, ay = 0.0;
-  if (f64) {
-    double tot = 0.0;
-#pragma unroll
-    for (int j = HM_K - 1; j >= 0; --j) tot += top.v[j];
-    tot += 1e-9;
-#pragma unroll
-    for (int j = HM_K - 1; j >= 0; --j) {
-      const double wgt = top.v[j] / tot;
-      ax += (double)(top.ix[j] % w0) * wgt;
-      ay += (double)(top.ix[j] / w0) * wgt;
-    }
-  } else {
-    float tot = 0.f;
-#pragma unroll
-    for (int j = HM_K - 1; j >= 0; --j) tot += (float)top.v[j];
-    tot += 1e-9f;
-#pragma unroll
-    for (int j = HM_K - 1; j >= 0; --j) {
-      const float wgt = (float)top.v[j] / tot;
-      ax += (double)(top.ix[j] % w0) * (double)wgt;
-      ay += (double)(top.ix[j] / w0) * (double)wgt;
-    }
-  }
-  *ox = ax;
-  *oy = ay;
+  constexpr bool PEAK = false;
+  [[maybe_unused]] double* const peak = nullptr;
+#include "heatmap_merge_body.inc"
+}
+
+__global__ __launch_bounds__(64) void heatmap_peak_merge_kernel(const double* __restrict__ part_v, const int* __restrict__ part_i,
+                                                                const double* __restrict__ part_sum, int nbands, int K, int T, int w0,
+                                                                int f64, double* __restrict__ coords, double* __restrict__ peak) {
+  constexpr bool PEAK = true;
+#include "heatmap_merge_body.inc"
 }
 
 size_t heatmap_workspace_bytes(int T, int K) {
@@ -885,17 +848,22 @@ size_t fgvc_heatmap_coords_workspace_bytes(int T, int K) {
   return heatmap_workspace_bytes(T, K);
 }
 
-int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
-                            int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream) {
-  FGVC_REQUIRE(map0 && coords && (bank || T <= 1), FGVC_ERR_INVALID_ARG, "fgvc_heatmap_coords_f32: null pointer");
+}  // extern "C"
+
+// fgvc_heatmap_coords_f32 (peak null) and fgvc_heatmap_coords_peak_f32 (`name`: the one called, for its errors): one body, the merge
+// kernel with or without the peak's store
+static int heatmap_coords_entry(const char* name, const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm,
+                                int wm, int hp, int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, double* peak,
+                                void* workspace, void* stream) {
+  FGVC_REQUIRE(map0 && coords && (bank || T <= 1), FGVC_ERR_INVALID_ARG, "%s: null pointer", name);
   FGVC_REQUIRE(T >= 0 && T <= 65535 && Hf > 0 && Wf > 0 && K >= 1 && K <= 256 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_heatmap_coords_f32: bad shape (1 <= K <= 256, T <= 65535)");
+               "%s: bad shape (1 <= K <= 256, T <= 65535)", name);
   FGVC_REQUIRE(hm > 0 && wm > 0 && top >= 0 && left >= 0 && top + hm <= hp && left + wm <= wp, FGVC_ERR_INVALID_ARG,
-               "fgvc_heatmap_coords_f32: the map must lie inside the padded frame");
+               "%s: the map must lie inside the padded frame", name);
   FGVC_REQUIRE((long long)h0 * w0 >= HM_K && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_UNSUPPORTED,
-               "fgvc_heatmap_coords_f32: h0*w0 out of range (5 <= h0*w0 < 2^31)");
+               "%s: h0*w0 out of range (5 <= h0*w0 < 2^31)", name);
   FGVC_REQUIRE(workspace != nullptr || T == 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_heatmap_coords_f32: workspace of fgvc_heatmap_coords_workspace_bytes() bytes required");
+               "%s: workspace of fgvc_heatmap_coords_workspace_bytes() bytes required", name);
   if (T == 0) return FGVC_OK;
   HeatGeom g;
   g.K = K; g.Hf = Hf; g.Wf = Wf; g.hm = hm; g.wm = wm; g.hp = hp; g.wp = wp; g.top = top; g.left = left; g.h0 = h0; g.w0 = w0;
@@ -918,9 +886,28 @@ int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, i
     else
       heatmap_band_kernel<true><<<grid, HM_BLOCK, 0, s>>>(bank, g, part_v, part_i, part_sum);
   }
-  heatmap_merge_kernel<<<cdiv((int)maps, 64), 64, 0, s>>>(part_v, part_i, part_sum, HM_BANDS, K, T, w0, f64_arith, coords);
-  FGVC_CHECK_LAUNCH("fgvc_heatmap_coords_f32");
+  if (peak)
+    heatmap_peak_merge_kernel<<<cdiv((int)maps, 64), 64, 0, s>>>(part_v, part_i, part_sum, HM_BANDS, K, T, w0, f64_arith, coords, peak);
+  else
+    heatmap_merge_kernel<<<cdiv((int)maps, 64), 64, 0, s>>>(part_v, part_i, part_sum, HM_BANDS, K, T, w0, f64_arith, coords);
+  FGVC_CHECK_LAUNCH(name);
   return FGVC_OK;
+}
+
+extern "C" {
+
+int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                            int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream) {
+  return heatmap_coords_entry("fgvc_heatmap_coords_f32", bank, map0, map0_f64, T, Hf, Wf, K, hm, wm, hp, wp, top, left, h0, w0, f64_arith, coords,
+                              nullptr, workspace, stream);
+}
+
+int fgvc_heatmap_coords_peak_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                                 int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, double* peak, void* workspace,
+                                 void* stream) {
+  FGVC_REQUIRE(peak, FGVC_ERR_INVALID_ARG, "fgvc_heatmap_coords_peak_f32: null pointer");
+  return heatmap_coords_entry("fgvc_heatmap_coords_peak_f32", bank, map0, map0_f64, T, Hf, Wf, K, hm, wm, hp, wp, top, left, h0, w0, f64_arith,
+                              coords, peak, workspace, stream);
 }
 
 int fgvc_softmap_readout_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,

@@ -1,30 +1,19 @@
 // Motion trails: overlay, then every point's last L steps as anti-aliased line segments, then the dots, onto uint8
 // RGB video, all T frames in ONE launch -- fgvc_amd/viz.py's host backend, bit for bit.  The load, overlay, points and store are
-// render_body.hpp's; this file adds the stage between the overlay and the points.
-//   * on frame t a point has n = min(t, L) segments, s = t - n .. t - 1, segment s from tracks[i][s] + 0.5 to tracks[i][s + 1] + 0.5.  The
-//     workgroup walks the frame's P n candidate items (item = i n + k, s = t - n + k: point order, oldest first) RN_BLOCK at a time and
-//     compacts IN ITEM ORDER (ballot + prefix count per wave, wave totals through LDS) those whose two ends are visible, whose four
-//     coordinates are below 2^20 in magnitude (which NaN and the infinities are not) and whose box, grown by ceil(ro), meets the tile, into
-//     an LDS list: ax, ay, dx, dy, L2, the fade factor, the packed colour and the box cut to the tile (4 bytes).  56 bytes per item, 14 KB
-//     beside the point stage's 12 KB: 26.4 KB, six workgroups of 4 waves in a compute unit's 160 KB, which is also what its 79 VGPRs admit
-//     (six waves per SIMD);
-//   * every lane then walks the list for its 8 pixels: one integer compare of its 4 x 2 block against the item's box before any double,
-//     then per pixel the distance to the segment without a square root and with ONE division (correctly rounded: no fast-math),
-//       u = clamp(((px - ax) dx + (py - ay) dy) / L2, 0, 1) (0 when L2 == 0),  d2 = |p - (a + u d)|^2,  cov = clamp((ro2 - d2) g, 0, 1),
-//       v_c = (1 - cov fade) v_c + cov fade colour_c, truncated to uint8 after every segment;
-//     a pixel outside the box (floor of the smaller end - ceil(ro) .. ceil of the larger end + ceil(ro)) is ceil(ro) + 1 or more away from
-//     the segment in x or in y, so d2 - ro2 >= 2 ceil(ro) + 1 against a rounding error below 2^-10 at the 2^20 limit: its cov is exactly 0,
-//     it would keep its value, and leaving it out changes nothing.
+// render_body.hpp's; the stage between the overlay and the points is segments.hpp's (the compaction and the per-pixel rule, shared with
+// pose.hip's limbs); this file adds where a trail's items come from.
+//   * on frame t a point has n = min(t, L) segments, s = t - n .. t - 1, segment s from tracks[i][s] + 0.5 to tracks[i][s + 1] + 0.5: the
+//     frame's P n candidate items (item = i n + k, s = t - n + k: point order, oldest first), each with the fade factor of its age;
+//   * the list is 14 KB beside the point stage's 12 KB: 26.4 KB, six workgroups of 4 waves in a compute unit's 160 KB, which is also what
+//     its 79 VGPRs admit (six waves per SIMD).
 // Float64 with contraction off, every product and sum left to right.  No atomics, no second launch, no workspace.
-#include "render_body.hpp"
+#include "segments.hpp"
 
 #pragma clang fp contract(off)
 
 namespace fgvc {
 
 namespace {
-
-constexpr double TRAIL_LIMIT = 1048576.0;          // 2^20: beyond it a coordinate is not drawn (and every integer below is exact)
 
 struct TrailArgs {
   const double* tracks;        // never null here
@@ -37,104 +26,45 @@ struct TrailArgs {
   int P, L, reach;             // reach = ceil(ro)
 };
 
+// the item source of segments.hpp: item c of frame t is step s = s0 + c % n of point i = c / n
+struct TrailItems {
+  const TrailArgs& b;
+  int n, s0;
+  struct Item {
+    int i, s;
+  };
+
+  __device__ __forceinline__ void locate(int c, const RenderLane& k, int reach, Item& it, SegmentGeom& sg) const {
+    const int i = (int)((unsigned)c / (unsigned)n);
+    const int s = s0 + (c - i * n);
+    it.i = i;
+    it.s = s;
+    bool seen = true;
+    if (b.visibles) {
+      const uint8_t* q = b.visibles + (long long)i * b.vis_sp + (long long)s * b.vis_st;
+      seen = q[0] != 0 && q[b.vis_st] != 0;
+    }
+    if (seen) {
+      const double* p = b.tracks + (long long)i * b.trk_sp + (long long)s * b.trk_st;
+      segment_ends(p[0], p[1], p[b.trk_st], p[b.trk_st + 1], reach, k, sg);
+    }
+  }
+
+  __device__ __forceinline__ double factor(const Item& it, const RenderLane& k) const { return b.fade[k.t - 1 - it.s]; }
+
+  __device__ __forceinline__ uint32_t colour(const Item& it, const RenderLane&) const {
+    const uint8_t* col = b.time_colors ? b.time_colors + (long long)it.s * 3 : b.colors + (long long)it.i * 3;
+    return (uint32_t)col[0] | (uint32_t)col[1] << 8 | (uint32_t)col[2] << 16;
+  }
+};
+
 struct TrailStage {
   TrailArgs b;
 
   __device__ __forceinline__ void operator()(unsigned (&v)[RN_LANE_ROWS][RN_PX * 3], const RenderLane& k) const {
-    __shared__ double l_ax[RN_BLOCK], l_ay[RN_BLOCK], l_dx[RN_BLOCK], l_dy[RN_BLOCK], l_l2[RN_BLOCK], l_fade[RN_BLOCK];
-    __shared__ uint32_t l_col[RN_BLOCK], l_box[RN_BLOCK];
-    __shared__ int wave_n[RN_WAVES];
     const int n = imin(k.t, b.L);                                     // segments per point on this frame (uniform in the workgroup)
     if (n <= 0) return;
-    const int s0 = k.t - n;
-    const int items = b.P * n;                                        // P L < 2^31 (checked on the host)
-    const int lx = k.lane * RN_PX, ly = k.wave * RN_LANE_ROWS;        // the lane's block inside the tile
-    for (int base = 0; base < items; base += RN_BLOCK) {
-      const int c = base + k.tid;
-      bool take = false;
-      double ax = 0.0, ay = 0.0, dx = 0.0, dy = 0.0;
-      uint32_t box = 0;
-      int i = 0, s = 0;
-      if (c < items) {
-        i = (int)((unsigned)c / (unsigned)n);
-        s = s0 + (c - i * n);
-        bool seen = true;
-        if (b.visibles) {
-          const uint8_t* q = b.visibles + (long long)i * b.vis_sp + (long long)s * b.vis_st;
-          seen = q[0] != 0 && q[b.vis_st] != 0;
-        }
-        if (seen) {
-          const double* p = b.tracks + (long long)i * b.trk_sp + (long long)s * b.trk_st;
-          const double x0 = p[0], y0 = p[1], x1 = p[b.trk_st], y1 = p[b.trk_st + 1];
-          if (fabs(x0) < TRAIL_LIMIT && fabs(y0) < TRAIL_LIMIT && fabs(x1) < TRAIL_LIMIT && fabs(y1) < TRAIL_LIMIT) {   // false for NaN
-            ax = x0 + 0.5;
-            ay = y0 + 0.5;
-            const double bx = x1 + 0.5, by = y1 + 0.5;
-            dx = bx - ax;
-            dy = by - ay;
-            const int xlo = (int)floor(fmin(ax, bx)) - b.reach - k.tx0, xhi = (int)ceil(fmax(ax, bx)) + b.reach - k.tx0;   // in the tile's frame
-            const int ylo = (int)floor(fmin(ay, by)) - b.reach - k.ty0, yhi = (int)ceil(fmax(ay, by)) + b.reach - k.ty0;
-            take = xhi >= 0 && xlo < RN_COLS && yhi >= 0 && ylo < RN_ROWS;
-            box = (uint32_t)imax(xlo, 0) | (uint32_t)imin(xhi, RN_COLS - 1) << 8 | (uint32_t)imax(ylo, 0) << 16 |
-                  (uint32_t)imin(yhi, RN_ROWS - 1) << 24;
-          }
-        }
-      }
-      const unsigned long long bal = __ballot(take);
-      const int before = __popcll(bal & ((1ull << k.lane) - 1ull));
-      if (k.lane == 0) wave_n[k.wave] = __popcll(bal);
-      __syncthreads();
-      int off = 0, kept = 0;
-#pragma unroll
-      for (int wv = 0; wv < RN_WAVES; ++wv) {
-        const int cnt = wave_n[wv];
-        off += wv < k.wave ? cnt : 0;
-        kept += cnt;
-      }
-      if (take) {
-        const int e = off + before;
-        l_ax[e] = ax;
-        l_ay[e] = ay;
-        l_dx[e] = dx;
-        l_dy[e] = dy;
-        l_l2[e] = dx * dx + dy * dy;
-        l_fade[e] = b.fade[k.t - 1 - s];
-        const uint8_t* col = b.time_colors ? b.time_colors + (long long)s * 3 : b.colors + (long long)i * 3;
-        l_col[e] = (uint32_t)col[0] | (uint32_t)col[1] << 8 | (uint32_t)col[2] << 16;
-        l_box[e] = box;
-      }
-      __syncthreads();
-      for (int e = 0; e < kept; ++e) {
-        const uint32_t bb = l_box[e];
-        const int bx0 = (int)(bb & 255u), bx1 = (int)((bb >> 8) & 255u), by0 = (int)((bb >> 16) & 255u), by1 = (int)(bb >> 24);
-        if (lx + RN_PX - 1 < bx0 || lx > bx1 || ly + RN_LANE_ROWS - 1 < by0 || ly > by1) continue;
-        const double sax = l_ax[e], say = l_ay[e], sdx = l_dx[e], sdy = l_dy[e], l2 = l_l2[e], fd = l_fade[e];
-        const uint32_t col = l_col[e];
-#pragma unroll
-        for (int rr = 0; rr < RN_LANE_ROWS; ++rr) {
-          if (ly + rr < by0 || ly + rr > by1) continue;
-          const double py = (double)(k.ty0 + ly + rr);
-#pragma unroll
-          for (int j = 0; j < RN_PX; ++j) {
-            if (lx + j < bx0 || lx + j > bx1) continue;
-            const double px = (double)(k.tx0 + lx + j);
-            const double q = ((px - sax) * sdx + (py - say) * sdy) / l2;
-            const double u = l2 == 0.0 ? 0.0 : fmin(fmax(q, 0.0), 1.0);
-            const double ex = px - (sax + u * sdx), ey = py - (say + u * sdy);
-            const double d2 = ex * ex + ey * ey;
-            const double cov = fmin(fmax((b.ro2 - d2) * b.g, 0.0), 1.0);
-            if (!(cov > 0.0)) continue;                               // the pixel keeps its value
-            const double op = cov * fd, keep = 1.0 - op;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-              const double cv = (double)((col >> (8 * ch)) & 255u);
-              v[rr][3 * j + ch] = (unsigned)(int)(keep * (double)v[rr][3 * j + ch] + op * cv);
-            }
-          }
-        }
-      }
-      __syncthreads();                                                // the list is rewritten by the next round
-    }
+    segment_stage(v, k, TrailItems{b, n, k.t - n}, b.P * n, b.ro2, b.g, b.reach);   // P L < 2^31 (checked on the host)
   }
 };
 

@@ -924,16 +924,74 @@ def propagate_soft_bank(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.T
     return bank, sw
 
 
+@dataclass
+class PoseConfig:
+    """test_cfg.pose = dict(confidence=True, keep_field=False), parsed."""
+    confidence: bool = True
+    keep_field: bool = False
+
+
+def parse_pose(spec) -> Optional[PoseConfig]:
+    """None -> None (the option is off: the coords=True call leaves last_pose None).  A mapping -> PoseConfig; an unknown key or value
+    raises ValueError, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.pose: a dict such as dict(confidence=True, keep_field=False), got {type(spec).__name__}")
+    spec = dict(spec)
+    confidence, keep_field = spec.pop("confidence", True), spec.pop("keep_field", False)
+    if spec:
+        raise ValueError(f"test_cfg.pose: unknown key(s) {sorted(spec)} (confidence, keep_field)")
+    if not isinstance(confidence, bool):
+        raise ValueError(f"test_cfg.pose: confidence={confidence!r} (True or False)")
+    if not isinstance(keep_field, bool):
+        raise ValueError(f"test_cfg.pose: keep_field={keep_field!r} (True or False)")
+    return PoseConfig(confidence, keep_field)
+
+
+@dataclass
+class PoseField:
+    """What the coordinate read-out of one clip scanned, kept on the device (test_cfg.pose.keep_field=True): the label bank (T, HfWf, K) f32,
+    the first-frame map (K, hm, wm) and the geometry.  maps() makes the full-resolution maps of a frame range from them, without a second
+    model call: T K h0 w0 values never have to exist at once."""
+    bank: torch.Tensor
+    heat: torch.Tensor
+    Hf: int
+    Wf: int
+    map_pad: Tuple[int, int, int, int]
+    out_shape: Tuple[int, int]
+
+    @property
+    def num_frames(self) -> int:
+        return int(self.bank.shape[0])
+
+    @property
+    def num_joints(self) -> int:
+        return int(self.heat.shape[0])
+
+    def maps(self, f_begin: int = 0, f_end: Optional[int] = None, out_dtype: Optional[torch.dtype] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Frames [f_begin, f_end) of the maps, (f_end - f_begin, K, h0, w0) on the device: ops.softmap_readout, what the return_maps=True
+        call gives for those frames, bit for bit."""
+        f_end = self.num_frames if f_end is None else int(f_end)
+        return ops.softmap_readout(self.bank, self.heat, self.Hf, self.Wf, self.map_pad, self.out_shape, frames=(int(f_begin), f_end),
+                                   out_dtype=out_dtype, out=out)
+
+
 def propagate_heatmaps(feats_hwc: torch.Tensor, Hf: int, Wf: int, heat: torch.Tensor, map_pad: Tuple[int, int, int, int],
                        out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
-                       events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+                       events: Optional[dict] = None, affinity_stats: Optional[dict] = None, peak: bool = False,
+                       field_out: Optional[list] = None):
     """Soft first-frame labels read out as joint coordinates for one clip (test_cfg.coords=True): propagate_soft_bank's arguments and
     out_shape = (h0, w0).  Returns (2, K, T) float64 on the device = img2coord of the stacked maps (:814-818); frame 0 is the padded map,
-    not unpadded (:712-716)."""
+    not unpadded (:712-716).  peak=True: (coords, peak (K, T) float64), every map's largest value (ops.heatmap_coords).  field_out: a list
+    that receives the clip's PoseField."""
     bank, _ = propagate_soft_bank(feats_hwc, Hf, Wf, heat, map_pad, cfg, channels, stats_out, events, affinity_stats)
     _record(events, "readout")
-    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape)
+    coords = ops.heatmap_coords(bank, heat, Hf, Wf, map_pad, out_shape, peak=peak)
     _record(events, "end")
+    if field_out is not None:
+        field_out.append(PoseField(bank, heat, Hf, Wf, tuple(map_pad), tuple(out_shape)))
     return coords
 
 

@@ -152,6 +152,8 @@ class VanillaTracker(BaseTracker):
         self.last_flow = None              # forward_test_flow's dict of the last points call with test_cfg.chain set, else None
         self.refs_cfg = engine.parse_refs(self.test_cfg.get("refs", None))         # test_cfg.refs (None: ref_seg_map is one tensor for frame 0)
         self.last_confidence = None        # dict(conf, stats, frame_score) of the last mask call with test_cfg.refs.confidence=True, else None
+        self.pose_cfg = engine.parse_pose(self.test_cfg.get("pose", None))         # test_cfg.pose (None: the coords=True call returns coordinates only)
+        self.last_pose = None              # dict(peak, field) of the last coords=True call with test_cfg.pose set, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -691,10 +693,18 @@ class VanillaTracker(BaseTracker):
         frames, map_pad, out_shape = self._heat_inputs(imgs, heat, img_meta)
         feats, Hf, Wf = self._label_feats(frames)
         stats, self.label_stats = [], {}
+        pose, self.last_pose = self.pose_cfg, None
+        field = [] if pose is not None and pose.keep_field else None
         coords = engine.propagate_heatmaps(feats, Hf, Wf, heat, map_pad, out_shape, cfg, channels=self.feat_channels, stats_out=stats,
-                                           affinity_stats=self.label_stats)
+                                           affinity_stats=self.label_stats, peak=pose is not None and pose.confidence, field_out=field)
         self._refine_stats = stats or None
         self._check_kernels()
+        if pose is not None:
+            peak = None
+            if pose.confidence:
+                coords, peak = coords
+                peak = peak.cpu().numpy()
+            self.last_pose = dict(peak=peak, field=field[0] if field else None)
         return [coords.cpu().numpy()]
 
     def _maps_budget(self) -> int:

@@ -1472,11 +1472,13 @@ def seg_soft_labels(heat: torch.Tensor, pad: Tuple[int, int, int, int], Hf: int,
 
 
 def heatmap_coords(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, pad: Tuple[int, int, int, int],
-                   out_shape: Tuple[int, int], f64_arith: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out_shape: Tuple[int, int], f64_arith: Optional[bool] = None, out: Optional[torch.Tensor] = None, peak: bool = False):
     """img2coord of the T frames the reference stacks (vanilla_tracker.py:712-716, :770-784, :803, :814-818) -> (2, K, T) f64.
     Frame 0 = bilinear(F.pad(heat, pad) -> out_shape) in heat's dtype, not unpadded; frame f >= 1 = bilinear to the padded size, unpad,
     bilinear to out_shape, in f32, from bank[f] (T, HfWf, K) f32 (bank[0] is not read).  The top-5 normalisation runs in f64 when
-    `f64_arith` (default: heat is float64, as np.stack makes it), else in f32.  No (K, h0, w0) map is built."""
+    `f64_arith` (default: heat is float64, as np.stack makes it), else in f32.  No (K, h0, w0) map is built.
+    peak=True: (coords, peak (K, T) f64) from fgvc_heatmap_coords_peak_f32: the same coordinates, and every map's largest value, the
+    softmap_readout(...).amax((2, 3)) of that map (frame 0 in heat's dtype, later frames f32, widened)."""
     heat = _heat(heat)
     bank = _chk(bank, torch.float32, "bank")
     K, hm, wm = heat.shape
@@ -1491,9 +1493,15 @@ def heatmap_coords(bank: torch.Tensor, heat: torch.Tensor, Hf: int, Wf: int, pad
     else:
         assert out.is_contiguous() and out.shape == (2, K, T) and out.dtype == torch.float64
     ws = torch.empty((max(_lib.load().fgvc_heatmap_coords_workspace_bytes(T, K), 8) + 7) // 8, device=heat.device, dtype=torch.float64)
-    _lib.call("fgvc_heatmap_coords_f32", _ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm,
-              hm + lh + uh, wm + lw + uw, lh, lw, h0, w0, int(bool(f64_arith)), _ptr(out), _ptr(ws), _stream(heat))
-    return out
+    head = (_ptr(bank), _ptr(heat), int(heat.dtype == torch.float64), T, Hf, Wf, K, hm, wm, hm + lh + uh, wm + lw + uw, lh, lw, h0, w0,
+            int(bool(f64_arith)), _ptr(out))
+    if not peak:
+        _lib.call("fgvc_heatmap_coords_f32", *head, _ptr(ws), _stream(heat))
+        return out
+    pk = torch.empty((K, T), device=heat.device, dtype=torch.float64)
+    if T > 0:
+        _lib.call("fgvc_heatmap_coords_peak_f32", *head, _ptr(pk), _ptr(ws), _stream(heat))
+    return out, pk
 
 
 def softmap_readout(bank: Optional[torch.Tensor], heat: torch.Tensor, Hf: int, Wf: int, pad: Tuple[int, int, int, int],
@@ -1837,8 +1845,9 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
     return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, None)
 
 
-def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, trails):
-    """render_frames (trails None) and render_trails (trails = (L, linewidth, fade, time_colors, dots)): one set of checks, one launch."""
+def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, trails, pose=None):
+    """render_frames (trails None), render_trails (trails = (L, linewidth, fade, time_colors, dots)) and render_pose (trails = (.., dots),
+    pose = its stage's arguments): one set of checks, one launch."""
     from . import viz
     if not frames_u8.is_cuda:
         raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
@@ -1919,6 +1928,11 @@ def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, r
         return None if x is None else _ptr(x)
     head = (_ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W, ptr(m), m_st, m_sy, ptr(pal), al, ct,
             ptr(tr), tr_sp, tr_st, ptr(vis), v_sp, v_st, ptr(col), int(P or 0), int(r or 0), ptr(icon))
+    if pose is not None:
+        tail, hold = pose(P or 0, col)
+        _lib.call("fgvc_render_pose_u8", *head, *tail, _stream(f))
+        del hold
+        return out
     if trails is None:
         _lib.call("fgvc_render_frames_u8", *head, _stream(f))
         return out
@@ -1960,3 +1974,81 @@ def render_trails(frames_u8: torch.Tensor, tracks: torch.Tensor, visibles: Optio
             raise ValueError(f"time_colors: {(max(T - 1, 0), 3)} on {dev}, got {tuple(time_colors.shape)} on {time_colors.device}")
         time_colors = time_colors.contiguous()
     return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, (L, lw, fade, time_colors, bool(dots)))
+
+
+def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, visibles: Optional[torch.Tensor] = None,
+                colors: Optional[torch.Tensor] = None, skeleton: Optional[torch.Tensor] = None, limb_colors: Optional[torch.Tensor] = None,
+                limb_width: float = 2.0, limb_alpha: float = 1.0, heat: Optional[torch.Tensor] = None,
+                heat_colors: Optional[torch.Tensor] = None, heat_gain: float = 1.0, heat_alpha: float = 0.5,
+                ids: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, alpha: int = 128, contour: bool = True,
+                radius: Optional[int] = None, dots: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """render_frames with a pose: the overlay, then the heat maps `heat` (T, K, H, W) float32 | float64 blended in
+    with heat_colors (K, 3) uint8 (None: viz.track_colors(K)), then the limbs of skeleton (E, 2) integer joint indices (numpy, a list or a
+    tensor; checked on the host, so a device tensor is read back: pass a host table where that matters) `limb_width`
+    (1 .. 16) pixels wide in limb_colors (E, 3) uint8 (None: the colour of each edge's second joint), then (dots=True) the dots --
+    viz.render(skeleton=..., heat=...)'s host backend bit for bit, in one launch of fgvc_render_pose_u8 on the current stream.  The maps
+    are read through their frame, channel and row strides (a time slice, a channel-strided view or a window is not copied; a row's values
+    must be contiguous).  Every other argument is render_frames'; with dots=False `radius` is not used.  Neither skeleton nor heat: the
+    bytes of render_frames."""
+    from . import viz
+    if skeleton is not None and tracks is None:
+        raise ValueError("skeleton: needs tracks (P, T, 2), got None")
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames_u8: (T, H, W, 3), got {tuple(frames_u8.shape)}")
+    dev = frames_u8.device
+    T, H, W, _ = frames_u8.shape
+    P = tracks.shape[0] if tracks is not None and tracks.dim() == 3 else 0
+    hargs = (None, 0, 0, 0, 0, 0, None, 1.0, 0.0)
+    if heat is not None:
+        gain, h_alpha = viz._check_heat_consts(heat_gain, heat_alpha)
+        if not isinstance(heat, torch.Tensor) or heat.device != dev:
+            raise ValueError(f"heat: a tensor on {dev} with the frames")
+        if heat.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"heat: expected float32 or float64, got {heat.dtype}")
+        if heat.dim() != 4 or (heat.shape[0], heat.shape[2], heat.shape[3]) != (T, H, W):
+            raise ValueError(f"heat: ({T}, K, {H}, {W}) to go with the frames, got {tuple(heat.shape)}")
+        K = heat.shape[1]
+        if not 1 <= K <= viz.MAX_HEAT_MAPS:
+            raise ValueError(f"heat: K={K} maps (1 .. {viz.MAX_HEAT_MAPS})")
+        if heat.numel() and (heat.stride(3) != 1 or heat.stride(2) < W or min(heat.stride(0), heat.stride(1)) < 0):
+            heat = heat.contiguous()
+        if heat_colors is None:
+            heat_colors = torch.from_numpy(viz.track_colors(K)).to(dev)
+        if heat_colors.dtype != torch.uint8:
+            raise TypeError(f"heat_colors: expected torch.uint8, got {heat_colors.dtype}")
+        if tuple(heat_colors.shape) != (K, 3) or heat_colors.device != dev:
+            raise ValueError(f"heat_colors: {(K, 3)} on {dev} to go with the maps, got {tuple(heat_colors.shape)} on {heat_colors.device}")
+        heat_colors = heat_colors.contiguous()
+        hargs = (heat, int(heat.dtype == torch.float64), K, heat.stride(0), heat.stride(1), heat.stride(2), heat_colors, gain, h_alpha)
+    largs = None
+    if skeleton is not None:
+        lw, l_alpha = viz._check_limb_consts(limb_width, limb_alpha)
+        # the table is checked on the host (the kernel skips, never reads, an edge outside 0 .. P - 1) and kept on the device per distinct
+        # table: a skeleton given as numpy or a list costs no transfer after its first call; a device tensor is read back every call
+        host = skeleton.detach().cpu().numpy() if isinstance(skeleton, torch.Tensor) else skeleton
+        edges = viz._check_skeleton(host, P)
+        E = edges.shape[0]
+        sk = _render_table(("skeleton", edges.tobytes()), dev, lambda: edges) if E else None
+        if limb_colors is not None:
+            if limb_colors.dtype != torch.uint8:
+                raise TypeError(f"limb_colors: expected torch.uint8, got {limb_colors.dtype}")
+            if tuple(limb_colors.shape) != (E, 3) or limb_colors.device != dev:
+                raise ValueError(f"limb_colors: {(E, 3)} on {dev} to go with the skeleton, got {tuple(limb_colors.shape)} on {limb_colors.device}")
+            limb_colors = limb_colors.contiguous()
+        ro2, g, _ = viz.trail_consts(lw)
+        largs = (sk, E, limb_colors, lw, ro2, g, l_alpha)
+
+    def stage(P, col):
+        """the arguments of fgvc_render_pose_u8 after `icon`, and the tensors they point into (held by the caller until the launch is
+        queued); col: the joints' colours as _render checked them"""
+        h, hold = hargs, ()
+        if largs is None or largs[1] == 0:
+            limbs = (None, 0, None, 2.0, 1.0, 1.0, 1.0)
+        else:
+            sk, E, lcol, lw, ro2, g, l_alpha = largs
+            if lcol is None:
+                lcol = col[sk[:, 1].long()].contiguous()                                  # the colour of every edge's second joint
+            limbs, hold = (_ptr(sk), E, _ptr(lcol), lw, ro2, g, l_alpha), (sk, lcol)
+        args = (*limbs, None if h[0] is None else _ptr(h[0]), h[1], h[2], h[3], h[4], h[5], None if h[6] is None else _ptr(h[6]), h[7], h[8])
+        return args, hold
+    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, (0, 0.0, None, None, bool(dots)), stage)

@@ -4,6 +4,8 @@
     overlay_masks(frames, ids, palette, alpha, contour)          object ids blended in, integer arithmetic, optional contour
     render(frames, ids=..., tracks=..., visibles=...)            overlay, then points; with trail=L: overlay, trails, points
     paint_trails(frames, point_tracks, visibles, trail=8)        every point's last L steps as a fading poly-line
+    paint_pose(frames, joints, visibles, skeleton=, heat=)       joint heat maps, limbs and dots
+    pose_tracks(coords), pose_visibles(coords, peak, min_conf)   the pose call's (2, K, T) coordinates as what the painters take
     frames_to_yuv420(frames, fmt, matrix, range, siting)         the painted frames as packed 8-bit 4:2:0 video
 
 backend='host' is plain numpy: it is the contract, the default, and works without a GPU.  backend='hip' is ONE launch of
@@ -27,6 +29,14 @@ fgvc_render_frames_u8 (ops.render_frames) and is held to the host backend with `
               v_c = (1 - op) v_c + op colour_c, truncated to uint8 after EVERY segment; cov <= 0: the pixel keeps its value
             float64, every product and sum left to right, no square root, one (correctly rounded) division.  Not OpenCV's LINE_AA rasteriser
             (the reference's draw_traj_on_image_py), whose bytes nothing here can pin; the joint of two consecutive segments is blended twice.
+  heat      (heat=(T, K, H, W) float32 | float64; after the overlay; backend='hip': ONE launch of fgvc_render_pose_u8, ops.render_pose)  per
+            pixel, for k = 0 .. K - 1 in order, with v = heat[t, k, y, x] widened to float64:
+              a   = min(max(v heat_gain, 0), 1) heat_alpha;  not a > 0 (zero, negative, NaN): the pixel keeps its value
+              v_c = (1 - a) v_c + a heat_colors[k][c], truncated to uint8 after EVERY map.
+  limbs     (skeleton=(E, 2) joint indices; after the heat, before the points; the same launch)  on frame t, for every edge e = (a, b) in
+            order: the trails' segment from A = track[a, t] + 0.5 to B = track[b, t] + 0.5 with linewidth = limb_width, drawn only if both
+            ends are visible on t and all four coordinates are below 2**20 in magnitude; op = cov limb_alpha, colour limb_colors[e] (None:
+            the colour of joint b), truncated to uint8 after EVERY limb.  a == b and a zero-length limb are discs (L2 == 0).
 Tracks are (x, y) in the pixel frame of `frames` (scale_tracks for tracks predicted at another size) and are converted to float64 first.
 """
 from __future__ import annotations
@@ -43,6 +53,10 @@ MAX_TRAIL = 64
 LINEWIDTHS = (1.0, 16.0)
 TRAIL_LIMIT = float(2 ** 20)    # a segment with a coordinate at or beyond it (or NaN) is not drawn
 TRAIL_COLOR_BY = ("track", "time")
+MAX_HEAT_MAPS = 256
+# The 14 limbs of a JHMDB puppet over the dataset's joint order -- 0 neck, 1 belly, 2 face, 3 right shoulder, 4 left shoulder, 5 right hip,
+# 6 left hip, 7 right elbow, 8 left elbow, 9 right knee, 10 left knee, 11 right wrist, 12 left wrist, 13 right ankle, 14 left ankle.
+_JHMDB_EDGES = ((0, 1), (0, 2), (0, 3), (0, 4), (1, 5), (1, 6), (3, 7), (7, 11), (4, 8), (8, 12), (5, 9), (9, 13), (6, 10), (10, 14))
 DOT_FRACTION = 0.015          # the reference's dot_size_as_fraction_of_min_edge
 SHARPNESS = 0.15
 
@@ -77,6 +91,18 @@ def track_colors(num_points: int) -> np.ndarray:
         r, g, b = colorsys.hls_to_rgb(((i * step) % P) / P, 0.55, 0.95)
         out[i] = (int(r * 255), int(g * 255), int(b * 255))
     return out
+
+
+def _jhmdb_skeleton() -> np.ndarray:
+    sk = np.array(_JHMDB_EDGES, np.int32)
+    sk.setflags(write=False)
+    return sk
+
+
+JHMDB_SKELETON = _jhmdb_skeleton()
+"""JHMDB_SKELETON: (14, 2) int32, read-only, zero-based: the limbs of the JHMDB puppet as a tree over its 15 joints (neck, belly, face, right
+and left shoulder, hip, elbow, knee, wrist, ankle).  Restated from the dataset's public description of its joint order; it is UNPINNED:
+no JHMDB data is available offline to check it against.  BADJA has no agreed skeleton: pass the edges."""
 
 
 def default_radius(h: int, w: int) -> int:
@@ -246,6 +272,95 @@ def _check_trails(trail, linewidth, fade, color_by):
     return L, lw, fade
 
 
+def _check_limb_consts(limb_width, limb_alpha):
+    """-> (limb_width, limb_alpha) as floats"""
+    try:
+        lw = float(limb_width)
+    except (TypeError, ValueError):
+        raise ValueError(f"limb_width={limb_width!r}: a number in {list(LINEWIDTHS)}") from None
+    if not LINEWIDTHS[0] <= lw <= LINEWIDTHS[1]:
+        raise ValueError(f"limb_width={limb_width!r}: a number in {list(LINEWIDTHS)}")
+    try:
+        la = float(limb_alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"limb_alpha={limb_alpha!r}: a number in [0, 1]") from None
+    if not 0.0 <= la <= 1.0:
+        raise ValueError(f"limb_alpha={limb_alpha!r}: a number in [0, 1]")
+    return lw, la
+
+
+def _check_skeleton(skeleton, num_joints: int) -> np.ndarray:
+    """-> (E, 2) int32, every index in 0 .. P - 1"""
+    sk = np.asarray(skeleton)
+    if sk.size == 0 and sk.ndim <= 2:
+        return np.zeros((0, 2), np.int32)
+    if sk.dtype.kind not in "iu":
+        raise TypeError(f"skeleton: (E, 2) integer joint indices, got {sk.dtype}")
+    if sk.ndim != 2 or sk.shape[1] != 2:
+        raise ValueError(f"skeleton: (E, 2) integer joint indices, got {sk.shape}")
+    P = int(num_joints)
+    for e, (a, b) in enumerate(sk.tolist()):
+        if not (0 <= a < P and 0 <= b < P):
+            raise ValueError(f"skeleton: edge {e} = ({a}, {b}) names a joint outside 0 .. {P - 1}")
+    return np.ascontiguousarray(sk, dtype=np.int32)
+
+
+def _check_limb_colors(limb_colors, skeleton, colors) -> np.ndarray:
+    """-> (E, 3) uint8; None: the colour of every edge's second joint"""
+    E = skeleton.shape[0]
+    if limb_colors is None:
+        return np.ascontiguousarray(colors[skeleton[:, 1]], dtype=np.uint8).reshape(E, 3)
+    if limb_colors.dtype.kind not in "iu":
+        raise TypeError(f"limb_colors: integers in 0 .. 255, got {limb_colors.dtype}")
+    if limb_colors.shape != (E, 3):
+        raise ValueError(f"limb_colors: {(E, 3)} to go with the skeleton, got {limb_colors.shape}")
+    if limb_colors.size and (int(limb_colors.min()) < 0 or int(limb_colors.max()) > 255):
+        raise ValueError("limb_colors: integers in 0 .. 255")
+    return limb_colors.astype(np.uint8)
+
+
+def _check_heat_consts(heat_gain, heat_alpha):
+    """-> (heat_gain, heat_alpha) as floats"""
+    try:
+        gain = float(heat_gain)
+    except (TypeError, ValueError):
+        raise ValueError(f"heat_gain={heat_gain!r}: a finite number > 0") from None
+    if not (np.isfinite(gain) and gain > 0.0):
+        raise ValueError(f"heat_gain={heat_gain!r}: a finite number > 0")
+    try:
+        ha = float(heat_alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"heat_alpha={heat_alpha!r}: a number in [0, 1]") from None
+    if not 0.0 <= ha <= 1.0:
+        raise ValueError(f"heat_alpha={heat_alpha!r}: a number in [0, 1]")
+    return gain, ha
+
+
+def _check_heat_shape(shape, dtype_name: str, frames_shape):
+    """heat's shape and type against the frames' (T, H, W, 3); -> K"""
+    T, H, W = (int(v) for v in frames_shape[:3])
+    if dtype_name not in ("float32", "float64"):
+        raise TypeError(f"heat: expected float32 or float64, got {dtype_name}")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 4 or (shape[0], shape[2], shape[3]) != (T, H, W):
+        raise ValueError(f"heat: ({T}, K, {H}, {W}) to go with the frames, got {shape}")
+    if not 1 <= shape[1] <= MAX_HEAT_MAPS:
+        raise ValueError(f"heat: K={shape[1]} maps (1 .. {MAX_HEAT_MAPS})")
+    return shape[1]
+
+
+def _check_heat_colors(heat_colors, K: int) -> np.ndarray:
+    if heat_colors is None:
+        return track_colors(K)
+    if heat_colors.dtype.kind not in "iu":
+        raise TypeError(f"heat_colors: integers in 0 .. 255, got {heat_colors.dtype}")
+    if heat_colors.shape != (K, 3):
+        raise ValueError(f"heat_colors: {(K, 3)} to go with the maps, got {heat_colors.shape}")
+    if heat_colors.size and (int(heat_colors.min()) < 0 or int(heat_colors.max()) > 255):
+        raise ValueError("heat_colors: integers in 0 .. 255")
+    return heat_colors.astype(np.uint8)
+
+
 def _backend(backend: str) -> bool:
     """True for 'hip' (after its refusal), False for 'host'."""
     if backend not in BACKENDS:
@@ -305,11 +420,32 @@ def _paint_host(video, tracks, visibles, colors, radius):
     return video
 
 
-def _trails_host(video, t, tracks, visibles, colors, L, ro2, g, reach, fade, time_colors):
-    """Frame t's trails into video[t] (H, W, 3) uint8: the module text's rule, a segment at a time on the part of its box (grown by
-    ceil(ro): outside it cov is exactly 0) inside the image."""
-    image = video[t]
+def _segment_host(image, ax, ay, bx, by, ro2, g, reach, factor, colour):
+    """One anti-aliased segment from (ax, ay) to (bx, by) (the + 0.5 already in) into image (H, W, 3) uint8, of opacity cov * factor: the
+    module text's rule on the part of the segment's box (grown by ceil(ro): outside it cov is exactly 0) inside the image.  What the trails
+    and the limbs share."""
     H, W = image.shape[:2]
+    x_lo, x_hi = max(int(np.floor(min(ax, bx))) - reach, 0), min(int(np.ceil(max(ax, bx))) + reach, W - 1)
+    y_lo, y_hi = max(int(np.floor(min(ay, by))) - reach, 0), min(int(np.ceil(max(ay, by))) + reach, H - 1)
+    if x_lo > x_hi or y_lo > y_hi:
+        return
+    px = np.arange(x_lo, x_hi + 1, dtype=np.float64)[np.newaxis, :]
+    py = np.arange(y_lo, y_hi + 1, dtype=np.float64)[:, np.newaxis]
+    dx, dy = bx - ax, by - ay
+    L2 = dx * dx + dy * dy
+    u = 0.0 if L2 == 0 else np.minimum(np.maximum(((px - ax) * dx + (py - ay) * dy) / L2, 0.0), 1.0)
+    ex, ey = px - (ax + u * dx), py - (ay + u * dy)
+    d2 = ex * ex + ey * ey
+    cov = np.minimum(np.maximum((ro2 - d2) * g, 0.0), 1.0)
+    op = (cov * factor)[:, :, np.newaxis]
+    col = colour.astype(np.float64)[np.newaxis, np.newaxis, :]
+    ys, xs = slice(y_lo, y_hi + 1), slice(x_lo, x_hi + 1)
+    image[ys, xs] = ((1 - op) * image[ys, xs] + op * col).astype(np.uint8)
+
+
+def _trails_host(video, t, tracks, visibles, colors, L, ro2, g, reach, fade, time_colors):
+    """Frame t's trails into video[t] (H, W, 3) uint8: a segment at a time, in point order, oldest step first."""
+    image = video[t]
     s0 = max(0, t - L)
     if s0 >= t or tracks.shape[0] == 0:
         return
@@ -319,40 +455,78 @@ def _trails_host(video, t, tracks, visibles, colors, L, ro2, g, reach, fade, tim
         s = s0 + int(k)
         ax, ay = tracks[i, s] + 0.5
         bx, by = tracks[i, s + 1] + 0.5
-        x_lo, x_hi = max(int(np.floor(min(ax, bx))) - reach, 0), min(int(np.ceil(max(ax, bx))) + reach, W - 1)
-        y_lo, y_hi = max(int(np.floor(min(ay, by))) - reach, 0), min(int(np.ceil(max(ay, by))) + reach, H - 1)
-        if x_lo > x_hi or y_lo > y_hi:
-            continue
-        px = np.arange(x_lo, x_hi + 1, dtype=np.float64)[np.newaxis, :]
-        py = np.arange(y_lo, y_hi + 1, dtype=np.float64)[:, np.newaxis]
-        dx, dy = bx - ax, by - ay
-        L2 = dx * dx + dy * dy
-        u = 0.0 if L2 == 0 else np.minimum(np.maximum(((px - ax) * dx + (py - ay) * dy) / L2, 0.0), 1.0)
-        ex, ey = px - (ax + u * dx), py - (ay + u * dy)
-        d2 = ex * ex + ey * ey
-        cov = np.minimum(np.maximum((ro2 - d2) * g, 0.0), 1.0)
-        op = (cov * fade[t - 1 - s])[:, :, np.newaxis]
-        col = (time_colors[s] if time_colors is not None else colors[i]).astype(np.float64)[np.newaxis, np.newaxis, :]
-        ys, xs = slice(y_lo, y_hi + 1), slice(x_lo, x_hi + 1)
-        image[ys, xs] = ((1 - op) * image[ys, xs] + op * col).astype(np.uint8)
+        _segment_host(image, ax, ay, bx, by, ro2, g, reach, fade[t - 1 - s], time_colors[s] if time_colors is not None else colors[i])
+
+
+def _limbs_host(video, t, tracks, visibles, skeleton, limb_colors, ro2, g, reach, limb_alpha):
+    """Frame t's limbs into video[t] (H, W, 3) uint8: an edge at a time, in edge order."""
+    if skeleton.shape[0] == 0:
+        return
+    with np.errstate(invalid="ignore"):
+        ok = visibles[:, t] & (np.abs(tracks[:, t]) < TRAIL_LIMIT).all(-1)
+    for e, (a, b) in enumerate(skeleton.tolist()):
+        if ok[a] and ok[b]:
+            ax, ay = tracks[a, t] + 0.5
+            bx, by = tracks[b, t] + 0.5
+            _segment_host(video[t], ax, ay, bx, by, ro2, g, reach, limb_alpha, limb_colors[e])
+
+
+def _heat_host(video, heat, heat_colors, gain, heat_alpha):
+    """The maps heat (T, K, H, W) into video (T, H, W, 3) uint8, map after map (the module text's rule)."""
+    cols = heat_colors.astype(np.float64)
+    for t in range(video.shape[0]):
+        image = video[t]
+        for k in range(heat.shape[1]):
+            with np.errstate(invalid="ignore", over="ignore"):
+                a = np.minimum(np.maximum(heat[t, k].astype(np.float64) * gain, 0.0), 1.0) * heat_alpha
+                m = a > 0                                                                # False for NaN
+            if not m.any():
+                continue
+            am = a[m][:, np.newaxis]
+            image[m] = ((1 - am) * image[m] + am * cols[k][np.newaxis, :]).astype(np.uint8)
 
 
 # ---- the public functions -----------------------------------------------------------------------------------------------------------------
 def render(frames, ids=None, tracks=None, visibles=None, colors=None, palette=None, alpha: int = 128, contour: bool = True,
            radius: Optional[int] = None, backend: str = "host", *, trail: Optional[int] = None, linewidth: float = 2.0, trail_fade=None,
-           trail_color_by: str = "track"):
+           trail_color_by: str = "track", skeleton=None, limb_colors=None, limb_width: float = 2.0, limb_alpha: float = 1.0, heat=None,
+           heat_colors=None, heat_gain: float = 1.0, heat_alpha: float = 0.5):
     """Overlay (when `ids` is given), then points (when `tracks` is given) onto frames (T, H, W, 3) uint8; neither: a copy.  ids (T, H, W)
     uint8, palette (256, 3) uint8 (None: davis_palette()), alpha 0 .. 256; tracks (P, T, 2) as (x, y), visibles (P, T) bool (None: all),
     colors (P, 3) integers 0 .. 255 (None: track_colors(P)), radius 1 .. 31 (None: the reference's round(min(H, W) * 0.015)).
     trail=L (1 .. 64, needs tracks; None: no trails): between the overlay and the points, every point's last L steps as line segments
     `linewidth` (1 .. 16) pixels wide, of opacity trail_fade[age] ((L,) in [0, 1]; None: trail_fade(L)), in the point's colour
     (trail_color_by='track') or the step's (='time': spring_colors(T)) -- the module text has the rule.
+    heat (T, K, H, W) float32 | float64 (None: no maps): after the overlay, map k blended in with heat_colors[k] ((K, 3) integers 0 .. 255;
+    None: track_colors(K)) at opacity clamp(v heat_gain, 0, 1) heat_alpha.  skeleton (E, 2) joint indices (needs tracks; None: no limbs):
+    after the heat, edge e as a line `limb_width` (1 .. 16) pixels wide of opacity limb_alpha in limb_colors[e] ((E, 3); None: the colour
+    of the edge's second joint).  The stages run overlay, heat, limbs, points; trail= goes with neither (one stage per launch: paint the
+    trails first and the pose onto that output).
     backend='hip': numpy arrays or CUDA tensors, one launch; returns a CUDA uint8 tensor when `frames` is one, numpy otherwise."""
+    pose = _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors, heat_gain, heat_alpha, trail, tracks, True)
     return _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, trail_fade,
-                   trail_color_by, True)
+                   trail_color_by, True, pose)
 
 
-def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, fade, color_by, dots):
+def _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors, heat_gain, heat_alpha, trail, tracks, dots):
+    """The pose stage's arguments as a dict, None without skeleton and heat; its refusals by name, before any work."""
+    if skeleton is None and heat is None:
+        return None
+    if trail is not None:
+        raise ValueError("trail: not together with skeleton= or heat= (one stage runs per launch: paint the trails first and the pose onto "
+                         "that output)")
+    if skeleton is not None and tracks is None:
+        raise ValueError("skeleton: needs tracks (P, T, 2), got None")
+    pose = dict(dots=bool(dots), skeleton=skeleton, limb_colors=limb_colors, heat=heat, heat_colors=heat_colors)
+    if skeleton is not None:
+        pose["limb_width"], pose["limb_alpha"] = _check_limb_consts(limb_width, limb_alpha)
+    if heat is not None:
+        pose["heat_gain"], pose["heat_alpha"] = _check_heat_consts(heat_gain, heat_alpha)
+    return pose
+
+
+def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, fade, color_by, dots,
+            pose=None):
     hip = _backend(backend)
     on_device = hip and _is_cuda(frames)
     trails = None
@@ -362,18 +536,33 @@ def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radi
         L, lw, fd = _check_trails(trail, linewidth, fade, color_by)
         trails = dict(L=L, linewidth=lw, fade=fd, by_time=color_by == "time", dots=bool(dots))
     if hip:
-        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails)
+        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails, pose)
     f = _numpy(frames)
     _check_frames(f)
-    out = f.copy()
+    hm = hcol = sk = lcol = pts = None
+    with_dots = (trails is None or trails["dots"]) and (pose is None or pose["dots"])
     if ids is not None:
         m = _numpy(ids)
         pal, a = _check_overlay(f, m, _numpy(palette), alpha)
-        out = _overlay_host(out, m, pal, a, bool(contour))
     if tracks is not None:
-        with_dots = trails is None or trails["dots"]
-        tr, vis, col, r = _check_points(f, _numpy(tracks), _numpy(visibles), _numpy(colors), radius if with_dots else 1)
-        out = np.ascontiguousarray(out)
+        pts = tr, vis, col, r = _check_points(f, _numpy(tracks), _numpy(visibles), _numpy(colors), radius if with_dots else 1)
+    if pose is not None and pose["heat"] is not None:
+        hm = _numpy(pose["heat"])
+        hcol = _check_heat_colors(_numpy(pose["heat_colors"]), _check_heat_shape(hm.shape, hm.dtype.name, f.shape))
+    if pose is not None and pose["skeleton"] is not None:
+        sk = _check_skeleton(_numpy(pose["skeleton"]), tr.shape[0])
+        lcol = _check_limb_colors(_numpy(pose["limb_colors"]), sk, col)
+    out = f.copy()
+    if ids is not None:
+        out = _overlay_host(out, m, pal, a, bool(contour))
+    out = np.ascontiguousarray(out)
+    if hm is not None:
+        _heat_host(out, hm, hcol, pose["heat_gain"], pose["heat_alpha"])
+    if sk is not None:
+        ro2, g, reach = trail_consts(pose["limb_width"])
+        for t in range(f.shape[0]):
+            _limbs_host(out, t, tr, vis, sk, lcol, ro2, g, reach, pose["limb_alpha"])
+    if pts is not None:
         if trails is not None:
             ro2, g, reach = trail_consts(trails["linewidth"])
             tcol = spring_colors(f.shape[0]) if trails["by_time"] else None
@@ -384,7 +573,7 @@ def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radi
     return out
 
 
-def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails=None):
+def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails=None, pose=None):
     import torch
     from . import ops
     dev = frames.device if on_device else torch.device("cuda", torch.cuda.current_device())
@@ -413,7 +602,27 @@ def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, 
                 raise ValueError("colors: integers in 0 .. 255")
             col = up(c.astype(np.uint8))
         kw.update(tracks=up(tr, torch.float64), visibles=up(visibles), colors=col, radius=radius)
-    if trails is not None:
+    if pose is not None:
+        def table(x, name):
+            if x is None:
+                return None
+            c = _numpy(x)
+            if c.dtype.kind not in "iu":
+                raise TypeError(f"{name}: integers in 0 .. 255, got {c.dtype}")
+            if c.size and (int(c.min()) < 0 or int(c.max()) > 255):
+                raise ValueError(f"{name}: integers in 0 .. 255")
+            return up(c.astype(np.uint8))
+        pk = dict(dots=pose["dots"])
+        if pose["heat"] is not None:
+            h = pose["heat"]
+            _check_heat_shape(h.shape, str(h.dtype).replace("torch.", ""), f.shape if f.dim() == 4 else (0, 0, 0))
+            pk.update(heat=up(h), heat_colors=table(pose["heat_colors"], "heat_colors"), heat_gain=pose["heat_gain"],
+                      heat_alpha=pose["heat_alpha"])
+        if pose["skeleton"] is not None:
+            pk.update(skeleton=_numpy(pose["skeleton"]), limb_colors=table(pose["limb_colors"], "limb_colors"),
+                      limb_width=pose["limb_width"], limb_alpha=pose["limb_alpha"])
+        out = ops.render_pose(f, **pk, **kw)
+    elif trails is not None:
         tcol = up(spring_colors(f.shape[0])) if trails["by_time"] and f.dim() == 4 else None
         out = ops.render_trails(f, trail=trails["L"], linewidth=trails["linewidth"], fade=up(trails["fade"]), time_colors=tcol,
                                 dots=trails["dots"], **kw)
@@ -432,6 +641,44 @@ def paint_trails(frames, point_tracks, visibles=None, colors=None, trail: int = 
     if trail is None:
         raise ValueError("trail=None: an integer in 1 .. 64 (paint_point_track draws the dots alone)")
     return _render(frames, None, point_tracks, visibles, colors, None, 128, True, radius, backend, trail, linewidth, fade, color_by, dots)
+
+
+def paint_pose(frames, joints=None, visibles=None, colors=None, skeleton=None, limb_colors=None, limb_width: float = 2.0,
+               limb_alpha: float = 1.0, heat=None, heat_colors=None, heat_gain: float = 1.0, heat_alpha: float = 0.5, dots: bool = True,
+               radius: Optional[int] = None, backend: str = "host"):
+    """frames (T, H, W, 3) uint8 with a pose drawn on: the joints' heat maps `heat` (T, K, H, W), the limbs of `skeleton` (E, 2) between the
+    joints (K, T, 2) (pose_tracks of the pose call's coordinates; pose_visibles for `visibles`) and, with dots=True, the joints' dots on
+    top -- see render and the module text.  JHMDB_SKELETON is the JHMDB puppet's; BADJA has no agreed skeleton."""
+    if joints is None and heat is None:
+        raise ValueError("paint_pose: joints (K, T, 2) or heat (T, K, H, W), got neither")
+    if skeleton is None and heat is None:
+        skeleton = np.zeros((0, 2), np.int32)                                           # the dots alone, through the same stage
+    pose = _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors, heat_gain, heat_alpha, None, joints, dots)
+    return _render(frames, None, joints, visibles, colors, None, 128, True, radius, backend, None, 2.0, None, "track", dots, pose)
+
+
+def pose_tracks(coords) -> np.ndarray:
+    """The pose call's coordinates (2, K, T) (x row, then y row) -> (K, T, 2) float64 as (x, y): what the painters take as tracks."""
+    c = np.asarray(_numpy(coords), dtype=np.float64)
+    if c.ndim != 3 or c.shape[0] != 2:
+        raise ValueError(f"coords: (2, K, T), got {c.shape}")
+    return np.ascontiguousarray(np.moveaxis(c, 0, -1))
+
+
+def pose_visibles(coords, peak=None, min_conf: Optional[float] = None) -> np.ndarray:
+    """(K, T) bool from the pose call's coordinates (2, K, T): a joint is visible when its coordinate is finite, is not the reference's
+    (-1, -1) of an empty map and, when both `peak` (K, T) (last_pose['peak']) and `min_conf` are given, peak >= min_conf."""
+    c = np.asarray(_numpy(coords), dtype=np.float64)
+    if c.ndim != 3 or c.shape[0] != 2:
+        raise ValueError(f"coords: (2, K, T), got {c.shape}")
+    vis = np.isfinite(c).all(0) & ~((c[0] == -1.0) & (c[1] == -1.0))
+    if peak is not None and min_conf is not None:
+        p = np.asarray(_numpy(peak), dtype=np.float64)
+        if p.shape != vis.shape:
+            raise ValueError(f"peak: {vis.shape} to go with the coordinates, got {p.shape}")
+        with np.errstate(invalid="ignore"):
+            vis &= p >= float(min_conf)
+    return vis
 
 
 def paint_point_track(frames, point_tracks, visibles, colors=None, radius: Optional[int] = None, backend: str = "host"):

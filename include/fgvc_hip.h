@@ -514,6 +514,28 @@ int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_
                           const uint8_t* colors, int P, int radius, const double* icon, int trail, double linewidth, double ro2, double g,
                           const double* fade, const uint8_t* time_colors, void* stream);
 
+/* ---- Pose: the renderer above with the joints' heat maps and the skeleton's limbs drawn between the overlay and the
+ * dots -- overlay, heat, limbs, dots -- still one launch; fgvc_amd/viz.py's host backend bit for bit.  Every argument up to `icon` is the
+ * renderer's, except: icon == null leaves the dots out (radius and colors are then ignored).
+ *   heat    [T][K][h][w] float32 or (heat_f64 != 0) float64, element (t, k, y, x) at heat[t stride_t + k stride_k + y stride_y + x] (strides in
+ *           elements), or null: no maps; 1 <= K <= 256; heat_colors [K][3] uint8.  Per pixel, for k = 0 .. K - 1 in order:
+ *             a = min(max(v heat_gain, 0), 1) heat_alpha, v widened to double; not a > 0 (zero, negative, NaN): unchanged; else
+ *             v_c = (1 - a) v_c + a colour_c, truncated towards zero to uint8 after every map.
+ *   skeleton [E][2] int32 joint indices in 0 .. P - 1 (an edge with an index outside is not drawn), limb_colors [E][3] uint8.  On frame t
+ *           edge e = (a, b) is the trail's segment from tracks[a][t] + 0.5 to tracks[b][t] + 0.5, drawn in edge order only if both ends are
+ *           visible on t and all four coordinates are below 2^20 in magnitude; its opacity is cov limb_alpha.  limb_width 1 .. 16 with
+ *           ro2 and g as fgvc_render_trails_u8's linewidth (viz.trail_consts).
+ * Errors as the renderer's, and FGVC_ERR_INVALID_ARG for K, heat_gain (finite, > 0), heat_alpha, limb_alpha (0 .. 1) or limb_width out of
+ * range, a null colour table, negative strides, a misaligned heat or skeleton.  No workspace, no atomics. */
+int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                        int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                        const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                        int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                        const uint8_t* colors, int P, int radius, const double* icon, const int32_t* skeleton, int E,
+                        const uint8_t* limb_colors, double limb_width, double ro2, double g, double limb_alpha, const void* heat, int heat_f64,
+                        int K, int64_t heat_stride_t, int64_t heat_stride_k, int64_t heat_stride_y, const uint8_t* heat_colors,
+                        double heat_gain, double heat_alpha, void* stream);
+
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage
  *                             (fgvc_pair_topk_f32 with topk=1 on the coarse features)
@@ -750,6 +772,12 @@ int fgvc_seg_soft_labels_f64(const double* map, int K, int hm, int wm, int hp, i
 size_t fgvc_heatmap_coords_workspace_bytes(int T, int K);
 int fgvc_heatmap_coords_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
                             int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, void* workspace, void* stream);
+
+/* fgvc_heatmap_coords_f32 with each map's peak: coords as above, bit for bit, and peak [K][T] f64, the largest value of the field that
+ * fgvc_softmap_readout_f32 writes for that map (the first of its top five), widened to f64: frame 0 in the map's dtype, later frames f32. */
+int fgvc_heatmap_coords_peak_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
+                                 int wp, int top, int left, int h0, int w0, int f64_arith, double* coords, double* peak, void* workspace,
+                                 void* stream);
 
 /* The maps themselves, frames [f_begin, f_end) of the stack the reference returns without `coords` (:770-784, :800-803), channel-first:
  *   out [f_end - f_begin][K][h0][w0], f32 or (out_f64 != 0) f64;

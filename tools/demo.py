@@ -8,6 +8,7 @@ mediapy: frames come and go through PIL).
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task points --query-points t x y ... --trails [L] [--trail-width X] [--trail-color track|time] --out OUT
     python tools/demo.py FRAMES_DIR --task flow [--flow-step 1] [--flow-occlusion fb_abs] --out OUT
+    python tools/demo.py FRAMES_DIR --task pose --joints x y [x y ...] [--skeleton jhmdb | a-b ...] [--min-conf X] [--heat] --out OUT
     python tools/demo.py CLIP.y4m --task points --query-points t x y ... [--yuv-matrix bt601|bt709] --out OUT
     python tools/demo.py CLIP.y4m --task points --query-points t x y ... --out OUT --out-video OUT.y4m [--out-matrix bt601|bt709] [--out-range limited|full]
 
@@ -26,6 +27,10 @@ section 20) -- and only the packed I420 frames, 1.5 bytes a pixel, cross to the 
 rate: `ffmpeg -i OUT.y4m out.mp4` takes the file.  Matrix, range and chroma siting are those the clip was decoded with for a .y4m input, else
 yuv_matrix_default(height), 'limited' and 'left'; --out-matrix and --out-range override.  A Y4M header has no matrix tag: the printed line says
 which one was used.  Frames with an odd side are refused (Y4M 4:2:0 has no odd form).
+--task pose propagates the joints --joints of frame 0 as heat maps (datasets.pose_heatmaps; test_cfg.coords=True with test_cfg.pose) and
+paints them with viz.paint_pose: the limbs of --skeleton, the dots, a joint whose map's peak is below --min-conf hidden; --heat blends the
+propagated maps in, made on the device from the kept field in frame chunks (maps at the frames' size only: not with another --size).
+
 --trails [L] (--task points; L = 8 when left out) also draws every point's last L steps as a fading poly-line under the dots, what the reference
 demo's second video shows: viz.render(trail=L), still one launch (fgvc_render_trails_u8).  --trail-width is the line
 width in pixels, --trail-color time the reference's colouring by time in place of the point's own colour.  It goes with --chain (a trail stops
@@ -156,6 +161,69 @@ def run_points(a, frames: np.ndarray, dev):
     return tracks, visibles, qp_out.cpu().numpy()
 
 
+def parse_skeleton(spec, num_joints: int):
+    """--skeleton jhmdb | a-b [a-b ...] -> (E, 2) int32, or None without the flag."""
+    if not spec:
+        return None
+    if len(spec) == 1 and spec[0] == "jhmdb":
+        edges = viz.JHMDB_SKELETON
+    else:
+        try:
+            edges = np.asarray([[int(v) for v in e.split("-")] for e in spec], np.int32).reshape(-1, 2)
+        except ValueError:
+            raise ValueError(f"--skeleton: 'jhmdb' or edges a-b of joint indices, got {spec}") from None
+    return viz._check_skeleton(edges, num_joints)
+
+
+def run_pose(a, frames, dev):
+    """-> joints (K, T, 2) float64 in the clip's pixel frame, visibles (K, T) bool, the model (its last_pose holds the peaks and, with --heat,
+    the field the maps are made from).  The first-frame maps are datasets.pose_heatmaps of --joints at the model's size."""
+    from fgvc_amd import datasets
+    T, H, W = frames.shape[:3]
+    j = np.asarray(a.joints, np.float64)
+    if j.size == 0 or j.size % 2:
+        raise ValueError("--joints: x y [x y ...]")
+    j = j.reshape(-1, 2)
+    size = tuple(a.size) if a.size else (H, W)
+    if a.heat and size != (H, W):
+        raise ValueError(f"--heat: the heat overlay needs maps at the frames' size {H} x {W}, and --size {size[0]} {size[1]} makes them at "
+                         f"another; resizing maps is out of scope (drop --size or --heat)")
+    heat = datasets.pose_heatmaps(j, (H, W), a.joint_sigma, size)                          # (K, h, w) float64
+    model = build_model(a, dev, input=_input(a, tuple(a.size) if a.size else None), coords=True,
+                        pose=dict(confidence=True, keep_field=bool(a.heat)))
+    with torch.no_grad():
+        out = model(test_mode=True, imgs=_raw(a, frames, dev)[None, None], ref_seg_map=torch.from_numpy(heat)[None].to(dev),
+                    img_meta=[dict(original_shape=size)])
+    coords = out[0]                                                                       # (2, K, T) at the model's size
+    joints = viz.scale_tracks(viz.pose_tracks(coords), size, (H, W))
+    visibles = viz.pose_visibles(coords, model.last_pose["peak"], a.min_conf)
+    return joints, visibles, model
+
+
+def paint_pose(a, frames, joints, visibles, model, dev):
+    """The painted clip (T, H, W, 3) uint8 as numpy.  With --heat the maps are made on the device from the kept field, in frame chunks under
+    test_cfg.maps_budget, and every chunk is painted on its own: the whole (T, K, H, W) stack never exists, on either side."""
+    from fgvc_amd import engine
+    K = joints.shape[0]
+    kw = dict(skeleton=parse_skeleton(a.skeleton, K), limb_width=a.limb_width, radius=a.radius)
+    host = a.host_render
+    f = (frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames) if host else \
+        (frames if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev))
+    backend = "host" if host else "hip"
+    if not a.heat:
+        out = viz.paint_pose(f, joints, visibles, backend=backend, **kw)
+        return out if host else out.cpu().numpy()
+    field = model.last_pose["field"]
+    T, H, W = f.shape[:3]
+    parts = []
+    for f0, f1 in engine.plan_map_chunks(T, K, (H, W), 4, model._maps_budget()):
+        maps = field.maps(f0, f1, out_dtype=torch.float32)                                # (f1 - f0, K, H, W) on the device
+        part = viz.paint_pose(f[f0:f1], joints[:, f0:f1], visibles[:, f0:f1], heat=maps.cpu().numpy() if host else maps,
+                              heat_gain=a.heat_gain, backend=backend, **kw)
+        parts.append(part if host else part.cpu().numpy())
+    return np.concatenate(parts)
+
+
 def _mask_png(path, H, W, flag) -> np.ndarray:
     from PIL import Image
     mask = np.asarray(Image.open(path))
@@ -275,7 +343,14 @@ def parse_args(argv=None):
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default=None,
                     help="the matrix of a .y4m clip's YUV (the file does not say); default: bt709 from 720 rows up, else bt601")
     ap.add_argument("--synthetic", type=int, nargs=3, metavar=("T", "H", "W"), help="a generated clip instead of FRAMES_DIR")
-    ap.add_argument("--task", choices=("points", "vos", "flow"), required=True)
+    ap.add_argument("--task", choices=("points", "vos", "flow", "pose"), required=True)
+    ap.add_argument("--joints", type=float, nargs="+", default=[], metavar="V", help="x y [x y ...], pixels of frame 0 (--task pose)")
+    ap.add_argument("--joint-sigma", type=float, default=4.0, help="the first-frame Gaussians' sigma in pixels (--task pose)")
+    ap.add_argument("--skeleton", nargs="+", default=None, metavar="EDGE", help="'jhmdb' or limbs a-b [a-b ...] of joint indices (--task pose)")
+    ap.add_argument("--min-conf", type=float, default=None, metavar="X", help="hide a joint whose map's peak is below X (--task pose)")
+    ap.add_argument("--heat", action="store_true", help="blend the propagated heat maps in (--task pose; maps at the frames' size only)")
+    ap.add_argument("--heat-gain", type=float, default=1.0, help="with --heat: the maps' values times this, clamped to [0, 1], is the opacity")
+    ap.add_argument("--limb-width", type=float, default=2.0, metavar="X", help="with --skeleton: the line width in pixels (1 .. 16)")
     ap.add_argument("--flow-step", type=int, default=1, help="frame distance of a flow pair (--task flow)")
     ap.add_argument("--flow-occlusion", choices=("consistency", "fb_abs"), default=None, help="also write the forward check's mask (--task flow)")
     ap.add_argument("--chain", action="store_true",
@@ -319,6 +394,12 @@ def parse_args(argv=None):
         ap.error("give FRAMES_DIR or --synthetic T H W")
     if a.task == "points" and not a.query_points:
         ap.error("--task points needs --query-points")
+    if a.task == "pose" and (not a.joints or len(a.joints) % 2):
+        ap.error("--task pose needs --joints x y [x y ...]")
+    if a.task != "pose" and (a.joints or a.skeleton or a.heat or a.min_conf is not None or a.heat_gain != 1.0 or a.limb_width != 2.0):
+        ap.error("--joints, --skeleton, --min-conf, --heat, --heat-gain and --limb-width go with --task pose")
+    if a.task == "pose" and a.heat and a.size and a.synthetic and tuple(a.size) != tuple(a.synthetic[1:]):
+        ap.error("--heat: the heat overlay needs maps at the frames' size; --size makes them at another (resizing maps is out of scope)")
     if a.task == "vos" and not (a.first_mask or a.mask):
         ap.error("--task vos needs --first-mask (or --mask T PNG)")
     if (a.both_ways or a.confidence or a.override != "new") and not a.mask:
@@ -355,6 +436,19 @@ def main(argv=None):
         if video:
             write_video(a.out_video, coloured, video, dev, host=a.host_render)
         return
+    if a.task == "pose":
+        tracks, visibles, model = run_pose(a, frames, dev)
+        rendered = paint_pose(a, frames, tracks, visibles, model, dev)
+        packed = write_video(a.out_video, rendered if a.host_render else torch.from_numpy(rendered).to(dev), video, dev,
+                             host=a.host_render) if video else None
+        frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
+        write(a.out, rendered, a.fps)
+        print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif (pose, {tracks.shape[0]} joints"
+              f"{', heat maps' if a.heat else ''}, {'host' if a.host_render else 'hip'} renderer)")
+        r = dict(frames=frames, tracks=tracks, visibles=visibles, peak=model.last_pose["peak"], rendered=rendered)
+        if video:
+            r.update(video=packed.numpy(), video_settings=video)
+        return r
     if a.task == "points":
         tracks, visibles, points = run_points(a, frames, dev)
     else:

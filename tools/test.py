@@ -28,7 +28,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import fgvc_amd.mmpt_api as api  # noqa: E402
-from fgvc_amd import apis, metrics  # noqa: E402
+from fgvc_amd import apis, metrics, viz  # noqa: E402
 from fgvc_amd.datasets import Davis2017, YoutubeVos, davis_evaluate, ytvos_run  # noqa: E402
 from fgvc_amd.datasets import BadjaPoses, JhmdbPoses, StridedLoader, SyntheticTapVid, TapVidPickles, badja_evaluate, jhmdb_evaluate  # noqa: E402
 from fgvc_amd.datasets import MapsAsCoords, badja_evaluate_heatmap, jhmdb_evaluate_heatmap  # noqa: E402
@@ -41,6 +41,62 @@ DEFAULT_CFG = dict(
     test_cfg_davis=dict(precede_frames=5, topk=10, temperature=0.07, strides=(1, 1, 1, 4), out_indices=(2,),
                         neighbor_range=30, step=512, with_first=True, with_first_neighbor=True),
 )
+
+
+def jhmdb_frames(ds, i):
+    """The frames the JHMDB heat-map form's coordinates refer to: the video's own."""
+    import numpy as np
+    from PIL import Image
+    return np.stack([np.asarray(Image.open(p).convert("RGB")) for p in ds.samples[i]["frames_path"]])
+
+
+def badja_frames(ds, i):
+    """The frames the BADJA heat-map form's coordinates refer to: the video's, resized to the network size."""
+    import numpy as np
+    from PIL import Image
+    v = ds.videos[i]
+    n = len(v["frames"]) if ds.length == -1 else min(ds.length, len(v["frames"]))
+    h, w = ds.size
+    return np.stack([np.asarray(Image.open(p).convert("RGB").resize((w, h), Image.BILINEAR)) for p in v["frames"][:n]])
+
+
+class PosePainter:
+    """--render: a coords=True tracker that also paints the clip it is called on -- viz.paint_pose on the device with the joints'
+    coordinates, their visibility by viz.pose_visibles (with --min-conf: from the peaks of test_cfg.pose) and the skeleton -- into
+    DIR/<video>/frame_%05d.png.  Which clip that is comes from the dataset: indexed(ds) notes the index of every item it hands out."""
+
+    def __init__(self, model, out_dir, names, clip, skeleton, min_conf):
+        self.model, self.out_dir, self.names, self.clip, self.skeleton, self.min_conf = model, out_dir, names, clip, skeleton, min_conf
+        self.index = None
+
+    def indexed(self, ds):
+        painter = self
+
+        class Indexed:
+            def __len__(self):
+                return len(ds)
+
+            def __getitem__(self, i):
+                painter.index = i
+                return ds[i]
+
+            def __getattr__(self, name):
+                return getattr(ds, name)
+        return Indexed()
+
+    def __call__(self, **data):
+        from PIL import Image
+        out = self.model(**data)
+        coords, i = out[0], self.index
+        peak = self.model.last_pose["peak"] if self.min_conf is not None else None
+        frames = self.clip(i)[:coords.shape[2]]
+        painted = viz.paint_pose(frames, viz.pose_tracks(coords), viz.pose_visibles(coords, peak, self.min_conf), skeleton=self.skeleton,
+                                 backend="hip")
+        d = os.path.join(self.out_dir, self.names(i))
+        os.makedirs(d, exist_ok=True)
+        for t, f in enumerate(painted):
+            Image.fromarray(f).save(os.path.join(d, f"frame_{t:05d}.png"))
+        return out
 
 
 def main():
@@ -60,6 +116,10 @@ def main():
                          "Gaussian maps and reads joints out of them (test_cfg.coords=True); 'softmap' has the propagated maps themselves "
                          "returned (test_cfg.return_maps=True) and reads the joints out of them on the host, by the same rule")
     ap.add_argument("--dump-maps", default=None, metavar="DIR", help="--pose-form softmap: write each video's (T, K, h0, w0) array as DIR/<video>.npy")
+    ap.add_argument("--render", default=None, metavar="DIR", help="--task jhmdb|badja --pose-form heatmap: paint every clip (JHMDB with its "
+                                                                  "skeleton, BADJA the joints alone) into DIR/<video>/frame_%05d.png")
+    ap.add_argument("--min-conf", type=float, default=None, metavar="X", help="with --render: hide a joint whose map's peak is below X "
+                                                                              "(test_cfg.pose; the scores do not change)")
     ap.add_argument("--eval-arc", default=None, help="tracker class to build, overriding the config's eval_arc (e.g. HRVanillaTracker: the "
                                                      "local-window affinity for masks, heat maps and points)")
     ap.add_argument("--occlusion", action="store_true",
@@ -126,6 +186,12 @@ def main():
     softmap = heatmap and a.pose_form == "softmap"
     if a.dump_maps and not softmap:
         raise SystemExit("--dump-maps goes with --task jhmdb|badja --pose-form softmap")
+    if a.render and not (heatmap and not softmap):
+        raise SystemExit("--render goes with --task jhmdb|badja --pose-form heatmap")
+    if a.min_conf is not None and not a.render:
+        raise SystemExit("--min-conf goes with --render")
+    if a.min_conf is not None:
+        test_cfg = dict(test_cfg, pose=dict(confidence=True, keep_field=False))     # the peaks, for the painter alone
     if softmap:
         test_cfg = dict(test_cfg, return_maps=True)  # the maps themselves (the reference's coords=False return value), decoded below
     elif heatmap:
@@ -167,8 +233,11 @@ def main():
         api.load_checkpoint(model, a.checkpoint)                                             # :158-159
     model = model.to(dev).eval()
 
-    def scored(names):
-        """The model the heat-map evaluators call: itself, or under --pose-form softmap its maps decoded on the host (and dumped)."""
+    def scored(names, clip=None):
+        """The model the heat-map evaluators call: itself, or under --pose-form softmap its maps decoded on the host (and dumped), or
+        under --render itself with every clip painted on the way (clip(i) -> the frames (T, h, w, 3) uint8 the coordinates refer to)."""
+        if a.render:
+            return PosePainter(model, a.render, names, clip, viz.JHMDB_SKELETON if a.task == "jhmdb" else None, a.min_conf)
         if not softmap:
             return model
         if a.dump_maps:
@@ -201,7 +270,8 @@ def main():
         if rank == 0:          # (one process scores the set, as for JHMDB below; badja_dataset.py:451-571)
             if heatmap:        # --pose-form heatmap: the reference's own first-frame label (BadjaPoses(form='heatmap'))
                 ds = BadjaPoses(a.data_root, size=POSE_SIZE["badja"], device=dev, form="heatmap", raw=a.raw_frames)
-                pck = badja_evaluate_heatmap(scored(lambda i: str(ds.videos[i]["name"])), ds)
+                m = scored(lambda i: str(ds.videos[i]["name"]), lambda i: badja_frames(ds, i))
+                pck = badja_evaluate_heatmap(m, m.indexed(ds) if a.render else ds)
             else:
                 pck = badja_evaluate(model, BadjaPoses(a.data_root, size=POSE_SIZE["badja"], device=dev, raw=a.raw_frames))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
@@ -216,7 +286,8 @@ def main():
             if heatmap:
                 ds = JhmdbPoses(a.data_root, split="val", input_size=POSE_SIZE["jhmdb"], device=dev, form="heatmap", raw=a.raw_frames)
                 vname = lambda i: os.path.relpath(ds.samples[i]["video_path"], ds.root).replace(os.sep, "_")   # <action>_<video>
-                pck = jhmdb_evaluate_heatmap(scored(vname), ds)
+                m = scored(vname, lambda i: jhmdb_frames(ds, i))
+                pck = jhmdb_evaluate_heatmap(m, m.indexed(ds) if a.render else ds)
             else:
                 pck = jhmdb_evaluate(model, JhmdbPoses(a.data_root, split="val", input_size=POSE_SIZE["jhmdb"], device=dev, raw=a.raw_frames))
             print(json.dumps({k: round(v, 2) for k, v in pck.items()}))
