@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "render_host.hpp"
 
 namespace fgvc {
 
@@ -55,17 +56,6 @@ int frames_rgb8_to_yuv420_launch(const uint8_t*, int, int, int, long long, long 
 void yuv_out_tile(int*, int*);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
-int render_frames_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
-                         const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
-                         int, const double*, hipStream_t);
-void render_tile(int*, int*);
-int render_trails_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
-                         const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
-                         int, const double*, int, int, double, double, const double*, const uint8_t*, hipStream_t);
-int render_pose_launch(const uint8_t*, long long, long long, uint8_t*, long long, long long, int, int, int, const uint8_t*, long long, long long,
-                       const uint8_t*, int, int, const double*, long long, long long, const uint8_t*, long long, long long, const uint8_t*, int,
-                       int, const double*, const int32_t*, int, const uint8_t*, int, double, double, double, const void*, int, int, long long,
-                       long long, long long, const uint8_t*, double, double, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -766,38 +756,58 @@ int fgvc_render_tile_cols(void) {
   return cols;
 }
 
+// The three render entries share their 25 leading arguments (render_host.hpp's RenderCall) and the two sets of checks below; `fn` is the
+// entry's name.  First the sizes, which come before the "no pixel exists" return ...
+static int render_check_sizes(const char* fn, const RenderCall& c) {
+  FGVC_REQUIRE(c.T >= 0 && c.h >= 0 && c.w >= 0, FGVC_ERR_INVALID_ARG, "%s: negative size (T=%d, %d x %d)", fn, c.T, c.h, c.w);
+  FGVC_REQUIRE(c.P >= 0, FGVC_ERR_INVALID_ARG, "%s: P=%d", fn, c.P);
+  FGVC_REQUIRE((long long)c.h * c.w < (1ll << 29), FGVC_ERR_INVALID_ARG, "%s: a frame of %d x %d has 2^29 pixels or more", fn, c.h, c.w);
+  return FGVC_OK;
+}
+
+// ... then the operands: pointers, strides, the overlay's, and (dots: the entry will run the point stage) the radius.  What else the points
+// need differs between the entries and stays with each.
+static int render_check_operands(const char* fn, const RenderCall& c, bool dots) {
+  FGVC_REQUIRE(c.frames && c.out, FGVC_ERR_INVALID_ARG, "%s: null pointer", fn);
+  const long long row = 3ll * c.w;
+  FGVC_REQUIRE(c.f_sy >= row && (c.T == 1 || c.f_st >= 0), FGVC_ERR_INVALID_ARG,
+               "%s: frames: a row stride of at least 3 w = %lld bytes, got %lld", fn, row, c.f_sy);
+  FGVC_REQUIRE(c.o_sy >= row && (c.T == 1 || c.o_st >= (long long)(c.h - 1) * c.o_sy + row), FGVC_ERR_INVALID_ARG,
+               "%s: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)", fn, c.o_st, c.o_sy, c.h, c.w);
+  if (c.ids) {
+    FGVC_REQUIRE(c.palette, FGVC_ERR_INVALID_ARG, "%s: ids without a palette", fn);
+    FGVC_REQUIRE(c.alpha >= 0 && c.alpha <= 256, FGVC_ERR_INVALID_ARG, "%s: alpha=%d (0 .. 256)", fn, c.alpha);
+    FGVC_REQUIRE(c.i_sy >= c.w && (c.T == 1 || c.i_st >= 0), FGVC_ERR_INVALID_ARG,
+                 "%s: ids: a row stride of at least w = %d bytes, got %lld", fn, c.w, c.i_sy);
+  }
+  if (dots) {
+    FGVC_REQUIRE(c.radius >= 1, FGVC_ERR_INVALID_ARG, "%s: radius=%d (at least 1)", fn, c.radius);
+    FGVC_REQUIRE(c.radius <= 31, FGVC_ERR_UNSUPPORTED, "%s: radius=%d beyond 31", fn, c.radius);
+  }
+  return FGVC_OK;
+}
+
+static bool aligned8(const void* p, const void* q, const void* r = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(r)) & 7u) == 0;
+}
+
 int fgvc_render_frames_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
                           int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
                           const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
                           int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
                           const uint8_t* colors, int P, int radius, const double* icon, void* stream) {
-  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: negative size (T=%d, %d x %d)", T, h, w);
-  FGVC_REQUIRE(P >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: P=%d", P);
-  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
+  const char* fn = "fgvc_render_frames_u8";
+  const RenderCall c{frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                     palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p, visibles_stride_t,
+                     colors, P, radius, icon};
+  if (int rc = render_check_sizes(fn, c)) return rc;
   if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
-  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: null pointer");
-  const long long row = 3ll * w;
-  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_frames_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
-  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_frames_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
-               (long long)out_stride_t, (long long)out_stride_y, h, w);
-  if (ids) {
-    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: ids without a palette");
-    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: alpha=%d (0 .. 256)", alpha);
-    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_frames_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
-  }
+  if (int rc = render_check_operands(fn, c, tracks && P > 0)) return rc;
   if (tracks && P > 0) {
-    FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: radius=%d (at least 1)", radius);
-    FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_frames_u8: radius=%d beyond 31", radius);
-    FGVC_REQUIRE(colors && icon, FGVC_ERR_INVALID_ARG, "fgvc_render_frames_u8: tracks without colors or the icon table");
-    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon)) & 7u) == 0, FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_frames_u8: tracks and icon must be 8-byte aligned");
+    FGVC_REQUIRE(colors && icon, FGVC_ERR_INVALID_ARG, "%s: tracks without colors or the icon table", fn);
+    FGVC_REQUIRE(aligned8(tracks, icon), FGVC_ERR_INVALID_ARG, "%s: tracks and icon must be 8-byte aligned", fn);
   }
-  return render_frames_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
-                              palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
-                              visibles_stride_t, colors, P, radius, icon, (hipStream_t)stream);
+  return render_frames_launch(c, (hipStream_t)stream);
 }
 
 int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
@@ -806,46 +816,27 @@ int fgvc_render_trails_u8(const uint8_t* frames, int64_t frames_stride_t, int64_
                           int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
                           const uint8_t* colors, int P, int radius, const double* icon, int trail, double linewidth, double ro2, double g,
                           const double* fade, const uint8_t* time_colors, void* stream) {
-  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: negative size (T=%d, %d x %d)", T, h, w);
-  FGVC_REQUIRE(P >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: P=%d", P);
-  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
-  FGVC_REQUIRE(trail >= 1 && trail <= 64, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: trail=%d (1 .. 64)", trail);
-  FGVC_REQUIRE(linewidth >= 1.0 && linewidth <= 16.0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: linewidth=%g (1 .. 16)", linewidth);
-  FGVC_REQUIRE((long long)P * trail < (1ll << 30), FGVC_ERR_UNSUPPORTED, "fgvc_render_trails_u8: P * trail = %lld items, 2^30 or more",
-               (long long)P * trail);
+  const char* fn = "fgvc_render_trails_u8";
+  const RenderCall c{frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                     palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p, visibles_stride_t,
+                     colors, P, radius, icon};
+  if (int rc = render_check_sizes(fn, c)) return rc;
+  FGVC_REQUIRE(trail >= 1 && trail <= 64, FGVC_ERR_INVALID_ARG, "%s: trail=%d (1 .. 64)", fn, trail);
+  FGVC_REQUIRE(linewidth >= 1.0 && linewidth <= 16.0, FGVC_ERR_INVALID_ARG, "%s: linewidth=%g (1 .. 16)", fn, linewidth);
+  FGVC_REQUIRE((long long)P * trail < (1ll << 30), FGVC_ERR_UNSUPPORTED, "%s: P * trail = %lld items, 2^30 or more", fn, (long long)P * trail);
   if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
-  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: null pointer");
-  const long long row = 3ll * w;
-  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_trails_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
-  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_trails_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
-               (long long)out_stride_t, (long long)out_stride_y, h, w);
-  if (ids) {
-    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: ids without a palette");
-    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: alpha=%d (0 .. 256)", alpha);
-    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_trails_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
-  }
+  if (int rc = render_check_operands(fn, c, P > 0 && icon)) return rc;
   if (P > 0) {
-    FGVC_REQUIRE(tracks && fade, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: null tracks or fade table");
-    FGVC_REQUIRE(colors || (time_colors && !icon), FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: neither colors nor time_colors");
-    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: tracks: a negative frame stride (%lld)",
-                 (long long)tracks_stride_t);
-    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_trails_u8: visibles: a negative frame stride (%lld)", (long long)visibles_stride_t);
-    FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: ro2=%g, g=%g (both positive, ro2 <= 81)", ro2, g);
-    if (icon) {
-      FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: radius=%d (at least 1)", radius);
-      FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_trails_u8: radius=%d beyond 31", radius);
-    }
-    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon) | reinterpret_cast<uintptr_t>(fade)) & 7u) == 0,
-                 FGVC_ERR_INVALID_ARG, "fgvc_render_trails_u8: tracks, icon and fade must be 8-byte aligned");
+    FGVC_REQUIRE(tracks && fade, FGVC_ERR_INVALID_ARG, "%s: null tracks or fade table", fn);
+    FGVC_REQUIRE(colors || (time_colors && !icon), FGVC_ERR_INVALID_ARG, "%s: neither colors nor time_colors", fn);
+    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "%s: tracks: a negative frame stride (%lld)", fn, c.trk_st);
+    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG, "%s: visibles: a negative frame stride (%lld)", fn,
+                 c.vis_st);
+    FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "%s: ro2=%g, g=%g (both positive, ro2 <= 81)", fn, ro2, g);
+    FGVC_REQUIRE(aligned8(tracks, icon, fade), FGVC_ERR_INVALID_ARG, "%s: tracks, icon and fade must be 8-byte aligned", fn);
   }
   const int reach = (int)ceil(linewidth / 2.0 + 0.5);                 // ceil(ro): what a segment's box is grown by
-  return render_trails_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
-                              palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
-                              visibles_stride_t, colors, P, radius, icon, trail, reach, ro2, g, fade, time_colors, (hipStream_t)stream);
+  return render_trails_launch(c, trail, reach, ro2, g, fade, time_colors, (hipStream_t)stream);
 }
 
 int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
@@ -856,61 +847,44 @@ int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t 
                         const uint8_t* limb_colors, double limb_width, double ro2, double g, double limb_alpha, const void* heat, int heat_f64,
                         int K, int64_t heat_stride_t, int64_t heat_stride_k, int64_t heat_stride_y, const uint8_t* heat_colors,
                         double heat_gain, double heat_alpha, void* stream) {
-  FGVC_REQUIRE(T >= 0 && h >= 0 && w >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: negative size (T=%d, %d x %d)", T, h, w);
-  FGVC_REQUIRE(P >= 0 && E >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: P=%d, E=%d", P, E);
-  FGVC_REQUIRE((long long)h * w < (1ll << 29), FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: a frame of %d x %d has 2^29 pixels or more", h, w);
-  FGVC_REQUIRE(E < (1 << 30), FGVC_ERR_UNSUPPORTED, "fgvc_render_pose_u8: E = %d limbs, 2^30 or more", E);
-  FGVC_REQUIRE(!heat || (K >= 1 && K <= 256), FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: K=%d heat maps (1 .. 256)", K);
+  const char* fn = "fgvc_render_pose_u8";
+  const RenderCall c{frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                     palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p, visibles_stride_t,
+                     colors, P, radius, icon};
+  if (int rc = render_check_sizes(fn, c)) return rc;
+  FGVC_REQUIRE(E >= 0, FGVC_ERR_INVALID_ARG, "%s: E=%d", fn, E);
+  FGVC_REQUIRE(E < (1 << 30), FGVC_ERR_UNSUPPORTED, "%s: E = %d limbs, 2^30 or more", fn, E);
+  FGVC_REQUIRE(!heat || (K >= 1 && K <= 256), FGVC_ERR_INVALID_ARG, "%s: K=%d heat maps (1 .. 256)", fn, K);
   if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
-  FGVC_REQUIRE(frames && out, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: null pointer");
-  const long long row = 3ll * w;
-  FGVC_REQUIRE(frames_stride_y >= row && (T == 1 || frames_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_pose_u8: frames: a row stride of at least 3 w = %lld bytes, got %lld", row, (long long)frames_stride_y);
-  FGVC_REQUIRE(out_stride_y >= row && (T == 1 || out_stride_t >= (long long)(h - 1) * out_stride_y + row), FGVC_ERR_INVALID_ARG,
-               "fgvc_render_pose_u8: out: rows and frames must not overlap (strides %lld, %lld bytes for %d x %d)",
-               (long long)out_stride_t, (long long)out_stride_y, h, w);
-  if (ids) {
-    FGVC_REQUIRE(palette, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: ids without a palette");
-    FGVC_REQUIRE(alpha >= 0 && alpha <= 256, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: alpha=%d (0 .. 256)", alpha);
-    FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_pose_u8: ids: a row stride of at least w = %d bytes, got %lld", w, (long long)ids_stride_y);
-  }
+  if (int rc = render_check_operands(fn, c, P > 0 && icon)) return rc;
   if (heat) {
-    FGVC_REQUIRE(heat_colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat without heat_colors");
-    FGVC_REQUIRE(isfinite(heat_gain) && heat_gain > 0.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat_gain=%g (finite, > 0)", heat_gain);
-    FGVC_REQUIRE(heat_alpha >= 0.0 && heat_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: heat_alpha=%g (0 .. 1)", heat_alpha);
+    FGVC_REQUIRE(heat_colors, FGVC_ERR_INVALID_ARG, "%s: heat without heat_colors", fn);
+    FGVC_REQUIRE(isfinite(heat_gain) && heat_gain > 0.0, FGVC_ERR_INVALID_ARG, "%s: heat_gain=%g (finite, > 0)", fn, heat_gain);
+    FGVC_REQUIRE(heat_alpha >= 0.0 && heat_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "%s: heat_alpha=%g (0 .. 1)", fn, heat_alpha);
     FGVC_REQUIRE(heat_stride_y >= w && (T == 1 || heat_stride_t >= 0) && (K == 1 || heat_stride_k >= 0), FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_pose_u8: heat: a row stride of at least w = %d elements and non-negative strides, got %lld, %lld, %lld", w,
+                 "%s: heat: a row stride of at least w = %d elements and non-negative strides, got %lld, %lld, %lld", fn, w,
                  (long long)heat_stride_t, (long long)heat_stride_k, (long long)heat_stride_y);
     FGVC_REQUIRE((reinterpret_cast<uintptr_t>(heat) & (heat_f64 ? 7u : 3u)) == 0, FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_pose_u8: heat must be aligned to its element size");
+                 "%s: heat must be aligned to its element size", fn);
   }
   if (P > 0 && (E > 0 || icon)) {
-    FGVC_REQUIRE(tracks, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limbs or dots without tracks");
-    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: tracks: a negative frame stride (%lld)",
-                 (long long)tracks_stride_t);
-    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_pose_u8: visibles: a negative frame stride (%lld)", (long long)visibles_stride_t);
+    FGVC_REQUIRE(tracks, FGVC_ERR_INVALID_ARG, "%s: limbs or dots without tracks", fn);
+    FGVC_REQUIRE(T == 1 || tracks_stride_t >= 0, FGVC_ERR_INVALID_ARG, "%s: tracks: a negative frame stride (%lld)", fn, c.trk_st);
+    FGVC_REQUIRE(T == 1 || !visibles || visibles_stride_t >= 0, FGVC_ERR_INVALID_ARG, "%s: visibles: a negative frame stride (%lld)", fn,
+                 c.vis_st);
     if (E > 0) {
-      FGVC_REQUIRE(skeleton && limb_colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limbs without a skeleton or limb_colors");
-      FGVC_REQUIRE(limb_width >= 1.0 && limb_width <= 16.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limb_width=%g (1 .. 16)", limb_width);
-      FGVC_REQUIRE(limb_alpha >= 0.0 && limb_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: limb_alpha=%g (0 .. 1)", limb_alpha);
-      FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: ro2=%g, g=%g (both positive, ro2 <= 81)", ro2, g);
-      FGVC_REQUIRE((reinterpret_cast<uintptr_t>(skeleton) & 3u) == 0, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: skeleton must be 4-byte aligned");
+      FGVC_REQUIRE(skeleton && limb_colors, FGVC_ERR_INVALID_ARG, "%s: limbs without a skeleton or limb_colors", fn);
+      FGVC_REQUIRE(limb_width >= 1.0 && limb_width <= 16.0, FGVC_ERR_INVALID_ARG, "%s: limb_width=%g (1 .. 16)", fn, limb_width);
+      FGVC_REQUIRE(limb_alpha >= 0.0 && limb_alpha <= 1.0, FGVC_ERR_INVALID_ARG, "%s: limb_alpha=%g (0 .. 1)", fn, limb_alpha);
+      FGVC_REQUIRE(ro2 > 0.0 && g > 0.0 && ro2 <= 81.0, FGVC_ERR_INVALID_ARG, "%s: ro2=%g, g=%g (both positive, ro2 <= 81)", fn, ro2, g);
+      FGVC_REQUIRE((reinterpret_cast<uintptr_t>(skeleton) & 3u) == 0, FGVC_ERR_INVALID_ARG, "%s: skeleton must be 4-byte aligned", fn);
     }
-    if (icon) {
-      FGVC_REQUIRE(colors, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: dots without colors");
-      FGVC_REQUIRE(radius >= 1, FGVC_ERR_INVALID_ARG, "fgvc_render_pose_u8: radius=%d (at least 1)", radius);
-      FGVC_REQUIRE(radius <= 31, FGVC_ERR_UNSUPPORTED, "fgvc_render_pose_u8: radius=%d beyond 31", radius);
-    }
-    FGVC_REQUIRE(((reinterpret_cast<uintptr_t>(tracks) | reinterpret_cast<uintptr_t>(icon)) & 7u) == 0, FGVC_ERR_INVALID_ARG,
-                 "fgvc_render_pose_u8: tracks and icon must be 8-byte aligned");
+    FGVC_REQUIRE(!icon || colors, FGVC_ERR_INVALID_ARG, "%s: dots without colors", fn);
+    FGVC_REQUIRE(aligned8(tracks, icon), FGVC_ERR_INVALID_ARG, "%s: tracks and icon must be 8-byte aligned", fn);
   }
   const int reach = E > 0 ? (int)ceil(limb_width / 2.0 + 0.5) : 0;    // ceil(ro): what a limb's box is grown by
-  return render_pose_launch(frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
-                            palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p,
-                            visibles_stride_t, colors, P, radius, icon, skeleton, E, limb_colors, reach, ro2, g, limb_alpha, heat, heat_f64 != 0,
-                            heat ? K : 0, heat_stride_t, heat_stride_k, heat_stride_y, heat_colors, heat_gain, heat_alpha, (hipStream_t)stream);
+  return render_pose_launch(c, skeleton, E, limb_colors, reach, ro2, g, limb_alpha, heat, heat_f64 != 0, heat ? K : 0, heat_stride_t,
+                            heat_stride_k, heat_stride_y, heat_colors, heat_gain, heat_alpha, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

@@ -1,7 +1,8 @@
 // Pose: overlay, then the joints' heat maps blended in, then the skeleton's limbs as anti-aliased line segments,
 // then the dots, onto uint8 RGB video, all T frames in ONE launch -- fgvc_amd/viz.py's host backend, bit for bit.  The load, overlay,
-// points and store are render_body.hpp's; the limbs are segments.hpp's stage (the trail's compaction and per-pixel rule) with an item
-// source of its own; this file adds that source and the heat loop.
+// points and store are render_body.hpp's, and so are the fill of the shared arguments and the launch loop; the limbs are segments.hpp's
+// stage (the trail's compaction and per-pixel rule) with an item source of its own; this file adds that source, the heat loop, its
+// stage's arguments and the launch lines.
 //   * heat: for k = 0 .. K - 1 in order a lane reads its 4 x 2 values of map k (f32 or f64, through the maps' frame, channel and row
 //     strides; 16-byte loads where the row's address allows them) and blends colour k in:
 //       a = min(max(v gain, 0), 1) alpha with v widened to double;  not a > 0 (zero, negative, NaN): the pixel keeps its value;
@@ -128,36 +129,22 @@ template <typename HT>
 __global__ __launch_bounds__(RN_BLOCK) void render_pose_kernel(const RenderArgs a, const PoseArgs b) { render_body(a, PoseStage<HT>{a, b}); }
 
 // icon == null: no dots; heat == null: no maps; E == 0: no limbs
-int render_pose_launch(const uint8_t* frames, long long f_st, long long f_sy, uint8_t* out, long long o_st, long long o_sy, int T, int h, int w,
-                       const uint8_t* ids, long long i_st, long long i_sy, const uint8_t* palette, int alpha, int contour,
-                       const double* tracks, long long trk_sp, long long trk_st, const uint8_t* visibles, long long vis_sp, long long vis_st,
-                       const uint8_t* colors, int P, int radius, const double* icon, const int32_t* skeleton, int E,
-                       const uint8_t* limb_colors, int reach, double ro2, double g, double limb_alpha, const void* heat, int heat_f64, int K,
-                       long long h_st, long long h_sk, long long h_sy, const uint8_t* heat_colors, double heat_gain, double heat_alpha,
-                       hipStream_t s) {
-  if (T == 0 || h == 0 || w == 0) return FGVC_OK;
-  RenderArgs a;
-  a.frames = frames; a.out = out; a.ids = ids; a.palette = palette;
-  a.tracks = P > 0 && icon ? tracks : nullptr; a.visibles = visibles; a.colors = colors; a.icon = icon;
-  a.f_st = f_st; a.f_sy = f_sy; a.o_st = o_st; a.o_sy = o_sy; a.i_st = i_st; a.i_sy = i_sy;
-  a.trk_sp = trk_sp; a.trk_st = trk_st; a.vis_sp = vis_sp; a.vis_st = vis_st;
-  a.h = h; a.w = w; a.xtiles = cdiv(w, RN_COLS); a.alpha = alpha; a.contour = contour; a.P = P; a.radius = radius;
+int render_pose_launch(const RenderCall& c, const int32_t* skeleton, int E, const uint8_t* limb_colors, int reach, double ro2, double g,
+                       double limb_alpha, const void* heat, int heat_f64, int K, long long h_st, long long h_sk, long long h_sy,
+                       const uint8_t* heat_colors, double heat_gain, double heat_alpha, hipStream_t s) {
+  RenderArgs a = render_args(c, true);
   PoseArgs b;
-  b.tracks = tracks; b.skeleton = skeleton; b.limb_colors = limb_colors;
+  b.tracks = c.tracks; b.skeleton = skeleton; b.limb_colors = limb_colors;
   b.heat = K > 0 ? heat : nullptr; b.heat_colors = heat_colors;
   b.h_st = h_st; b.h_sk = h_sk; b.h_sy = h_sy;
   b.ro2 = ro2; b.g = g; b.limb_alpha = limb_alpha; b.heat_gain = heat_gain; b.heat_alpha = heat_alpha;
-  b.E = P > 0 && tracks ? E : 0; b.K = K; b.reach = reach;
-  for (int t0 = 0; t0 < T; t0 += 65535) {                             // grid.y is 16-bit
-    a.t0 = t0;
-    const dim3 grid(a.xtiles * cdiv(h, RN_ROWS), imin(T - t0, 65535));
+  b.E = c.P > 0 && c.tracks ? E : 0; b.K = K; b.reach = reach;
+  return render_launches("fgvc_render_pose_u8", a, c.T, [&](dim3 grid) {
     if (heat_f64)
       render_pose_kernel<double><<<grid, RN_BLOCK, 0, s>>>(a, b);
     else
       render_pose_kernel<float><<<grid, RN_BLOCK, 0, s>>>(a, b);
-    FGVC_CHECK_LAUNCH("fgvc_render_pose_u8");
-  }
-  return FGVC_OK;
+  });
 }
 
 }  // namespace fgvc

@@ -1,6 +1,8 @@
-// The renderer's shared pieces (DESIGN.md sections 16 and 21): the tile, the 12-byte load and store, and the body of the one-launch kernel --
-// load, overlay, [a stage of the including file], points, store.  render.hip instantiates it with no stage (fgvc_render_frames_u8),
-// trails.hip with the trail stage between the overlay and the points (fgvc_render_trails_u8).
+// The renderer's shared pieces (DESIGN.md sections 16, 21 and 23): the tile, the 12-byte load and store, and the body of the one-launch
+// kernel -- load, overlay, [a stage of the including file], points, store.  render.hip instantiates it with no stage
+// (fgvc_render_frames_u8), trails.hip with the trail stage between the overlay and the points (fgvc_render_trails_u8), pose.hip with the
+// heat maps and limbs there (fgvc_render_pose_u8).  At the end, the host side the three launchers share: the fill of RenderArgs from
+// render_host.hpp's RenderCall and the launch loop over the frames.
 //   * a workgroup owns RN_ROWS rows x RN_COLS columns of one frame; a lane owns 4 consecutive pixels (12 bytes) of RN_ROWS / 4 rows and keeps
 //     them in registers from its one load to its one store, so `out` may be `frames`;
 //   * the 12 bytes of a lane start at any address (W * 3 is generally no multiple of 4, and a cropped view starts anywhere): they are moved as
@@ -19,6 +21,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "render_host.hpp"
 
 #pragma clang fp contract(off)
 
@@ -259,6 +262,30 @@ __device__ __forceinline__ void render_body(const RenderArgs& a, const Stage& st
         if (k < npx * 3) q[k] = (uint8_t)v[rr][k];
     }
   }
+}
+
+// ---- host: what the three launchers share ----
+// the kernel's arguments of a call; dots_need_icon (trails, pose): no icon, no point stage.  t0 is the launch loop's
+inline RenderArgs render_args(const RenderCall& c, bool dots_need_icon) {
+  RenderArgs a;
+  a.frames = c.frames; a.out = c.out; a.ids = c.ids; a.palette = c.palette;
+  a.tracks = c.P > 0 && (c.icon || !dots_need_icon) ? c.tracks : nullptr; a.visibles = c.visibles; a.colors = c.colors; a.icon = c.icon;
+  a.f_st = c.f_st; a.f_sy = c.f_sy; a.o_st = c.o_st; a.o_sy = c.o_sy; a.i_st = c.i_st; a.i_sy = c.i_sy;
+  a.trk_sp = c.trk_sp; a.trk_st = c.trk_st; a.vis_sp = c.vis_sp; a.vis_st = c.vis_st;
+  a.t0 = 0; a.h = c.h; a.w = c.w; a.xtiles = cdiv(c.w, RN_COLS); a.alpha = c.alpha; a.contour = c.contour; a.P = c.P; a.radius = c.radius;
+  return a;
+}
+
+// launch(grid) enqueues the entry's kernel on `a`: once per 65535 frames (grid.y is 16-bit), a.t0 set; `entry` names a failure
+template <class Launch>
+int render_launches(const char* entry, RenderArgs& a, int T, const Launch& launch) {
+  if (a.h == 0 || a.w == 0) return FGVC_OK;
+  for (int t0 = 0; t0 < T; t0 += 65535) {
+    a.t0 = t0;
+    launch(dim3(a.xtiles * cdiv(a.h, RN_ROWS), imin(T - t0, 65535)));
+    FGVC_CHECK_LAUNCH(entry);
+  }
+  return FGVC_OK;
 }
 
 }  // namespace fgvc

@@ -1,7 +1,7 @@
 // Motion trails: overlay, then every point's last L steps as anti-aliased line segments, then the dots, onto uint8
 // RGB video, all T frames in ONE launch -- fgvc_amd/viz.py's host backend, bit for bit.  The load, overlay, points and store are
-// render_body.hpp's; the stage between the overlay and the points is segments.hpp's (the compaction and the per-pixel rule, shared with
-// pose.hip's limbs); this file adds where a trail's items come from.
+// render_body.hpp's, and so are the fill of the shared arguments and the launch loop; the stage between the overlay and the points is segments.hpp's (the compaction and the per-pixel rule, shared with
+// pose.hip's limbs); this file adds where a trail's items come from, its stage's arguments and the launch line.
 //   * on frame t a point has n = min(t, L) segments, s = t - n .. t - 1, segment s from tracks[i][s] + 0.5 to tracks[i][s + 1] + 0.5: the
 //     frame's P n candidate items (item = i n + k, s = t - n + k: point order, oldest first), each with the fade factor of its age;
 //   * the list is 14 KB beside the point stage's 12 KB: 26.4 KB, six workgroups of 4 waves in a compute unit's 160 KB, which is also what
@@ -73,29 +73,14 @@ struct TrailStage {
 __global__ __launch_bounds__(RN_BLOCK) void render_trails_kernel(const RenderArgs a, const TrailArgs b) { render_body(a, TrailStage{b}); }
 
 // icon == null: no dots (the trails alone)
-int render_trails_launch(const uint8_t* frames, long long f_st, long long f_sy, uint8_t* out, long long o_st, long long o_sy, int T, int h, int w,
-                         const uint8_t* ids, long long i_st, long long i_sy, const uint8_t* palette, int alpha, int contour,
-                         const double* tracks, long long trk_sp, long long trk_st, const uint8_t* visibles, long long vis_sp, long long vis_st,
-                         const uint8_t* colors, int P, int radius, const double* icon, int trail, int reach, double ro2, double g,
-                         const double* fade, const uint8_t* time_colors, hipStream_t s) {
-  if (T == 0 || h == 0 || w == 0) return FGVC_OK;
-  RenderArgs a;
-  a.frames = frames; a.out = out; a.ids = ids; a.palette = palette;
-  a.tracks = P > 0 && icon ? tracks : nullptr; a.visibles = visibles; a.colors = colors; a.icon = icon;
-  a.f_st = f_st; a.f_sy = f_sy; a.o_st = o_st; a.o_sy = o_sy; a.i_st = i_st; a.i_sy = i_sy;
-  a.trk_sp = trk_sp; a.trk_st = trk_st; a.vis_sp = vis_sp; a.vis_st = vis_st;
-  a.h = h; a.w = w; a.xtiles = cdiv(w, RN_COLS); a.alpha = alpha; a.contour = contour; a.P = P; a.radius = radius;
+int render_trails_launch(const RenderCall& c, int trail, int reach, double ro2, double g, const double* fade, const uint8_t* time_colors,
+                         hipStream_t s) {
+  RenderArgs a = render_args(c, true);
   TrailArgs b;
-  b.tracks = tracks; b.visibles = visibles; b.colors = colors; b.time_colors = time_colors; b.fade = fade;
-  b.trk_sp = trk_sp; b.trk_st = trk_st; b.vis_sp = vis_sp; b.vis_st = vis_st;
-  b.ro2 = ro2; b.g = g; b.P = P; b.L = P > 0 ? trail : 0; b.reach = reach;
-  for (int t0 = 0; t0 < T; t0 += 65535) {                             // grid.y is 16-bit
-    a.t0 = t0;
-    const dim3 grid(a.xtiles * cdiv(h, RN_ROWS), imin(T - t0, 65535));
-    render_trails_kernel<<<grid, RN_BLOCK, 0, s>>>(a, b);
-    FGVC_CHECK_LAUNCH("fgvc_render_trails_u8");
-  }
-  return FGVC_OK;
+  b.tracks = c.tracks; b.visibles = c.visibles; b.colors = c.colors; b.time_colors = time_colors; b.fade = fade;
+  b.trk_sp = c.trk_sp; b.trk_st = c.trk_st; b.vis_sp = c.vis_sp; b.vis_st = c.vis_st;
+  b.ro2 = ro2; b.g = g; b.P = c.P; b.L = c.P > 0 ? trail : 0; b.reach = reach;
+  return render_launches("fgvc_render_trails_u8", a, c.T, [&](dim3 grid) { render_trails_kernel<<<grid, RN_BLOCK, 0, s>>>(a, b); });
 }
 
 }  // namespace fgvc

@@ -1842,12 +1842,17 @@ def render_frames(frames_u8: torch.Tensor, ids: Optional[torch.Tensor] = None, p
     Frames, ids and `out` are read and written through their own frame and row strides (a time slice or a cropped window is not copied;
     pixels must be packed); tracks of another float type are converted to float64 first (exact).  `out`: a (T, H, W, 3) uint8 tensor to write
     into, `frames_u8` itself included; neither ids nor tracks: a copy."""
-    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, None)
+    head, out, _, hold = _render_head(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out)
+    if head is not None:
+        _lib.call("fgvc_render_frames_u8", *head, _stream(out))
+    return out
 
 
-def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, trails, pose=None):
-    """render_frames (trails None), render_trails (trails = (L, linewidth, fade, time_colors, dots)) and render_pose (trails = (.., dots),
-    pose = its stage's arguments): one set of checks, one launch."""
+def _render_head(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, dots=True):
+    """What render_frames, render_trails and render_pose share: the checks on the frames, `out`, ids and tracks (dots=False: no radius, no
+    icon).  Returns (head, out, colors, hold): the 25 leading arguments of the three entries (None when no pixel exists: nothing to
+    launch), the tensor to return, the points' colours as checked (None without tracks), and every tensor `head` points into -- the
+    caller keeps `hold` until its call has returned."""
     from . import viz
     if not frames_u8.is_cuda:
         raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path)")
@@ -1870,6 +1875,7 @@ def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, r
             raise ValueError(f"out: a uint8 tensor of shape {(T, H, W, 3)} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
         if packed(out, 3) is not out:
             raise ValueError(f"out: packed pixels and non-negative strides, got strides {out.stride()}")
+    hold = [f]
     args_ids = (None, 0, 0, None, 128, 0)
     if ids is not None:
         if not ids.is_cuda or ids.device != dev:
@@ -1887,8 +1893,9 @@ def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, r
         if tuple(palette.shape) != (256, 3) or palette.device != dev:
             raise ValueError(f"palette: (256, 3) on {dev}, got {tuple(palette.shape)} on {palette.device}")
         m, palette = packed(ids, 1), palette.contiguous()
-        args_ids = (m, m.stride(0), m.stride(1), palette, int(alpha), int(bool(contour)))
-    args_pts = (None, 0, 0, None, 0, 0, None, 0, 0, None)
+        args_ids = (_ptr(m), m.stride(0), m.stride(1), _ptr(palette), int(alpha), int(bool(contour)))
+        hold += [m, palette]
+    args_pts, col = (None, 0, 0, None, 0, 0, None, 0, 0, None), None
     if tracks is not None:
         if tracks.device != dev:
             raise ValueError(f"tracks: on {dev} with the frames, got {tracks.device}")
@@ -1897,7 +1904,6 @@ def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, r
         if tracks.dtype == torch.bool or tracks.dtype.is_complex:
             raise TypeError(f"tracks: a real number type, got {tracks.dtype}")
         P = tracks.shape[0]
-        dots = trails is None or trails[4]
         r = viz.check_radius(radius, H, W) if dots else 0
         tr = tracks.to(torch.float64)
         if tr.stride(2) != 1 or tr.data_ptr() % 8:
@@ -1915,31 +1921,15 @@ def _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, r
             raise TypeError(f"colors: expected torch.uint8, got {colors.dtype}")
         if tuple(colors.shape) != (P, 3) or colors.device != dev:
             raise ValueError(f"colors: {(P, 3)} on {dev} to go with the tracks, got {tuple(colors.shape)} on {colors.device}")
-        colors = colors.contiguous()
+        col = colors.contiguous()
         icon = _render_table(("icon", r), dev, lambda: viz.icon_table(r)) if dots else None
-        args_pts = (tr, tr.stride(0), tr.stride(1), vis, 0 if vis is None else vis.stride(0), 0 if vis is None else vis.stride(1), colors, P, r,
-                    icon)
+        args_vis = (None, 0, 0) if vis is None else (_ptr(vis), vis.stride(0), vis.stride(1))
+        args_pts = (_ptr(tr), tr.stride(0), tr.stride(1), *args_vis, _ptr(col), int(P), int(r), None if icon is None else _ptr(icon))
+        hold += [tr, vis, col, icon]
     if T == 0 or H == 0 or W == 0:
-        return out
-    m, m_st, m_sy, pal, al, ct = args_ids
-    tr, tr_sp, tr_st, vis, v_sp, v_st, col, P, r, icon = args_pts
-
-    def ptr(x):
-        return None if x is None else _ptr(x)
-    head = (_ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W, ptr(m), m_st, m_sy, ptr(pal), al, ct,
-            ptr(tr), tr_sp, tr_st, ptr(vis), v_sp, v_st, ptr(col), int(P or 0), int(r or 0), ptr(icon))
-    if pose is not None:
-        tail, hold = pose(P or 0, col)
-        _lib.call("fgvc_render_pose_u8", *head, *tail, _stream(f))
-        del hold
-        return out
-    if trails is None:
-        _lib.call("fgvc_render_frames_u8", *head, _stream(f))
-        return out
-    L, lw, fade, tcol = trails[:4]
-    ro2, g, _ = viz.trail_consts(lw)
-    _lib.call("fgvc_render_trails_u8", *head, L, lw, ro2, g, _ptr(fade), ptr(tcol) if T > 1 else None, _stream(f))
-    return out
+        return None, out, col, hold
+    head = (_ptr(f), f.stride(0), f.stride(1), _ptr(out), out.stride(0), out.stride(1), T, H, W, *args_ids, *args_pts)
+    return head, out, col, hold
 
 
 def render_trails(frames_u8: torch.Tensor, tracks: torch.Tensor, visibles: Optional[torch.Tensor] = None, colors: Optional[torch.Tensor] = None,
@@ -1973,7 +1963,12 @@ def render_trails(frames_u8: torch.Tensor, tracks: torch.Tensor, visibles: Optio
         if tuple(time_colors.shape) != (max(T - 1, 0), 3) or time_colors.device != dev:
             raise ValueError(f"time_colors: {(max(T - 1, 0), 3)} on {dev}, got {tuple(time_colors.shape)} on {time_colors.device}")
         time_colors = time_colors.contiguous()
-    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, (L, lw, fade, time_colors, bool(dots)))
+    head, out, _, hold = _render_head(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, bool(dots))
+    if head is not None:
+        ro2, g, _ = viz.trail_consts(lw)
+        tcol = None if time_colors is None or frames_u8.shape[0] <= 1 else _ptr(time_colors)
+        _lib.call("fgvc_render_trails_u8", *head, L, lw, ro2, g, _ptr(fade), tcol, _stream(out))
+    return out
 
 
 def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, visibles: Optional[torch.Tensor] = None,
@@ -1998,7 +1993,7 @@ def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, 
     dev = frames_u8.device
     T, H, W, _ = frames_u8.shape
     P = tracks.shape[0] if tracks is not None and tracks.dim() == 3 else 0
-    hargs = (None, 0, 0, 0, 0, 0, None, 1.0, 0.0)
+    maps = (None, 0, 0, 0, 0, 0, None, 1.0, 0.0)                                              # the entry's arguments from `heat` on
     if heat is not None:
         gain, h_alpha = viz._check_heat_consts(heat_gain, heat_alpha)
         if not isinstance(heat, torch.Tensor) or heat.device != dev:
@@ -2019,8 +2014,8 @@ def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, 
         if tuple(heat_colors.shape) != (K, 3) or heat_colors.device != dev:
             raise ValueError(f"heat_colors: {(K, 3)} on {dev} to go with the maps, got {tuple(heat_colors.shape)} on {heat_colors.device}")
         heat_colors = heat_colors.contiguous()
-        hargs = (heat, int(heat.dtype == torch.float64), K, heat.stride(0), heat.stride(1), heat.stride(2), heat_colors, gain, h_alpha)
-    largs = None
+        maps = (_ptr(heat), int(heat.dtype == torch.float64), K, heat.stride(0), heat.stride(1), heat.stride(2), _ptr(heat_colors), gain, h_alpha)
+    E = 0
     if skeleton is not None:
         lw, l_alpha = viz._check_limb_consts(limb_width, limb_alpha)
         # the table is checked on the host (the kernel skips, never reads, an edge outside 0 .. P - 1) and kept on the device per distinct
@@ -2036,19 +2031,13 @@ def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, 
                 raise ValueError(f"limb_colors: {(E, 3)} on {dev} to go with the skeleton, got {tuple(limb_colors.shape)} on {limb_colors.device}")
             limb_colors = limb_colors.contiguous()
         ro2, g, _ = viz.trail_consts(lw)
-        largs = (sk, E, limb_colors, lw, ro2, g, l_alpha)
-
-    def stage(P, col):
-        """the arguments of fgvc_render_pose_u8 after `icon`, and the tensors they point into (held by the caller until the launch is
-        queued); col: the joints' colours as _render checked them"""
-        h, hold = hargs, ()
-        if largs is None or largs[1] == 0:
-            limbs = (None, 0, None, 2.0, 1.0, 1.0, 1.0)
-        else:
-            sk, E, lcol, lw, ro2, g, l_alpha = largs
-            if lcol is None:
-                lcol = col[sk[:, 1].long()].contiguous()                                  # the colour of every edge's second joint
-            limbs, hold = (_ptr(sk), E, _ptr(lcol), lw, ro2, g, l_alpha), (sk, lcol)
-        args = (*limbs, None if h[0] is None else _ptr(h[0]), h[1], h[2], h[3], h[4], h[5], None if h[6] is None else _ptr(h[6]), h[7], h[8])
-        return args, hold
-    return _render(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, (0, 0.0, None, None, bool(dots)), stage)
+    head, out, col, hold = _render_head(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out, bool(dots))
+    if head is None:
+        return out
+    limbs = (None, 0, None, 2.0, 1.0, 1.0, 1.0)
+    if E:
+        if limb_colors is None:
+            limb_colors = col[sk[:, 1].long()].contiguous()                               # the colour of every edge's second joint
+        limbs = (_ptr(sk), E, _ptr(limb_colors), lw, ro2, g, l_alpha)
+    _lib.call("fgvc_render_pose_u8", *head, *limbs, *maps, _stream(out))
+    return out

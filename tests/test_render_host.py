@@ -202,18 +202,40 @@ def test_entry_refuses_bad_arguments_before_any_launch():
     buf = (ctypes.c_double * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
 
-    def call(frames=p, f_sy=12, out=p, o_st=48, o_sy=12, T=2, h=4, w=4, ids=None, i_sy=4, pal=None, alpha=128, tracks=None, colors=None, P=0, radius=2,
-             icon=None):
-        return lib.fgvc_render_frames_u8(frames, 48, f_sy, out, o_st, o_sy, T, h, w, ids, 16, i_sy, pal, alpha, 1, tracks, 4, 2, None, 0, 0, colors, P,
-                                         radius, icon, None)
-    for kw, code, text in ((dict(frames=None), 1, b"null pointer"), (dict(out=None), 1, b"null pointer"), (dict(T=-1), 1, b"negative size"),
-                           (dict(P=-1), 1, b"P=-1"), (dict(f_sy=11), 1, b"row stride"), (dict(o_sy=11), 1, b"overlap"),
-                           (dict(o_st=47), 1, b"overlap"), (dict(ids=p), 1, b"palette"), (dict(ids=p, pal=p, alpha=257), 1, b"alpha"),
-                           (dict(ids=p, pal=p, i_sy=3), 1, b"row stride"), (dict(tracks=p, colors=p, icon=p, P=1, radius=0), 1, b"radius"),
-                           (dict(tracks=p, colors=p, icon=p, P=1, radius=32), 2, b"radius"), (dict(tracks=p, P=1), 1, b"colors"),
-                           (dict(h=1 << 15, w=1 << 14), 1, b"2^29")):
+    # each entry's own arguments after `icon`, valid; trails: trail, linewidth, ro2, g, fade, time_colors; pose: no limbs, no maps
+    tails = {"fgvc_render_frames_u8": (), "fgvc_render_trails_u8": (1, 2.0, 2.25, 0.5, p, None),
+             "fgvc_render_pose_u8": (None, 0, None, 2.0, 2.25, 0.5, 1.0, None, 0, 0, 0, 0, 0, None, 1.0, 0.5)}
+
+    def call(entry="fgvc_render_frames_u8", frames=p, f_sy=12, out=p, o_st=48, o_sy=12, T=2, h=4, w=4, ids=None, i_sy=4, pal=None, alpha=128,
+             tracks=None, colors=None, P=0, radius=2, icon=None, tail=None):
+        return getattr(lib, entry)(frames, 48, f_sy, out, o_st, o_sy, T, h, w, ids, 16, i_sy, pal, alpha, 1, tracks, 4, 2, None, 0, 0, colors, P,
+                                   radius, icon, *(tails[entry] if tail is None else tail), None)
+    # what the three entries refuse alike, each under its own name
+    for entry in tails:
+        for kw, code, text in ((dict(frames=None), 1, b"null pointer"), (dict(out=None), 1, b"null pointer"), (dict(T=-1), 1, b"negative size"),
+                               (dict(P=-1), 1, b"P=-1"), (dict(f_sy=11), 1, b"row stride"), (dict(o_sy=11), 1, b"overlap"),
+                               (dict(o_st=47), 1, b"overlap"), (dict(ids=p), 1, b"palette"), (dict(ids=p, pal=p, alpha=257), 1, b"alpha"),
+                               (dict(ids=p, pal=p, i_sy=3), 1, b"row stride"), (dict(h=1 << 15, w=1 << 14), 1, b"2^29")):
+            assert call(entry, **kw) == code, (entry, kw, lib.fgvc_last_error())
+            assert text in lib.fgvc_last_error() and lib.fgvc_last_error().startswith(entry.encode() + b": "), (entry, kw, lib.fgvc_last_error())
+        assert call(entry, T=0) == 0 and call(entry, h=0) == 0                    # nothing to do: no launch
+    # what the points need differs between the entries: frames wants the radius, colors and the icon whenever there are tracks ...
+    for kw, code, text in ((dict(tracks=p, colors=p, icon=p, P=1, radius=0), 1, b"radius"),
+                           (dict(tracks=p, colors=p, icon=p, P=1, radius=32), 2, b"radius"), (dict(tracks=p, P=1), 1, b"colors")):
         assert call(**kw) == code and text in lib.fgvc_last_error(), (kw, lib.fgvc_last_error())
-    assert call(T=0) == 0 and call(h=0) == 0                                      # nothing to do: no launch
+        assert lib.fgvc_last_error().startswith(b"fgvc_render_frames_u8: ")
+    # ... trails reads the radius only with an icon (no icon: no dots), and takes time_colors in place of colors then
+    trails = dict(entry="fgvc_render_trails_u8", tracks=p, P=1)
+    assert call(**trails, colors=p, icon=p, radius=0) == 1 and lib.fgvc_last_error().startswith(b"fgvc_render_trails_u8: radius=0")
+    assert call(**trails, colors=p, icon=p, radius=32) == 2 and b"radius" in lib.fgvc_last_error()
+    assert call(**trails) == 1 and b"neither colors nor time_colors" in lib.fgvc_last_error()
+    assert call(**trails, icon=p, tail=(1, 2.0, 2.25, 0.5, p, p)) == 1 and b"neither colors nor time_colors" in lib.fgvc_last_error()
+    assert call(**trails, T=0, colors=p, radius=0) == 0                           # (accepted cases at T = 0: nothing is launched)
+    assert call(**trails, T=0, radius=0, tail=(1, 2.0, 2.25, 0.5, p, p)) == 0
+    # at T = 2 the same two get as far as the entry's last check, the alignment of `fade`: neither the radius nor the colours stopped them
+    odd = ctypes.c_void_p(p.value + 4)
+    for kw in (dict(colors=p, tail=(1, 2.0, 2.25, 0.5, odd, None)), dict(tail=(1, 2.0, 2.25, 0.5, odd, p))):
+        assert call(**trails, radius=0, **kw) == 1 and b"8-byte aligned" in lib.fgvc_last_error(), (kw, lib.fgvc_last_error())
 
 
 def test_hip_backend_without_a_gpu_raises(monkeypatch):
