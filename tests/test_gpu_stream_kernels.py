@@ -2,8 +2,10 @@
 f16 + FP6: main loop one generated assembly statement) -- against the kernels they replace (conv64_kernel<1>: option conv64_variant = 16;
 conv_split_kernel: option conv_debug = 1024).  Same arithmetic AND the same accumulation order, so every output is BIT-identical: split
 rows with their zero borders, f32 rows, feature-bank rows, overflow flags.  Sizes: partial tile columns, row counts that are no multiple
-of a tile, fewer tiles than workgroups and several per workgroup, 1 / 2 / 4 / 8 input chunks.  (The replaced kernels are themselves held
-to float64 in test_gpu_parity.py; the encoder-level tests there run on the new ones by default.)"""
+of a tile, fewer tiles than workgroups and several per workgroup, 1 / 2 / 4 / 8 input chunks.  (Both sides are themselves held to float64
+models of the sums they add in test_gpu_conv_ops.py -- bit for bit on planted operands, within four times an f32 emulation's error on
+realistic rows; test_gpu_parity.py compares them with torch's float64 convolution under the formats' flat bars, and its encoder-level
+tests run on the new kernels by default.)"""
 import pytest
 import torch
 
