@@ -131,6 +131,14 @@ SIGNATURES = {
     "fgvc_heatmap_coords_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "fgvc_heatmap_coords_peak_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "fgvc_softmap_readout_f32": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_guide_cells_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_readout_guided_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "fgvc_seg_readout_guided_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p]),
+    "fgvc_seg_readout_guided_conf_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double,
+                                             _p, _p, _p, _p, _p]),
+    "fgvc_guided_channel_chunk": (_i, []),
+    "fgvc_guided_tile_rows": (_i, []),
+    "fgvc_guided_tile_cols": (_i, []),
 }
 
 _lib = None

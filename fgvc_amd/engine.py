@@ -618,15 +618,176 @@ def _sweep_labels(bank: torch.Tensor, soft: torch.Tensor, sw: LabelSweep, Hf: in
             ops.seg_hard_onehot(soft[f], out=bank[f])
 
 
+# ---- the edge-aware read-out (test_cfg.readout, an extension key) ---------------------------------------------------
+#
+# The plain read-out interpolates the label grid and never looks at the frames.  type='guided' weighs the cells around an output pixel by
+# how close they are AND by how close their mean colour is to the pixel's own (joint bilateral upsampling), so that a label edge snaps to
+# the image edge beside it.  guided_readout_host states the rule in float64; ops.seg_readout_guided runs it in one kernel.
+
+READOUT_TYPES = ("bilinear", "guided")
+READOUT_RADII = (1, 2, 3)
+
+
+@dataclass
+class ReadoutConfig:
+    """test_cfg.readout = dict(type='guided', radius=2, sigma_space=1.0, sigma_range=0.1), parsed.  The default sigmas are untuned."""
+    type: str = "guided"
+    radius: int = 2
+    sigma_space: float = 1.0
+    sigma_range: float = 0.1
+
+
+def check_guided_args(Hf: int, Wf: int, pad_shape: Tuple[int, int], radius, sigma_space, sigma_range, name: str = "readout") -> None:
+    """The refusals the host rule and the parser share, each by name (ValueError)."""
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius not in READOUT_RADII:
+        raise ValueError(f"{name}: radius={radius!r} (an integer, one of {READOUT_RADII})")
+    for key, v in (("sigma_space", sigma_space), ("sigma_range", sigma_range)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{name}: {key}={v!r} (a positive finite number)")
+    if pad_shape is not None:
+        hp, wp = pad_shape
+        if Hf <= 0 or Wf <= 0 or hp % Hf or wp % Wf:
+            raise ValueError(f"{name}: the feature grid {Hf} x {Wf} does not divide the padded frame {hp} x {wp}")
+
+
+def parse_readout(spec) -> Optional[ReadoutConfig]:
+    """None or dict(type='bilinear') -> None (today's read-out, byte for byte).  dict(type='guided', ...) -> ReadoutConfig; an unknown
+    type, key or value raises ValueError by name, a non-mapping TypeError."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise TypeError(f"test_cfg.readout: a dict such as dict(type='guided', radius=2), got {type(spec).__name__}")
+    spec = dict(spec)
+    kind = spec.pop("type", None)
+    if kind not in READOUT_TYPES:
+        raise ValueError(f"test_cfg.readout: type={kind!r} (one of {READOUT_TYPES})")
+    allowed = ("radius", "sigma_space", "sigma_range") if kind == "guided" else ()
+    unknown = sorted(k for k in spec if k not in allowed)
+    if unknown:
+        raise ValueError(f"test_cfg.readout: unknown key(s) {unknown} for type={kind!r} (type" + "".join(f", {k}" for k in allowed) + ")")
+    if kind == "bilinear":
+        return None
+    rc = ReadoutConfig("guided", spec.get("radius", 2), spec.get("sigma_space", 1.0), spec.get("sigma_range", 0.1))
+    check_guided_args(1, 1, None, rc.radius, rc.sigma_space, rc.sigma_range, "test_cfg.readout")
+    return ReadoutConfig("guided", int(rc.radius), float(rc.sigma_space), float(rc.sigma_range))
+
+
+@dataclass
+class GuidedReadout:
+    """What guided_readout_host returns, all on the host."""
+    ids: torch.Tensor        # (n, h0, w0) uint8   argmax over C, the first maximum wins
+    conf: torch.Tensor       # (n, h0, w0) uint8   rint(255 * clamp(best - second, 0, 1)), 255 where C == 1
+    margin: torch.Tensor     # (n, h0, w0) float64 best - second (inf where C == 1)
+    values: torch.Tensor     # (n, h0, w0, C) float64 the filtered channel values
+    e_min: torch.Tensor      # (n, h0, w0) float64 the smallest exponent among each pixel's taps
+
+
+def guided_readout_host(labels: torch.Tensor, guide: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, int],
+                        pad: Tuple[int, int, int, int], out_shape: Tuple[int, int], norm: bool = True, radius: int = 2,
+                        sigma_space: float = 1.0, sigma_range: float = 0.1, shift: float = 0.0) -> GuidedReadout:
+    """The edge-aware read-out in float64 torch on the CPU: the contract ops.seg_readout_guided is held to.
+
+    labels (n, Hf*Wf, C): what seg_readout takes.  guide (n, 3, hp, wp): the padded Lab-normalised frames the encoder read; its values are
+    ASSUMED FINITE (as the labels are), nothing is promised otherwise.  (hp, wp) = pad_shape must be whole multiples of (Hf, Wf);
+    pad = (left, right, top, bottom); out_shape = (h0, w0).  Per frame:
+      cell colours   Gc[i, j] = the mean of the guide over the cell's (hp / Hf) x (wp / Wf) pixel block;
+      normalisation  (norm) per channel (L - min) / (max - min + 1e-12) where max > 0, else L: seg_readout's rule, but with the extremes
+                     taken over the FEATURE GRID, not over the interpolated full-resolution map (the filter below is a convex combination,
+                     so the affine map may be applied to the cell values first; the two read-outs therefore normalise slightly differently);
+      position       py = clamp((y + 0.5) hu / h0 - 0.5, 0, hu - 1) + top with hu the unpadded height, px alike; I = the guide sampled
+                     bilinearly at (py, px); fy = (py + 0.5) Hf / hp - 0.5, fx alike; centre cell (floor(fy + 0.5), floor(fx + 0.5));
+      taps           the (2 radius + 1)^2 cells around the centre cell that lie inside the grid:
+                     e = ((i - fy)^2 + (j - fx)^2) / (2 sigma_space^2) + |I - Gc[i, j]|^2 / (2 sigma_range^2) (+ shift),
+                     w = exp(-(e - e_min)), e_min the smallest e of the pixel: the ratio is unchanged and the denominator is >= 1;
+      value          sum(w L) / sum(w) per channel; id = argmax, the first maximum wins; conf as seg_readout_conf defines it.
+    `shift` is added to every exponent; it cancels (a test's handle on exactly that)."""
+    (hp, wp), (lw, uw, lh, uh), (h0, w0) = (int(v) for v in pad_shape), (int(v) for v in pad), (int(v) for v in out_shape)
+    check_guided_args(Hf, Wf, (hp, wp), radius, sigma_space, sigma_range, "guided_readout_host")
+    labels, guide = labels.detach().cpu().double(), guide.detach().cpu().double()
+    n, HW, C = labels.shape
+    if HW != Hf * Wf or tuple(guide.shape) != (n, 3, hp, wp):
+        raise ValueError(f"guided_readout_host: labels {tuple(labels.shape)} / guide {tuple(guide.shape)} against ({n}, {Hf * Wf}, C) / "
+                         f"({n}, 3, {hp}, {wp})")
+    hu, wu = hp - lh - uh, wp - lw - uw
+    if hu <= 0 or wu <= 0 or min(lh, uh, lw, uw) < 0:
+        raise ValueError("guided_readout_host: the unpadded window must lie inside the padded frame")
+    sy, sx = hp // Hf, wp // Wf
+    Gc = guide.reshape(n, 3, Hf, sy, Wf, sx).mean((3, 5))                                  # (n, 3, Hf, Wf)
+    L = labels.reshape(n, Hf, Wf, C)
+    if norm:
+        mn, mx = L.amin((1, 2), keepdim=True), L.amax((1, 2), keepdim=True)
+        L = torch.where(mx > 0, (L - mn) / (mx - mn + 1e-12), L)
+
+    def axis(n_out, n_un, off, n_pad, n_cells):
+        o = torch.arange(n_out, dtype=torch.float64)
+        p = ((o + 0.5) * n_un / n_out - 0.5).clamp(0, n_un - 1) + off
+        f = (p + 0.5) * n_cells / n_pad - 0.5
+        p0 = torch.floor(p).long().clamp(max=n_pad - 1)
+        return p0, (p0 + 1).clamp(max=n_pad - 1), p - p0, f, torch.floor(f + 0.5).long()
+
+    y0, y1, ly, fy, cy = axis(h0, hu, lh, hp, Hf)
+    x0, x1, lx, fx, cx = axis(w0, wu, lw, wp, Wf)
+    ly, lx = ly[None, :, None], lx[None, None, :]
+    ids = torch.empty((n, h0, w0), dtype=torch.uint8)
+    conf = torch.empty((n, h0, w0), dtype=torch.uint8)
+    margin = torch.empty((n, h0, w0), dtype=torch.float64)
+    values = torch.empty((n, h0, w0, C), dtype=torch.float64)
+    e_min = torch.empty((n, h0, w0), dtype=torch.float64)
+    for f in range(n):
+        g = guide[f]
+        I = ((1 - ly) * ((1 - lx) * g[:, y0][:, :, x0] + lx * g[:, y0][:, :, x1])
+             + ly * ((1 - lx) * g[:, y1][:, :, x0] + lx * g[:, y1][:, :, x1]))             # (3, h0, w0)
+        E, taps = [], []
+        for a in range(-radius, radius + 1):
+            i = cy + a
+            for b in range(-radius, radius + 1):
+                j = cx + b
+                inside = ((i >= 0) & (i < Hf))[:, None] & ((j >= 0) & (j < Wf))[None, :]
+                ic, jc = i.clamp(0, Hf - 1), j.clamp(0, Wf - 1)
+                e = (((i - fy) ** 2)[:, None] + ((j - fx) ** 2)[None, :]) / (2 * sigma_space ** 2) \
+                    + ((I - Gc[f][:, ic][:, :, jc]) ** 2).sum(0) / (2 * sigma_range ** 2) + shift
+                E.append(torch.where(inside, e, torch.full_like(e, float("inf"))))
+                taps.append((ic, jc))
+        E = torch.stack(E)
+        e_min[f] = E.amin(0)
+        W = torch.exp(-(E - e_min[f]))
+        num = torch.zeros((h0, w0, C), dtype=torch.float64)
+        for k, (ic, jc) in enumerate(taps):
+            num += W[k][..., None] * L[f][ic][:, jc]
+        values[f] = num / W.sum(0)[..., None]
+        ids[f] = values[f].argmax(-1).to(torch.uint8)
+        if C == 1:
+            margin[f] = float("inf")
+            conf[f] = 255
+        else:
+            top = values[f].topk(2, dim=-1).values
+            margin[f] = top[..., 0] - top[..., 1]
+            conf[f] = torch.round(255 * margin[f].clamp(0, 1)).to(torch.uint8)
+    return GuidedReadout(ids, conf, margin, values, e_min)
+
+
+def _guided_call(soft: torch.Tensor, guide: torch.Tensor, cells: Optional[torch.Tensor], Hf: int, Wf: int, pad_shape, pad, out_shape,
+                 norm_mask: bool, readout: ReadoutConfig, conf: bool = False, out=None):
+    if guide is None:
+        raise ValueError("the guided read-out needs the padded frames (guide=)")
+    return ops.seg_readout_guided(soft, guide, Hf, Wf, pad_shape, pad, out_shape, norm_mask, readout.radius, readout.sigma_space,
+                                  readout.sigma_range, conf=conf, out=out, cells=cells)
+
+
 def _mask_readout(soft: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
-                  out_shape: Tuple[int, int], norm_mask: bool) -> torch.Tensor:
+                  out_shape: Tuple[int, int], norm_mask: bool, guide: Optional[torch.Tensor] = None,
+                  readout: Optional[ReadoutConfig] = None) -> torch.Tensor:
     """(T, h0, w0) uint8: the argmax of the soft logits for frames 1.. (:772-802); frame 0 is the unpadded input map, nearest-resized to
-    the output size (:708-711)."""
+    the output size (:708-711).  readout (a ReadoutConfig): frames 1.. go through the edge-aware read-out with guide (T, 3, hp, wp), the
+    clip's padded frames; frame 0 is unchanged."""
     T = soft.shape[0]
     hp, wp = seg_map.shape
     lw, uw, lh, uh = pad
     masks = torch.empty((T, *out_shape), device=soft.device, dtype=torch.uint8)
-    if T > 1:
+    if T > 1 and readout is not None:
+        _guided_call(soft[1:], None if guide is None else guide[1:], None, Hf, Wf, (hp, wp), pad, out_shape, norm_mask, readout,
+                     out=masks[1:])
+    elif T > 1:
         ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, norm_mask, out=masks[1:])
     ref = seg_map[lh:hp - uh, lw:wp - uw].float()[None, None]
     masks[0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
@@ -635,13 +796,15 @@ def _mask_readout(soft: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, p
 
 def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
                     out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
-                    events: Optional[dict] = None, affinity_stats: Optional[dict] = None) -> torch.Tensor:
+                    events: Optional[dict] = None, affinity_stats: Optional[dict] = None, guide: Optional[torch.Tensor] = None,
+                    readout: Optional[ReadoutConfig] = None) -> torch.Tensor:
     """Semi-supervised VOS for one clip.  feats_hwc: the clip's bank as run_affinity (TrackerConfig) or run_local_affinity (LocalConfig)
     takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame index map; pad = (left, right, top, bottom) as
     pad_divide_by gives it; out_shape = (h0, w0).  On the local window the feature grid is whatever the encoder made of the padded
     frame: (Hf, Wf) need not divide (hp, wp).
     Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
-    resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output)."""
+    resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output).
+    readout (parse_readout's ReadoutConfig) with guide (T, 3, hp, wp) f32, the padded frames: the edge-aware read-out; None: the plain one."""
     T, dev = feats_hwc.shape[0], feats_hwc.device
     _record(events, "labels")
     C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
@@ -653,7 +816,7 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     soft = torch.empty_like(bank) if cfg.hard_prop else bank       # the read-out always sees the soft logits (:772-786)
     _sweep_labels(bank, soft, sw, Hf, Wf, cfg.hard_prop)
     _record(events, "readout")
-    masks = _mask_readout(soft, Hf, Wf, seg_map, pad, out_shape, cfg.norm_mask)
+    masks = _mask_readout(soft, Hf, Wf, seg_map, pad, out_shape, cfg.norm_mask, guide, readout)
     _record(events, "end")
     return masks
 
@@ -833,13 +996,17 @@ def _sweep_refs(bank: torch.Tensor, soft: torch.Tensor, sw: Optional[LabelSweep]
 
 def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Dict[int, torch.Tensor], pad: Tuple[int, int, int, int],
                          out_shape: Tuple[int, int], cfg, rc: RefsConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
-                         confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None):
+                         confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None,
+                         guide: Optional[torch.Tensor] = None, readout: Optional[ReadoutConfig] = None, cells: Optional[torch.Tensor] = None):
     """propagate_masks with index maps at any frames: seg_maps = {frame: padded (hp, wp) uint8 map on the device}; rc names the direction and
     the override rule (sweep_refs_host is the contract).  Returns (T, h0, w0) uint8 on the device; frame s0 (the earliest annotated one) is
     its given map, unpadded and nearest-resized, every other frame the read-out of its rows, frames before s0 under 'forward' zero.
     confidence: (masks, conf (T, h0, w0) uint8, stats (T, C, 2) int64) as ops.seg_readout_conf gives them; frame s0 has conf 255, frames
     that are not labelled at all conf 0.  One host read: the presence sets of all maps (C = 1 + the largest id present in any).
-    sweeps / counters: refs_sweeps' cache and counter; counters['sweeps'] counts these calls."""
+    sweeps / counters: refs_sweeps' cache and counter; counters['sweeps'] counts these calls.
+    readout / guide as propagate_masks takes them; cells: ops.guide_cells of the whole guide where the caller keeps it (a LabelSession)."""
+    if readout is not None and guide is None:
+        raise ValueError("the guided read-out needs the padded frames (guide=)")
     if isinstance(cfg, LocalConfig):
         raise NotImplementedError("test_cfg.refs: the local-window affinity (plan_local_clip has no start frame)")
     T, dev = feats_hwc.shape[0], feats_hwc.device
@@ -874,7 +1041,14 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
         _sweep_refs(bank, soft, sw, Hf, Wf, cfg.hard_prop, inj)
         if n < 2:
             return
-        if confidence:
+        if readout is not None:
+            out = _guided_call(soft[1:], guide[dst], None if cells is None else cells[dst], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask,
+                               readout, conf=confidence)
+            if confidence:
+                masks[dst], conf[dst], stats[dst] = out
+            else:
+                masks[dst] = out
+        elif confidence:
             m, c, st = ops.seg_readout_conf(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
             masks[dst], conf[dst], stats[dst] = m, c, st
         elif isinstance(dst, slice):

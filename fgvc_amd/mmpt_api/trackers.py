@@ -94,6 +94,7 @@ class LabelSession:
         model._raw_input(imgs, "imgs")
         model._refuse_occlusion("the mask call (imgs= / ref_seg_map=)")
         model._refuse_refs()
+        model._refuse_readout()
         if imgs.shape[0] != 1 or imgs.shape[1] != 1:
             raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
         if not imgs.is_cuda:
@@ -104,6 +105,9 @@ class LabelSession:
         frames, self.size, self.pad = model._label_frames(imgs)                               # (T, 3, hp, wp)
         self.n_frames, self.device = frames.shape[0], frames.device
         self.feats, self.Hf, self.Wf = model._label_feats(frames, index_map=True)
+        # test_cfg.readout type='guided': the padded frames and their cell colours stay with the session (a later propagate encodes nothing)
+        self.guide = model._readout_guide(frames, self.Hf, self.Wf)
+        self.cells = None if self.guide is None else ops.guide_cells(self.guide, self.Hf, self.Wf)
         self._sweeps = {}
         self.counters = dict(encodes=1, affinity_runs=0, sweeps=0)
 
@@ -122,7 +126,8 @@ class LabelSession:
         stats = []
         out = engine.propagate_masks_refs(self.feats, self.Hf, self.Wf, segs, self.pad, self.out_shape, self.cfg, rc,
                                           channels=self.model.feat_channels, stats_out=stats, confidence=bool(confidence),
-                                          sweeps=self._sweeps, counters=self.counters)
+                                          sweeps=self._sweeps, counters=self.counters, guide=self.guide,
+                                          readout=self.model.readout_cfg if self.guide is not None else None, cells=self.cells)
         self.model._refine_stats = stats or None
         self.model._check_kernels()
         device = self.model.masks_form == "device"
@@ -132,8 +137,8 @@ class LabelSession:
         return (masks, conf, st) if device else (masks.cpu().numpy().astype("float64"), conf.cpu().numpy(), st.cpu().numpy())
 
     def close(self):
-        """Drop the features and the cached lists."""
-        self.feats, self._sweeps = None, {}
+        """Drop the features, the cached lists and the guide."""
+        self.feats, self._sweeps, self.guide, self.cells = None, {}, None, None
 
 
 @MODELS.register_module()
@@ -154,6 +159,7 @@ class VanillaTracker(BaseTracker):
         self.last_confidence = None        # dict(conf, stats, frame_score) of the last mask call with test_cfg.refs.confidence=True, else None
         self.pose_cfg = engine.parse_pose(self.test_cfg.get("pose", None))         # test_cfg.pose (None: the coords=True call returns coordinates only)
         self.last_pose = None              # dict(peak, field) of the last coords=True call with test_cfg.pose set, else None
+        self.readout_cfg = engine.parse_readout(self.test_cfg.get("readout", None))   # test_cfg.readout (None / type='bilinear': the plain read-out)
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -548,6 +554,7 @@ class VanillaTracker(BaseTracker):
             raise TypeError("VanillaTracker.forward_test_seg needs imgs, ref_seg_map and img_meta")
         self._raw_input(imgs, "imgs")                      # uint8 frames: TypeError without test_cfg.input, the GPU-only rule with it
         self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
+        self._refuse_readout(soft=torch.is_tensor(ref_seg_map) and ref_seg_map.ndim == 4)
         if self.refs_cfg is None and hasattr(ref_seg_map, "keys"):
             raise TypeError("ref_seg_map: a mapping {frame index: index map} is taken with the extension key test_cfg.refs = "
                             "dict(direction='forward' | 'both', override='new' | 'all'); without it ref_seg_map is frame 0's tensor")
@@ -591,12 +598,37 @@ class VanillaTracker(BaseTracker):
         feats, Hf, Wf = self._label_feats(frames, index_map=True)
         stats, self.label_stats = [], {}
         masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats,
-                                       affinity_stats=self.label_stats)
+                                       affinity_stats=self.label_stats, guide=self._readout_guide(frames, Hf, Wf),
+                                       readout=self.readout_cfg)
         self._refine_stats = stats or None
         self._check_kernels()
         if self.masks_form == "device":
             return [masks]
         return [masks.cpu().numpy().astype("float64")]
+
+    # ---- the edge-aware read-out: test_cfg.readout (an extension key) -------------------------------------------------
+    def _refuse_readout(self, soft: bool = False):
+        """What test_cfg.readout = dict(type='guided') does not cover, each refused by name before any work.  Without the key: nothing."""
+        if self.readout_cfg is None:
+            return
+        g = self.test_cfg.get
+        if g("coords", False) or g("return_maps", False) or soft:
+            raise NotImplementedError("fgvc_amd: test_cfg.readout type='guided' reads out index maps only; coords=True / return_maps=True "
+                                      "(soft labels) are not covered -- remove one of the keys")
+        if g("save_np", False):
+            raise NotImplementedError("fgvc_amd: test_cfg.readout type='guided' with save_np=True: save_np is not supported; the masks are "
+                                      "returned (save them with numpy.save)")
+
+    def _readout_guide(self, frames: torch.Tensor, Hf: int, Wf: int) -> Optional[torch.Tensor]:
+        """The padded frames (T, 3, hp, wp) as the guided read-out's guide (contiguous f32), None without the key.  The feature grid has to
+        divide the padded frame: HRVanillaTracker's grid is whatever its encoder makes of the frame, and is refused by name where it does not."""
+        if self.readout_cfg is None:
+            return None
+        hp, wp = frames.shape[-2:]
+        if hp % Hf or wp % Wf:
+            raise NotImplementedError(f"fgvc_amd: test_cfg.readout type='guided' with {type(self).__name__}: the feature grid {Hf} x {Wf} does "
+                                      f"not divide the padded frame {hp} x {wp}; use type='bilinear' or frames the grid divides")
+        return frames.to(torch.float32).contiguous()
 
     # ---- index maps at any frame: test_cfg.refs (an extension key; DESIGN.md section 22) ----------------------------------------------------
     def _refuse_refs(self):

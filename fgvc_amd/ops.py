@@ -1445,6 +1445,63 @@ def seg_readout_conf(labels: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[in
     return masks, conf, stats
 
 
+# ---- edge-aware read-out (test_cfg.readout = dict(type='guided'); engine.guided_readout_host is the rule in float64) ---------------------
+
+def guide_cells(frames: torch.Tensor, Hf: int, Wf: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames (n, 3, hp, wp) f32, the padded Lab-normalised frames -> (n, HfWf, 3) f32: the mean colour of every cell's (hp / Hf) x
+    (wp / Wf) pixel block.  (Hf, Wf) must divide (hp, wp)."""
+    frames = _chk(frames, torch.float32, "frames")
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"frames: (n, 3, hp, wp), got {tuple(frames.shape)}")
+    n, _, hp, wp = frames.shape
+    if out is None:
+        out = torch.empty((n, Hf * Wf, 3), device=frames.device, dtype=torch.float32)
+    else:
+        assert out.is_cuda and out.is_contiguous() and out.shape == (n, Hf * Wf, 3) and out.dtype == torch.float32
+    _lib.call("fgvc_guide_cells_f32", _ptr(frames), n, hp, wp, Hf, Wf, _ptr(out), _stream(frames))
+    return out
+
+
+def seg_readout_guided(labels: torch.Tensor, guide: torch.Tensor, Hf: int, Wf: int, pad_shape: Tuple[int, int],
+                       pad: Tuple[int, int, int, int], out_shape: Tuple[int, int], norm: bool = True, radius: int = 2,
+                       sigma_space: float = 1.0, sigma_range: float = 0.1, conf: bool = False, out=None,
+                       cells: Optional[torch.Tensor] = None):
+    """The edge-aware read-out: labels (n, HfWf, C) f32 and guide (n, 3, hp, wp) f32 (the padded frames the encoder read, finite) ->
+    masks (n, h0, w0) uint8; conf=True: (masks, conf (n, h0, w0) uint8, stats (n, C, 2) int64) as seg_readout_conf defines them.  Every
+    output pixel is a joint bilateral combination of the (2 radius + 1)^2 cells around it (engine.guided_readout_host states the rule);
+    pad_shape, pad, out_shape and norm as seg_readout takes them, except that norm's extremes are those of the feature grid.
+    `out`: masks, or (masks, conf), to write into.  `cells`: guide_cells(guide, Hf, Wf) where the caller already has it."""
+    labels = _chk(labels, torch.float32, "labels")
+    guide = _chk(guide, torch.float32, "guide")
+    n, C = labels.shape[0], labels.shape[2]
+    assert labels.shape[1] == Hf * Wf
+    (hp, wp), (lw, uw, lh, uh), (h0, w0) = pad_shape, pad, out_shape
+    if tuple(guide.shape) != (n, 3, hp, wp):
+        raise ValueError(f"guide: ({n}, 3, {hp}, {wp}) to go with the labels and pad_shape, got {tuple(guide.shape)}")
+    dev = labels.device
+    if cells is None:
+        cells = guide_cells(guide, Hf, Wf)
+    else:
+        cells = _chk(cells, torch.float32, "cells")
+        if tuple(cells.shape) != (n, Hf * Wf, 3):
+            raise ValueError(f"cells: ({n}, {Hf * Wf}, 3), got {tuple(cells.shape)}")
+    outs = (out,) if torch.is_tensor(out) else (tuple(out) if out is not None else ())
+    if len(outs) not in (0, 2 if conf else 1):
+        raise ValueError("out: masks, or (masks, conf) with conf=True")
+    outs = outs or tuple(torch.empty((n, h0, w0), device=dev, dtype=torch.uint8) for _ in range(2 if conf else 1))
+    for t in outs:
+        assert t.is_cuda and t.is_contiguous() and t.shape == (n, h0, w0) and t.dtype == torch.uint8
+    ws = torch.empty((max(_lib.load().fgvc_seg_readout_guided_workspace_bytes(n, C), 4) + 3) // 4, device=dev, dtype=torch.int32)
+    head = (_ptr(labels), _ptr(guide), _ptr(cells), n, Hf, Wf, C, hp, wp, lh, lw, hp - lh - uh, wp - lw - uw, h0, w0, int(bool(norm)),
+            int(radius), float(sigma_space), float(sigma_range))
+    if not conf:
+        _lib.call("fgvc_seg_readout_guided_u8", *head, _ptr(outs[0]), _ptr(ws), _stream(labels))
+        return outs[0]
+    stats = torch.empty((n, C, 2), device=dev, dtype=torch.int64)
+    _lib.call("fgvc_seg_readout_guided_conf_u8", *head, _ptr(outs[0]), _ptr(outs[1]), _ptr(stats), _ptr(ws), _stream(labels))
+    return outs[0], outs[1], stats
+
+
 # ---- soft first-frame labels read out as joint coordinates (JHMDB / BADJA heat maps, vanilla_tracker.py:663-830 with coords=True) ----
 
 def _heat(heat: torch.Tensor) -> torch.Tensor:

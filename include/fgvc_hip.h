@@ -791,6 +791,39 @@ int fgvc_heatmap_coords_peak_f32(const float* bank, const void* map0, int map0_f
 int fgvc_softmap_readout_f32(const float* bank, const void* map0, int map0_f64, int T, int Hf, int Wf, int K, int hm, int wm, int hp,
                              int wp, int top, int left, int h0, int w0, int f_begin, int f_end, int out_f64, void* out, void* stream);
 
+/* ---- Edge-aware mask read-out (test_cfg.readout = dict(type='guided'); the float64 statement of the rule is
+ * engine.guided_readout_host).  guide [n][3][hp][wp] f32: the padded Lab-normalised frames the encoder read, finite values.  The feature
+ * grid must divide the padded frame: hp % Hf == 0 and wp % Wf == 0.
+ *
+ * fgvc_guide_cells_f32: cells [n][Hf*Wf][3] f32 = the mean of the guide over each cell's (hp / Hf) x (wp / Wf) pixel block. */
+int fgvc_guide_cells_f32(const float* guide, int n, int hp, int wp, int Hf, int Wf, float* cells, void* stream);
+
+/* Read-out of n frames: labels [n][Hf*Wf][C] f32 -> masks [n][h0][w0] uint8.  Per output pixel (y, x):
+ *   py = clamp((y + 0.5) h / h0 - 0.5, 0, h - 1) + top (px alike), I = the guide sampled bilinearly at (py, px),
+ *   fy = (py + 0.5) Hf / hp - 0.5 (fx alike), centre cell (floor(fy + 0.5), floor(fx + 0.5));
+ *   over the (2 radius + 1)^2 cells (i, j) around the centre cell that lie inside the grid:
+ *     e = ((i - fy)^2 + (j - fx)^2) / (2 sigma_space^2) + |I - cells[i][j]|^2 / (2 sigma_range^2),   w = exp(-(e - min e));
+ *   value_c = sum(w L_c) / sum(w), with L_c the labels normalised (norm != 0) per (frame, channel) by (x - min) / (max - min + 1e-12)
+ *   where max > 0, min / max taken over the FEATURE GRID (fgvc_seg_readout_u8 takes them over its interpolated map);
+ *   id = argmax_c value_c, the first maximum wins.
+ * f32 arithmetic; one launch for all frames after the two small pre-passes; no [n][C][h0][w0] map is written.
+ * The _conf form adds conf and stats as fgvc_seg_readout_conf_u8 defines them (conf = rint(255 clamp(best - second, 0, 1)), 255 where
+ * C == 1; stats [n][C][2] int64 = pixel count and conf sum per id, cleared here).
+ * cells: fgvc_guide_cells_f32's output for the same guide.  workspace: fgvc_seg_readout_guided_workspace_bytes(n, C) bytes of device
+ * scratch.  1 <= C <= 256, 1 <= radius <= 3, sigmas positive and finite.  An output so much smaller than the frame that one
+ * fgvc_guided_tile_rows() x fgvc_guided_tile_cols() tile's footprint of cells does not fit the LDS is refused (FGVC_ERR_UNSUPPORTED). */
+size_t fgvc_seg_readout_guided_workspace_bytes(int n, int C);
+int fgvc_seg_readout_guided_u8(const float* labels, const float* guide, const float* cells, int n, int Hf, int Wf, int C, int hp, int wp,
+                               int top, int left, int h, int w, int h0, int w0, int norm, int radius, double sigma_space,
+                               double sigma_range, uint8_t* masks, void* workspace, void* stream);
+int fgvc_seg_readout_guided_conf_u8(const float* labels, const float* guide, const float* cells, int n, int Hf, int Wf, int C, int hp,
+                                    int wp, int top, int left, int h, int w, int h0, int w0, int norm, int radius, double sigma_space,
+                                    double sigma_range, uint8_t* masks, uint8_t* conf, int64_t* stats, void* workspace, void* stream);
+/* the main kernel's output tile and the number of label channels it stages at a time (for tests that straddle them) */
+int fgvc_guided_channel_chunk(void);
+int fgvc_guided_tile_rows(void);
+int fgvc_guided_tile_cols(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,9 +237,12 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     first annotated frame the given one; --confidence also writes conf_%05d.png into --out and prints the frame scores."""
     T, H, W = frames.shape[:3]
     imgs, meta = _raw(a, frames, dev)[None, None], [dict(original_shape=(H, W))]
+    edge = {}
+    if a.edge_aware:               # test_cfg.readout (DESIGN.md section 24): label edges follow the frames' own
+        edge = dict(readout=dict(type="guided", radius=a.edge_radius, sigma_space=1.0, sigma_range=a.edge_sigma_range))
     if not a.mask:
         mask = _mask_png(a.first_mask, H, W, "--first-mask")
-        model = build_model(a, dev, input=_input(a, None), masks="device")
+        model = build_model(a, dev, input=_input(a, None), masks="device", **edge)
         with torch.no_grad():
             out = model(test_mode=True, imgs=imgs, ref_seg_map=torch.from_numpy(mask)[None].to(dev), img_meta=meta)
         return out[0]
@@ -250,7 +253,7 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
         if not t.lstrip("-").isdigit() or not 0 <= int(t) < T or int(t) in refs:
             raise ValueError(f"--mask {t} {path}: a frame index 0 .. {T - 1}, each frame once")
         refs[int(t)] = torch.from_numpy(_mask_png(path, H, W, "--mask"))
-    model = build_model(a, dev, input=_input(a, None), masks="device",
+    model = build_model(a, dev, input=_input(a, None), masks="device", **edge,
                         refs=dict(direction="both" if a.both_ways else "forward", override=a.override, confidence=a.confidence))
     with torch.no_grad():
         out = model(test_mode=True, imgs=imgs, ref_seg_map=refs, img_meta=meta)
@@ -365,6 +368,11 @@ def parse_args(argv=None):
                     help="with --mask: a later mask brings in its new objects only, or replaces the frame's labels (a correction)")
     ap.add_argument("--confidence", action="store_true",
                     help="with --mask: write conf_%%05d.png (the top-two gap per pixel) and print the frame scores and the frame to annotate next")
+    ap.add_argument("--edge-aware", action="store_true",
+                    help="--task vos: the edge-aware read-out (test_cfg.readout type='guided': the masks' edges follow the frames')")
+    ap.add_argument("--edge-radius", type=int, default=2, choices=(1, 2, 3), help="with --edge-aware: cells around a pixel, per side")
+    ap.add_argument("--edge-sigma-range", type=float, default=0.1, metavar="X",
+                    help="with --edge-aware: the colour sigma in Lab-normalised units (untuned default)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--host-render", action="store_true", help="paint (and, with --out-video, encode) with viz's numpy backend instead of the kernels")
     ap.add_argument("--out-video", default=None, metavar="OUT.y4m", help="also write the result as a YUV4MPEG2 file of 8-bit 4:2:0 frames")
@@ -404,6 +412,8 @@ def parse_args(argv=None):
         ap.error("--task vos needs --first-mask (or --mask T PNG)")
     if (a.both_ways or a.confidence or a.override != "new") and not a.mask:
         ap.error("--both-ways, --override and --confidence go with --mask T PNG")
+    if (a.edge_aware or a.edge_radius != 2 or a.edge_sigma_range != 0.1) and not (a.task == "vos" and a.edge_aware):
+        ap.error("--edge-aware goes with --task vos; --edge-radius and --edge-sigma-range go with --edge-aware")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
         ap.error("--yuv-matrix goes with a .y4m clip")
     if a.trails is not None and a.task != "points":

@@ -139,6 +139,9 @@ def main():
     ap.add_argument("--gpu-metrics", action="store_true",
                     help="--task vos: keep the propagated masks on the device (test_cfg.masks='device') and score J&F from the counts of "
                          "the library's fgvc_jf_counts_u8 (metrics.davis_jf(backend='hip')): the same numbers, DESIGN.md section 15")
+    ap.add_argument("--readout", choices=["bilinear", "guided"], default=None,
+                    help="--task vos: the mask read-out (test_cfg.readout = dict(type=...)); 'guided' is the edge-aware one, whose effect on "
+                         "real DAVIS J&F is unmeasured")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -223,6 +226,12 @@ def main():
         if a.task != "vos":
             raise SystemExit("--gpu-metrics goes with --task vos (the J&F of the mask path)")
         test_cfg = dict(test_cfg, masks="device")
+    if a.readout is not None:
+        if a.task not in ("vos", "ytvos"):
+            raise SystemExit("--readout goes with --task vos (the index-map read-out of the mask path)")
+        if distributed:
+            raise SystemExit("--readout runs on one GPU (--launcher none); the multi-GPU path is not covered")
+        test_cfg = dict(test_cfg, readout=dict(type=a.readout))      # 'guided': DESIGN.md section 24, its default radius and sigmas (untuned)
     model_cfg = dict(type=a.eval_arc or cfg.get("eval_arc", "VanillaTracker"), backbone=dict(cfg.model.backbone))   # :139
     for k in ("out_indices", "strides", "dilations"):                                        # :141-145
         if k in test_cfg:
