@@ -139,6 +139,7 @@ SIGNATURES = {
     "fgvc_guided_channel_chunk": (_i, []),
     "fgvc_guided_tile_rows": (_i, []),
     "fgvc_guided_tile_cols": (_i, []),
+    "fgvc_seg_fuse_rows_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -831,14 +831,16 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
 
 REFS_DIRECTIONS = ("forward", "both")
 REFS_OVERRIDES = ("new", "all")
+REFS_FUSES = (None, "linear")
 
 
 @dataclass
 class RefsConfig:
-    """test_cfg.refs = dict(direction='forward' | 'both', override='new' | 'all', confidence=False), parsed."""
+    """test_cfg.refs = dict(direction='forward' | 'both', override='new' | 'all', confidence=False, fuse=None | 'linear'), parsed."""
     direction: str = "forward"
     override: str = "new"
     confidence: bool = False
+    fuse: Optional[str] = None         # 'linear': forward and backward sweeps blended between annotated frames (section 25)
 
 
 def parse_refs(spec) -> Optional[RefsConfig]:
@@ -850,15 +852,22 @@ def parse_refs(spec) -> Optional[RefsConfig]:
         raise TypeError(f"test_cfg.refs: a dict such as dict(direction='forward', override='new'), got {type(spec).__name__}")
     spec = dict(spec)
     direction, override, confidence = spec.pop("direction", "forward"), spec.pop("override", "new"), spec.pop("confidence", False)
+    fuse = spec.pop("fuse", None)
     if spec:
-        raise ValueError(f"test_cfg.refs: unknown key(s) {sorted(spec)} (direction, override, confidence)")
+        raise ValueError(f"test_cfg.refs: unknown key(s) {sorted(spec)} (direction, override, confidence, fuse)")
     if direction not in REFS_DIRECTIONS:
         raise ValueError(f"test_cfg.refs: direction={direction!r} (one of {REFS_DIRECTIONS})")
     if override not in REFS_OVERRIDES:
         raise ValueError(f"test_cfg.refs: override={override!r} (one of {REFS_OVERRIDES})")
     if not isinstance(confidence, bool):
         raise ValueError(f"test_cfg.refs: confidence={confidence!r} (True or False)")
-    return RefsConfig(direction, override, confidence)
+    if fuse not in REFS_FUSES:
+        raise ValueError(f"test_cfg.refs: fuse={fuse!r} (one of {REFS_FUSES})")
+    if fuse is not None and (direction != "both" or override != "all"):
+        # a later map under 'new' is partial (YouTube-VOS's are): its background proves nothing, so no backward pass can start from it
+        raise ValueError(f"test_cfg.refs: fuse={fuse!r} needs direction='both' and override='all', got direction={direction!r}, "
+                         f"override={override!r}")
+    return RefsConfig(direction, override, confidence, fuse)
 
 
 def check_ref_maps(refs, n_frames: int, shape: Tuple[int, int]) -> Dict[int, torch.Tensor]:
@@ -957,26 +966,74 @@ def next_frame_to_annotate(frame_score, annotated) -> Optional[int]:
     return best
 
 
+# ---- forward and backward sweeps fused between annotated frames (refs fuse='linear') --------------------------------
+#
+# With annotated frames s_0 < .. < s_m the forward pass starts at s_0 and the backward pass at s_m, both with every later (earlier) map
+# injected whole (override='all').  Between two annotated frames the two passes' soft rows are blended linearly in time; the number of
+# cells on which they name different objects is the frame's disagreement.
+
+def fuse_refs_host(small: Dict[int, torch.Tensor], n_frames: int, fw=None, bw=None, hard_prop: bool = False):
+    """The contract of test_cfg.refs fuse='linear' in float64 torch, on given top-k lists.  small as sweep_refs_host takes it; fw: the lists
+    of the forward sub-clip s_0 .. T-1, bw: the lists of the reversed sub-clip s_m, s_m - 1, .., 0 (the LabelSweep refs_sweeps keeps under
+    (s_m, 'bw')).  F = sweep_refs_host(forward, 'all') from s_0; B = the same rule on the reversed sub-clip with the maps mirrored, flipped
+    back; under hard_prop each pass keeps its own hard bank and the soft rows are what is fused.
+    Returns (rows (T, HW, C) float64, disagree (T,) int64):
+      rows[t] = F[t] at an annotated frame (its one-hot map) and for t > s_m;  B[t] for t < s_0;
+                w F[t] + (1 - w) B[t], w = (s_{i+1} - t) / (s_{i+1} - s_i), for s_i < t < s_{i+1};
+      disagree[t] = the number of cells with argmax F[t] != argmax B[t] (the first maximum wins) for s_i < t < s_{i+1}, else 0.
+    One annotated frame: sweep_refs_host(direction='both') itself and zeros."""
+    frames = sorted(small)
+    s0, sm, T = frames[0], frames[-1], int(n_frames)
+    disagree = torch.zeros(T, dtype=torch.int64)
+    if len(frames) == 1:
+        return sweep_refs_host(small, T, fw=fw, bw=bw, direction="both", override="all", hard_prop=hard_prop), disagree
+    F = sweep_refs_host(small, T, fw=fw, direction="forward", override="all", hard_prop=hard_prop)
+    mirrored = {sm - t: small[t] for t in frames}
+    B = sweep_refs_host(mirrored, sm + 1, fw=bw, direction="forward", override="all", hard_prop=hard_prop).flip(0)      # B[t], t = 0 .. s_m
+    rows = F.clone()
+    rows[:s0] = B[:s0]
+    for a, b in zip(frames[:-1], frames[1:]):
+        for t in range(a + 1, b):
+            w = (b - t) / (b - a)
+            rows[t] = w * F[t] + (1.0 - w) * B[t]
+            disagree[t] = int((F[t].argmax(-1) != B[t].argmax(-1)).sum())
+    return rows, disagree
+
+
+def next_frame_to_annotate_by(disagree, annotated) -> Optional[int]:
+    """The un-annotated frame with the largest disagreement count, the lowest index among equals; None when every frame is annotated."""
+    counts = [int(v) for v in (disagree.tolist() if hasattr(disagree, "tolist") else disagree)]
+    done = set(int(t) for t in annotated)
+    best = None
+    for f, n in enumerate(counts):
+        if f not in done and (best is None or n > counts[best]):
+            best = f
+    return best
+
+
 def refs_sweeps(feats_hwc: torch.Tensor, Hf: int, Wf: int, s0: int, both: bool, cfg: TrackerConfig, channels: Optional[int] = None,
-                stats_out: Optional[list] = None, sweeps: Optional[dict] = None, counters: Optional[dict] = None):
+                stats_out: Optional[list] = None, sweeps: Optional[dict] = None, counters: Optional[dict] = None,
+                bw_from: Optional[int] = None):
     """(fw, bw): the LabelSweeps of the forward sub-clip s0 .. T-1 and (both, s0 > 0) of the reversed sub-clip s0 .. 0; None where the
     sub-clip has one frame.  `sweeps`: a cache keyed (s0, 'fw' | 'bw') that is read and filled; `counters['affinity_runs']` goes up by one
-    when this call had to compute a part."""
+    when this call had to compute a part.  bw_from (the fused branch: the last annotated frame s_m): the reversed sub-clip starts there
+    instead, cached under (s_m, 'bw'); no (s_m, 'fw') is computed."""
     if isinstance(cfg, LocalConfig):
         raise NotImplementedError("test_cfg.refs: the local-window affinity (plan_local_clip has no start frame)")
     T = feats_hwc.shape[0]
     sweeps = {} if sweeps is None else sweeps
+    sb = s0 if bw_from is None else int(bw_from)
     ran = False
     if (s0, "fw") not in sweeps:
         sweeps[(s0, "fw")] = label_affinity(feats_hwc[s0:], Hf, Wf, T - s0, cfg, channels, stats_out) if T - s0 > 1 else None
         ran = ran or T - s0 > 1
-    if both and s0 > 0 and (s0, "bw") not in sweeps:
-        rev = feats_hwc[:s0 + 1].flip(0).contiguous()
-        sweeps[(s0, "bw")] = label_affinity(rev, Hf, Wf, s0 + 1, cfg, channels, stats_out)
+    if both and sb > 0 and (sb, "bw") not in sweeps:
+        rev = feats_hwc[:sb + 1].flip(0).contiguous()
+        sweeps[(sb, "bw")] = label_affinity(rev, Hf, Wf, sb + 1, cfg, channels, stats_out)
         ran = True
     if ran and counters is not None:
         counters["affinity_runs"] = counters.get("affinity_runs", 0) + 1
-    return sweeps[(s0, "fw")], (sweeps[(s0, "bw")] if both and s0 > 0 else None)
+    return sweeps[(s0, "fw")], (sweeps[(sb, "bw")] if both and sb > 0 else None)
 
 
 def _sweep_refs(bank: torch.Tensor, soft: torch.Tensor, sw: Optional[LabelSweep], Hf: int, Wf: int, hard_prop: bool, inject: dict) -> None:
@@ -997,14 +1054,18 @@ def _sweep_refs(bank: torch.Tensor, soft: torch.Tensor, sw: Optional[LabelSweep]
 def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Dict[int, torch.Tensor], pad: Tuple[int, int, int, int],
                          out_shape: Tuple[int, int], cfg, rc: RefsConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
                          confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None,
-                         guide: Optional[torch.Tensor] = None, readout: Optional[ReadoutConfig] = None, cells: Optional[torch.Tensor] = None):
+                         guide: Optional[torch.Tensor] = None, readout: Optional[ReadoutConfig] = None, cells: Optional[torch.Tensor] = None,
+                         disagree_out: Optional[list] = None):
     """propagate_masks with index maps at any frames: seg_maps = {frame: padded (hp, wp) uint8 map on the device}; rc names the direction and
     the override rule (sweep_refs_host is the contract).  Returns (T, h0, w0) uint8 on the device; frame s0 (the earliest annotated one) is
     its given map, unpadded and nearest-resized, every other frame the read-out of its rows, frames before s0 under 'forward' zero.
     confidence: (masks, conf (T, h0, w0) uint8, stats (T, C, 2) int64) as ops.seg_readout_conf gives them; frame s0 has conf 255, frames
     that are not labelled at all conf 0.  One host read: the presence sets of all maps (C = 1 + the largest id present in any).
     sweeps / counters: refs_sweeps' cache and counter; counters['sweeps'] counts these calls.
-    readout / guide as propagate_masks takes them; cells: ops.guide_cells of the whole guide where the caller keeps it (a LabelSession)."""
+    readout / guide as propagate_masks takes them; cells: ops.guide_cells of the whole guide where the caller keeps it (a LabelSession).
+    rc.fuse='linear' with more than one annotated frame (fuse_refs_host is the contract): the forward sweep from the first and the backward
+    sweep from the last annotated frame, blended between the maps by ops.seg_fuse_rows, then the same read-outs; disagree_out (a list)
+    receives the (T,) int64 device tensor of per-frame disagreement counts.  With one annotated frame the call is direction='both'."""
     if readout is not None and guide is None:
         raise ValueError("the guided read-out needs the padded frames (guide=)")
     if isinstance(cfg, LocalConfig):
@@ -1024,7 +1085,9 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
         if chosen:
             inject[t - s0] = (seg_maps[t], ops.label_set_words(sorted(chosen)).to(dev))
     both = rc.direction == "both"
-    fw, bw = refs_sweeps(feats_hwc, Hf, Wf, s0, both, cfg, channels, stats_out, sweeps, counters)
+    sm = frames[-1]
+    fused = rc.fuse is not None and sm > s0                             # one annotated frame: nothing to fuse, the call is direction='both'
+    fw, bw = refs_sweeps(feats_hwc, Hf, Wf, s0, both, cfg, channels, stats_out, sweeps, counters, bw_from=sm if fused else None)
     if counters is not None:
         counters["sweeps"] = counters.get("sweeps", 0) + 1
     hp, wp = seg_maps[s0].shape
@@ -1033,32 +1096,57 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
     conf = torch.zeros_like(masks) if confidence else None
     stats = torch.zeros((T, C, 2), device=dev, dtype=torch.int64) if confidence else None
 
-    def run(n, sw, inj, dst):
-        """one sub-clip of n frames from one_hot(M_s0); the read-out of its frames 1.. goes to the clip frames `dst` (a slice or an index)"""
+    def sweep(n, first, sw, inj):
+        """the soft rows (n, HW, C) of one sub-clip of n frames that starts from one_hot(M_first)"""
         bank = torch.zeros((n, Hf * Wf, C), device=dev, dtype=torch.float32)
-        ops.seg_onehot_labels(seg_maps[s0], Hf, Wf, C, out=bank[0])
+        ops.seg_onehot_labels(seg_maps[first], Hf, Wf, C, out=bank[0])
         soft = torch.empty_like(bank) if cfg.hard_prop else bank
         _sweep_refs(bank, soft, sw, Hf, Wf, cfg.hard_prop, inj)
-        if n < 2:
-            return
+        return soft
+
+    def read(rows, dst):
+        """the read-out of the row blocks `rows` goes to the clip frames `dst` (a slice or an index)"""
         if readout is not None:
-            out = _guided_call(soft[1:], guide[dst], None if cells is None else cells[dst], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask,
+            out = _guided_call(rows, guide[dst], None if cells is None else cells[dst], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask,
                                readout, conf=confidence)
             if confidence:
                 masks[dst], conf[dst], stats[dst] = out
             else:
                 masks[dst] = out
         elif confidence:
-            m, c, st = ops.seg_readout_conf(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
+            m, c, st = ops.seg_readout_conf(rows, Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
             masks[dst], conf[dst], stats[dst] = m, c, st
         elif isinstance(dst, slice):
-            ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[dst])
+            ops.seg_readout(rows, Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask, out=masks[dst])
         else:
-            masks[dst] = ops.seg_readout(soft[1:], Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
+            masks[dst] = ops.seg_readout(rows, Hf, Wf, (hp, wp), pad, out_shape, cfg.norm_mask)
 
-    run(T - s0, fw, inject, slice(s0 + 1, T))
-    if both and s0 > 0:
-        run(s0 + 1, bw, {}, torch.arange(s0 - 1, -1, -1, device=dev))
+    def run(n, sw, inj, dst):
+        """one sub-clip of n frames from one_hot(M_s0); the read-out of its frames 1.. goes to the clip frames `dst`"""
+        soft = sweep(n, s0, sw, inj)
+        if n >= 2:
+            read(soft[1:], dst)
+
+    if fused:
+        # forward from s_0 and backward from s_m, every other map injected whole; the frames between two maps are blended in ONE launch,
+        # written over the forward pass's rows, so that the read-outs below see the clip's rows where the unfused call has them
+        soft_f = sweep(T - s0, s0, fw, inject)
+        soft_b = sweep(sm + 1, sm, bw, {sm - t: (seg_maps[t], ops.label_set_words(sorted(ids)).to(dev))
+                                        for t, ids in zip(frames[:-1], present[:-1])})
+        between = [(t, (b - t) / (b - a)) for a, b in zip(frames[:-1], frames[1:]) for t in range(a + 1, b)]
+        disagree = torch.zeros((T,), device=dev, dtype=torch.int64)
+        if between:
+            _, counts = ops.seg_fuse_rows(soft_f, soft_b, [t - s0 for t, _ in between], [sm - t for t, _ in between], [w for _, w in between])
+            disagree[torch.tensor([t for t, _ in between], device=dev)] = counts
+        if disagree_out is not None:
+            disagree_out.append(disagree)
+        read(soft_f[1:], slice(s0 + 1, T))
+        if s0 > 0:
+            read(soft_b[sm - s0 + 1:], torch.arange(s0 - 1, -1, -1, device=dev))      # sub-clip frame j of the backward pass is clip frame s_m - j
+    else:
+        run(T - s0, fw, inject, slice(s0 + 1, T))
+        if both and s0 > 0:
+            run(s0 + 1, bw, {}, torch.arange(s0 - 1, -1, -1, device=dev))
     ref = seg_maps[s0][lh:hp - uh, lw:wp - uw].float()[None, None]
     masks[s0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
     if not confidence:

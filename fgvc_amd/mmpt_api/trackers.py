@@ -85,7 +85,8 @@ class BaseTracker(BaseModel):
 class LabelSession:
     """A clip encoded once, index maps propagated any number of times (model.open_label_session).  The affinity lists depend on the
     features only, so the session keeps one engine.LabelSweep per (first annotated frame, time direction): a second propagate with the
-    same first frame launches no encoder, no pair kernel and no merge -- only the sweep and the read-out.
+    same first frame launches no encoder, no pair kernel and no merge -- only the sweep and the read-out.  With fuse='linear' the
+    backward lists are those of the LAST annotated frame: a further map between the first and the last computes no lists either.
     counters: encodes (1), affinity_runs (propagate calls that had to compute lists), sweeps (propagate calls)."""
 
     def __init__(self, model, imgs, img_meta):
@@ -110,24 +111,33 @@ class LabelSession:
         self.cells = None if self.guide is None else ops.guide_cells(self.guide, self.Hf, self.Wf)
         self._sweeps = {}
         self.counters = dict(encodes=1, affinity_runs=0, sweeps=0)
+        self.last_disagree = None          # (T,) int64 on the host after a propagate with fuse set, else None
 
-    def propagate(self, refs, direction=None, override=None, confidence=False):
-        """refs: {frame index: index map (h, w) | (1, h, w)} at the network size, or one tensor for frame 0.  direction / override default to
-        test_cfg.refs' (else 'forward' / 'new').  Returns what the mask call returns, [masks] with masks (T, h0, w0) float64 on the host or
-        the uint8 device tensor (test_cfg.masks='device'); confidence=True: (masks, conf, stats) in the same form, conf (T, h0, w0) uint8,
-        stats (T, C, 2) int64 (ops.seg_readout_conf)."""
+    def propagate(self, refs, direction=None, override=None, confidence=False, fuse=None):
+        """refs: {frame index: index map (h, w) | (1, h, w)} at the network size, or one tensor for frame 0.  direction / override / fuse
+        default to test_cfg.refs' (else 'forward' / 'new' / None).  Returns what the mask call returns, [masks] with masks (T, h0, w0)
+        float64 on the host or the uint8 device tensor (test_cfg.masks='device'); confidence=True: (masks, conf, stats) in the same form,
+        conf (T, h0, w0) uint8, stats (T, C, 2) int64 (ops.seg_readout_conf).
+        fuse='linear' (with direction='both', override='all'): the frames between two annotated frames blend the forward and the backward
+        sweep (engine.fuse_refs_host); the per-frame counts of cells on which the two disagree stay in self.last_disagree, and the session
+        keeps the lists of (first annotated frame, 'fw') and (last annotated frame, 'bw') only."""
         if self.feats is None:
             raise RuntimeError("LabelSession: propagate after close()")
         base = self.model.refs_cfg or engine.RefsConfig()
         rc = engine.parse_refs(dict(direction=base.direction if direction is None else direction,
-                                    override=base.override if override is None else override))
+                                    override=base.override if override is None else override,
+                                    fuse=base.fuse if fuse is None else fuse))
         maps = engine.check_ref_maps(refs, self.n_frames, self.size)
         segs = {t: torch.nn.functional.pad(m.to(self.device, torch.uint8), self.pad).contiguous() for t, m in maps.items()}
-        stats = []
+        stats, disagree = [], []
         out = engine.propagate_masks_refs(self.feats, self.Hf, self.Wf, segs, self.pad, self.out_shape, self.cfg, rc,
                                           channels=self.model.feat_channels, stats_out=stats, confidence=bool(confidence),
                                           sweeps=self._sweeps, counters=self.counters, guide=self.guide,
-                                          readout=self.model.readout_cfg if self.guide is not None else None, cells=self.cells)
+                                          readout=self.model.readout_cfg if self.guide is not None else None, cells=self.cells,
+                                          disagree_out=disagree)
+        self.last_disagree = None
+        if rc.fuse is not None:            # one annotated frame: nothing was fused, nothing disagrees
+            self.last_disagree = disagree[0].cpu() if disagree else torch.zeros(self.n_frames, dtype=torch.int64)
         self.model._refine_stats = stats or None
         self.model._check_kernels()
         device = self.model.masks_form == "device"
@@ -156,7 +166,7 @@ class VanillaTracker(BaseTracker):
         self.chain_cfg = engine.parse_chain(self.test_cfg.get("chain", None))      # test_cfg.chain (None: the points call propagates labels, as ever)
         self.last_flow = None              # forward_test_flow's dict of the last points call with test_cfg.chain set, else None
         self.refs_cfg = engine.parse_refs(self.test_cfg.get("refs", None))         # test_cfg.refs (None: ref_seg_map is one tensor for frame 0)
-        self.last_confidence = None        # dict(conf, stats, frame_score) of the last mask call with test_cfg.refs.confidence=True, else None
+        self.last_confidence = None        # dict(conf, stats, frame_score[, disagree with refs.fuse]) of the last mask call with test_cfg.refs.confidence=True, else None
         self.pose_cfg = engine.parse_pose(self.test_cfg.get("pose", None))         # test_cfg.pose (None: the coords=True call returns coordinates only)
         self.last_pose = None              # dict(peak, field) of the last coords=True call with test_cfg.pose set, else None
         self.readout_cfg = engine.parse_readout(self.test_cfg.get("readout", None))   # test_cfg.readout (None / type='bilinear': the plain read-out)
@@ -650,7 +660,8 @@ class VanillaTracker(BaseTracker):
 
     def _forward_test_refs(self, imgs, ref_seg_map, img_meta):
         """The index-map call with test_cfg.refs set: one LabelSession, one propagate.  Returns [masks] as the call without the key does;
-        with refs.confidence=True the confidence bytes, statistics and frame scores stay in self.last_confidence."""
+        with refs.confidence=True the confidence bytes, statistics and frame scores stay in self.last_confidence, with refs.fuse set the
+        session's disagreement counts too ('disagree')."""
         rc = self.refs_cfg
         self.last_confidence = None
         session = LabelSession(self, imgs, img_meta)
@@ -662,6 +673,8 @@ class VanillaTracker(BaseTracker):
             return out
         masks, conf, stats = out
         self.last_confidence = dict(conf=conf, stats=stats, frame_score=engine.frame_scores(torch.as_tensor(stats), session.out_shape))
+        if rc.fuse is not None:
+            self.last_confidence["disagree"] = session.last_disagree
         return [masks]
 
     def _forward_test_heatmap(self, imgs, heat, img_meta, return_maps=False):

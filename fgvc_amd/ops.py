@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
+import struct
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -1500,6 +1501,83 @@ def seg_readout_guided(labels: torch.Tensor, guide: torch.Tensor, Hf: int, Wf: i
     stats = torch.empty((n, C, 2), device=dev, dtype=torch.int64)
     _lib.call("fgvc_seg_readout_guided_conf_u8", *head, _ptr(outs[0]), _ptr(outs[1]), _ptr(stats), _ptr(ws), _stream(labels))
     return outs[0], outs[1], stats
+
+
+# ---- forward and backward sweeps fused between annotated frames (test_cfg.refs fuse='linear'; engine.fuse_refs_host is the rule) ----------
+
+def _same_storage(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
+def seg_fuse_rows(fw: torch.Tensor, bw: torch.Tensor, fw_index, bw_index, weights, out: Optional[torch.Tensor] = None, out_index=None,
+                  counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One launch for len(weights) items.  fw (n_fw, HW, C), bw (n_bw, HW, C) f32 stacks of row blocks on one device; fw_index, bw_index,
+    out_index: per item a frame index into fw, bw and out (host integers); weights: per item a host number w, 0 <= w <= 1, rounded to
+    f32.  Item i writes out[out_index[i]] = w fw[fw_index[i]] + (1 - w) bw[bw_index[i]] (fma(w, x, fl(fl(1 - w) y)) in f32) and
+    counts[i] = the number of cells whose forward and backward rows have different arg-maxima over C (the first maximum wins).  The
+    rows are assumed finite: nothing is promised for a row that holds a NaN (include/fgvc_hip.h).
+    out=None: fw itself, in place, with out_index = fw_index; a separate out (n_out, HW, C) must share memory with neither stack, and the
+    out indices must differ from each other.  counts: an (n_items,) int64 device tensor to write into.  Returns (out, counts).
+    Every refusal (TypeError for a dtype, ValueError for the rest) comes before the launch; nothing is copied except the 16-byte item
+    records."""
+    for name, t in (("fw", fw), ("bw", bw)) + ((("out", out),) if out is not None else ()):
+        if not torch.is_tensor(t):
+            raise TypeError(f"seg_fuse_rows: {name}: a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"seg_fuse_rows: {name}: expected torch.float32, got {t.dtype}")
+        if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"seg_fuse_rows: {name}: a stack (n, HW, C), got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"seg_fuse_rows: {name} is not contiguous (the kernel addresses the stacks in place; no copy is made)")
+    HW, C = int(fw.shape[1]), int(fw.shape[2])
+    if not 1 <= C <= 256:
+        raise ValueError(f"seg_fuse_rows: C={C} (1 <= C <= 256)")
+    if tuple(bw.shape[1:]) != (HW, C) or bw.device != fw.device:
+        raise ValueError(f"seg_fuse_rows: bw {tuple(bw.shape)} on {bw.device} against fw's (n, {HW}, {C}) on {fw.device}")
+    in_place = out is None or (out.data_ptr() == fw.data_ptr() and out.shape == fw.shape)
+    if out is None:
+        out, out_index = fw, (fw_index if out_index is None else out_index)
+    elif tuple(out.shape[1:]) != (HW, C) or out.device != fw.device:
+        raise ValueError(f"seg_fuse_rows: out {tuple(out.shape)} on {out.device} against fw's (n, {HW}, {C}) on {fw.device}")
+    if out_index is None:
+        raise ValueError("seg_fuse_rows: out_index is needed with out=")
+    cols = [list(fw_index), list(bw_index), list(out_index), list(weights)]
+    n = len(cols[3])
+    if not 1 <= n <= 65535 or any(len(c) != n for c in cols):
+        raise ValueError(f"seg_fuse_rows: {[len(c) for c in cols]} fw / bw / out indices and weights (1 .. 65535 items, one of each per item)")
+    for name, col, size in (("fw_index", cols[0], fw.shape[0]), ("bw_index", cols[1], bw.shape[0]), ("out_index", cols[2], out.shape[0])):
+        for v in col:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < size:
+                raise ValueError(f"seg_fuse_rows: {name} {v!r} outside the stack's {size} frames")
+    for i, w in enumerate(cols[3]):
+        try:                                                               # any real number: a Python, numpy or 0-d tensor scalar
+            v = None if isinstance(w, (bool, str, bytes)) else float(w)
+        except (TypeError, ValueError):
+            v = None
+        if v is None or not 0.0 <= v <= 1.0:                               # NaN fails the comparison too
+            raise ValueError(f"seg_fuse_rows: weight {w!r} (a number, 0 <= w <= 1)")
+        cols[3][i] = v
+    if len(set(int(v) for v in cols[2])) != n:
+        raise ValueError(f"seg_fuse_rows: out_index {cols[2]} names a block twice")
+    if in_place:
+        if [int(v) for v in cols[2]] != [int(v) for v in cols[0]]:
+            raise ValueError("seg_fuse_rows: out is fw: every item must write the block it reads (out_index == fw_index)")
+    elif _same_storage(out, fw):
+        raise ValueError("seg_fuse_rows: out shares memory with fw without being fw (pass out=None to write in place)")
+    if _same_storage(out, bw):
+        raise ValueError("seg_fuse_rows: out shares memory with bw")
+    if not fw.is_cuda:                                                     # the argument checks above need no device; the launch does
+        raise _lib.FgvcHipError("seg_fuse_rows: the stacks must be on the GPU (fgvc_amd has no CPU path)")
+    if counts is None:
+        counts = torch.empty((n,), device=fw.device, dtype=torch.int64)
+    elif not (torch.is_tensor(counts) and counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.shape == (n,)):
+        raise ValueError(f"seg_fuse_rows: counts: a contiguous ({n},) int64 device tensor")
+    bits = struct.unpack(f"<{n}i", struct.pack(f"<{n}f", *(float(w) for w in cols[3])))
+    items = torch.tensor([[int(a), int(b), int(o), wb] for a, b, o, wb in zip(cols[0], cols[1], cols[2], bits)],
+                         dtype=torch.int32).to(fw.device)
+    _lib.call("fgvc_seg_fuse_rows_f32", _ptr(fw), _ptr(bw), _ptr(out), _ptr(items), n, fw.shape[0], bw.shape[0], out.shape[0], HW, C,
+              _ptr(counts), _stream(fw))
+    return out, counts
 
 
 # ---- soft first-frame labels read out as joint coordinates (JHMDB / BADJA heat maps, vanilla_tracker.py:663-830 with coords=True) ----

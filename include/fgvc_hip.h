@@ -824,6 +824,21 @@ int fgvc_guided_channel_chunk(void);
 int fgvc_guided_tile_rows(void);
 int fgvc_guided_tile_cols(void);
 
+/* Fusing a forward and a backward label sweep between annotated frames (test_cfg.refs fuse='linear'; engine.fuse_refs_host is the rule in
+ * float64).  ONE launch for n_items frames.  fw [n_fw][HW][C], bw [n_bw][HW][C] and out [n_out][HW][C] are f32 stacks of row blocks;
+ * items [n_items][4] int32 on the device holds per item the frame index into fw, into bw and into out, and the bits of an f32 weight w.
+ * Per cell of item i:  a = argmax_C fw[items[i][0]][cell], b = argmax_C bw[items[i][1]][cell] (the first maximum wins);
+ *   out[items[i][2]][cell][c] = fma(w, x, fl((fl(1 - w)) * y)) in f32 (1 - w is rounded once per item);
+ *   counts[i] (int64, cleared on `stream` by this call) = the number of cells with a != b: integer atomics, the same on every run.
+ * out may be fw itself where every item's out index is its fw index (each element is read and written by the same lane); apart from that
+ * the output blocks must overlap neither each other nor a block that any item reads.  An item with an index outside its stack writes
+ * nothing.  The rows are ASSUMED FINITE (the sweeps produce no other): on a row with a NaN the kernel's arg-maximum keeps the first
+ * element it compared, where torch.argmax and the float64 rule take the NaN, so nothing is promised for counts or rows there.
+ * With n_items = 0 nothing is launched.  FGVC_ERR_INVALID_ARG for a null pointer, n_items outside 0 .. 65535, an empty stack,
+ * HW < 1 or C outside 1 .. 256.  No workspace. */
+int fgvc_seg_fuse_rows_f32(const float* fw, const float* bw, float* out, const int32_t* items, int n_items, int n_fw, int n_bw, int n_out,
+                           int HW, int C, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,14 +253,19 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
         if not t.lstrip("-").isdigit() or not 0 <= int(t) < T or int(t) in refs:
             raise ValueError(f"--mask {t} {path}: a frame index 0 .. {T - 1}, each frame once")
         refs[int(t)] = torch.from_numpy(_mask_png(path, H, W, "--mask"))
-    model = build_model(a, dev, input=_input(a, None), masks="device", **edge,
-                        refs=dict(direction="both" if a.both_ways else "forward", override=a.override, confidence=a.confidence))
+    spec = dict(direction="both" if a.both_ways else "forward", override=a.override, confidence=a.confidence)
+    if a.fuse:                     # the frames between two masks blend the forward and the backward sweep; the model
+        spec.update(direction="both", override="all", fuse="linear", confidence=True)   # call keeps the counts beside the confidence
+    model = build_model(a, dev, input=_input(a, None), masks="device", **edge, refs=spec)
+    from fgvc_amd import engine
     with torch.no_grad():
         out = model(test_mode=True, imgs=imgs, ref_seg_map=refs, img_meta=meta)
+    lc = model.last_confidence
+    if a.fuse:
+        print("disagree: " + " ".join(str(v) for v in lc["disagree"].tolist()))
+        print(f"annotate next by disagreement: frame {engine.next_frame_to_annotate_by(lc['disagree'], refs)}")
     if a.confidence:
         from PIL import Image
-        from fgvc_amd import engine
-        lc = model.last_confidence
         os.makedirs(a.out, exist_ok=True)
         for f, c in enumerate(lc["conf"].cpu().numpy()):
             Image.fromarray(c).save(os.path.join(a.out, f"conf_{f:05d}.png"))
@@ -366,6 +371,9 @@ def parse_args(argv=None):
     ap.add_argument("--both-ways", action="store_true", help="with --mask: also label the frames before the first annotated one")
     ap.add_argument("--override", choices=("new", "all"), default="new",
                     help="with --mask: a later mask brings in its new objects only, or replaces the frame's labels (a correction)")
+    ap.add_argument("--fuse", action="store_true",
+                    help="with --mask: blend the forward and the backward sweep between two masks (test_cfg.refs fuse='linear'; implies "
+                         "--both-ways --override all) and print the per-frame disagreement counts")
     ap.add_argument("--confidence", action="store_true",
                     help="with --mask: write conf_%%05d.png (the top-two gap per pixel) and print the frame scores and the frame to annotate next")
     ap.add_argument("--edge-aware", action="store_true",
@@ -410,8 +418,8 @@ def parse_args(argv=None):
         ap.error("--heat: the heat overlay needs maps at the frames' size; --size makes them at another (resizing maps is out of scope)")
     if a.task == "vos" and not (a.first_mask or a.mask):
         ap.error("--task vos needs --first-mask (or --mask T PNG)")
-    if (a.both_ways or a.confidence or a.override != "new") and not a.mask:
-        ap.error("--both-ways, --override and --confidence go with --mask T PNG")
+    if (a.both_ways or a.confidence or a.fuse or a.override != "new") and not a.mask:
+        ap.error("--both-ways, --override, --fuse and --confidence go with --mask T PNG")
     if (a.edge_aware or a.edge_radius != 2 or a.edge_sigma_range != 0.1) and not (a.task == "vos" and a.edge_aware):
         ap.error("--edge-aware goes with --task vos; --edge-radius and --edge-sigma-range go with --edge-aware")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
