@@ -99,6 +99,10 @@ SIGNATURES = {
                                            _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "fgvc_frames_yuv420_to_rgb8": (_i, [_p, _p, _p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f,
                                         _i, _p, _p]),
+    "fgvc_frames_yuvp_to_lab_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                         _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_frames_yuvp_to_rgb8": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                      _f, _f, _f, _f, _f, _f, _f, _i, _p, _p]),
     "fgvc_frames_rgb8_to_yuv420": (_i, [_p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, C.c_int64, C.c_int64, _p, _p,
                                         C.c_int64, C.c_int64, C.c_int64, _f, _f, _f, _f, _f, _f, _f, _i, _p]),
     "fgvc_yuv_out_tile_rows": (_i, []),

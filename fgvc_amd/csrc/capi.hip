@@ -51,6 +51,10 @@ int frames_yuv420_to_lab_launch(const uint8_t*, const uint8_t*, const uint8_t*, 
                                 long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
 int frames_yuv420_to_rgb8_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
                                  long long, const float*, int, uint8_t*, hipStream_t);
+int frames_yuvp_to_lab_launch(const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long, long long, long long,
+                              long long, long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
+int frames_yuvp_to_rgb8_launch(const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long, long long, long long,
+                               long long, long long, const float*, int, uint8_t*, hipStream_t);
 int frames_rgb8_to_yuv420_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, uint8_t*, long long, long long,
                                  uint8_t*, uint8_t*, long long, long long, long long, const float*, int, hipStream_t);
 void yuv_out_tile(int*, int*);
@@ -690,6 +694,58 @@ int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t
   const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
   return frames_yuv420_to_rgb8_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, out,
                                       (hipStream_t)stream);
+}
+
+// what the two fgvc_frames_yuvp_* entries check alike: pointers, the sample format, the subsampling, the siting
+static int yuvp_check(const char* fn, const void* y, const void* u, const void* v, const void* out, int sample_bytes, int depth, int shift,
+                      int sub_x, int sub_y, int siting) {
+  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "%s: null pointer", fn);
+  FGVC_REQUIRE(sample_bytes == 1 || sample_bytes == 2, FGVC_ERR_INVALID_ARG, "%s: sample_bytes=%d (1 or 2)", fn, sample_bytes);
+  FGVC_REQUIRE(depth >= 8 && depth <= 16 && shift >= 0 && depth + shift <= 8 * sample_bytes, FGVC_ERR_INVALID_ARG,
+               "%s: depth=%d, shift=%d (depth 8..16, shift >= 0, depth + shift within the %d bits of a sample)", fn, depth, shift,
+               8 * sample_bytes);
+  FGVC_REQUIRE((sub_x == 1 || sub_x == 2) && (sub_y == 1 || sub_y == 2), FGVC_ERR_INVALID_ARG, "%s: sub_x=%d, sub_y=%d (1 or 2 each)", fn, sub_x,
+               sub_y);
+  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
+               "%s: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", fn, siting);
+  FGVC_REQUIRE(sample_bytes == 1 || ((((uintptr_t)y) | ((uintptr_t)u) | ((uintptr_t)v)) & 1) == 0, FGVC_ERR_INVALID_ARG,
+               "%s: alignment (16-bit planes at even addresses)", fn);
+  return FGVC_OK;
+}
+
+int fgvc_frames_yuvp_to_lab_f32(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
+                                int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
+                                int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
+                                int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out, void* stream) {
+  const int rc = yuvp_check("fgvc_frames_yuvp_to_lab_f32", y, u, v, out, sample_bytes, depth, shift, sub_x, sub_y, siting);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuvp_to_lab_f32: non-positive size (T=%d, %d x %d -> %d x %d)", T, h0, w0, h, w);
+  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuvp_to_lab_f32: negative pad (%d, %d, %d, %d)", pad_left, pad_right, pad_top, pad_bottom);
+  const long long hp = (long long)pad_top + h + pad_bottom, wp = (long long)pad_left + w + pad_right;
+  // the grid of fgvc_frames_yuv420_to_lab_f32
+  FGVC_REQUIRE(T <= 65535 && hp <= 4 * 65535ll && wp < (1ll << 30) && hp * wp < (1ll << 31) && h0 < (1 << 30) && w0 < (1 << 30),
+               FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuvp_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels, "
+               "source sides < 2^30)");
+  const float coef[7] = {y_off, cy, c_off, crv, cgu, cgv, cbu};
+  return frames_yuvp_to_lab_launch(y, u, v, sample_bytes, depth, shift, sub_x, sub_y, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y,
+                                   c_stride_x, coef, siting, h, w, pad_left, pad_right, pad_top, pad_bottom, out, (hipStream_t)stream);
+}
+
+int fgvc_frames_yuvp_to_rgb8(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
+                             int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
+                             int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
+                             uint8_t* out, void* stream) {
+  const int rc = yuvp_check("fgvc_frames_yuvp_to_rgb8", y, u, v, out, sample_bytes, depth, shift, sub_x, sub_y, siting);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuvp_to_rgb8: non-positive size (T=%d, %d x %d)", T, h0, w0);
+  FGVC_REQUIRE(T <= 65535 && h0 <= 4 * 65535ll && w0 < (1 << 30) && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_INVALID_ARG,
+               "fgvc_frames_yuvp_to_rgb8: shape beyond the launch grid (T <= 65535, rows <= 262140, frame < 2^31 pixels)");
+  const float coef[7] = {y_off, cy, c_off, crv, cgu, cgv, cbu};
+  return frames_yuvp_to_rgb8_launch(y, u, v, sample_bytes, depth, shift, sub_x, sub_y, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y,
+                                    c_stride_x, coef, siting, out, (hipStream_t)stream);
 }
 
 int fgvc_yuv_out_tile_rows(void) {

@@ -15,6 +15,7 @@
 //   * the interpolated chroma has quarter steps, so no 256-entry table applies: the sRGB transfer is evaluated per value in both paths.
 // No workspace, no atomics, no LDS, nothing allocates or synchronises.
 #include "input_lab.hpp"
+#include "yuv_taps.hpp"
 
 namespace fgvc {
 
@@ -30,21 +31,7 @@ struct YuvArgs {
   int h0, w0, ch, cw, h, w, left, top, hp, wp;
 };
 
-struct ChromaTap {
-  int i0, i1;
-  float l;                         // weight of i1: a multiple of 1/4
-};
-
-// chroma samples around luma index p of an axis with n chroma samples: s = p / 2 - 0.25 (`back`) or p / 2, clamped to [0, n - 1]; in quarter
-// samples that is the integer 2 p - 1 or 2 p
-__device__ __forceinline__ ChromaTap chroma_tap(int p, int back, int n) {
-  const int q = imax(imin(2 * p - back, 4 * (n - 1)), 0);
-  ChromaTap t;
-  t.i0 = q >> 2;
-  t.i1 = imin(t.i0 + 1, n - 1);
-  t.l = 0.25f * (float)(q & 3);
-  return t;
-}
+// (ChromaTap, chroma_tap: yuv_taps.hpp, shared with input_yuvp.hip)
 
 // (every weight a multiple of 1/4, every sample an integer <= 255: exact whatever the order)
 __device__ __forceinline__ float chroma_at(const uint8_t* r0, const uint8_t* r1, long long o0, long long o1, float lx, float ly) {

@@ -948,3 +948,205 @@ def write_y4m(path, frames, fps=(30, 1), siting: str = "left", range: str = "lim
         for frame in f:
             fh.write(b"FRAME\n")
             fh.write(np.ascontiguousarray(frame).tobytes())
+
+
+# ---- Y'CbCr at 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4: the input contract as torch ops, and Y4M files ---------------------
+def _yuv_subsampling(subsampling):
+    try:
+        sx, sy = (int(s) for s in subsampling)
+    except (TypeError, ValueError):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2") from None
+    if sx not in (1, 2) or sy not in (1, 2):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2")
+    return sx, sy
+
+
+def yuv_samples(p: torch.Tensor, depth: int = 8, shift: int = 0) -> torch.Tensor:
+    """A plane of uint8 / uint16 words -> its samples as f32: (word >> shift) & (2^depth - 1) -- P010 keeps its sample in the high bits
+    (shift 6), a low-aligned format may carry anything above the depth.  (Through int32: torch has no shifts on uint16.)"""
+    if p.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"expected torch.uint8 or torch.uint16, got {p.dtype}")
+    depth, shift = int(depth), int(shift)
+    if not 8 <= depth <= 16 or shift < 0 or depth + shift > 8 * p.element_size():
+        raise ValueError(f"depth={depth}, shift={shift}: depth 8..16 and depth + shift within the {8 * p.element_size()} bits of {p.dtype}")
+    return ((p.to(torch.int32) >> shift) & ((1 << depth) - 1)).to(torch.float32)
+
+
+def yuv_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, subsampling=(2, 2), siting: str = "left") -> torch.Tensor:
+    """One chroma plane (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of sample values -> its value at every luma pixel (T, h0, w0) f32.  A
+    subsampled axis is interpolated as yuv420_chroma_at_luma does (bilinear, edge clamped; vertically between the luma rows, horizontally by
+    `siting`); a full-resolution axis takes the sample at the luma index and no arithmetic touches it.  Exact: sixteenths on integers below
+    2^16 are 20 bits at most."""
+    if siting not in ("left", "center"):
+        raise ValueError(f"siting={siting!r}: 'left' or 'center'")
+    sx, sy = _yuv_subsampling(subsampling)
+    c = c.to(torch.float32)
+
+    def across(r):
+        if sx == 1:
+            return r
+        x0, x1, lx = _chroma_taps(w0, c.shape[2], siting == "center", c.device)
+        return (1 - lx) * r[:, :, x0] + lx * r[:, :, x1]
+    if sy == 1:
+        return across(c)
+    y0, y1, ly = _chroma_taps(h0, c.shape[1], True, c.device)
+    return (1 - ly)[:, None] * across(c[:, y0]) + ly[:, None] * across(c[:, y1])
+
+
+def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+               matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
+    """Planes y (T, h0, w0), u, v (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of uint8 / uint16 words -> R'G'B' (T, 3, h0, w0) f32 on the 0..255
+    scale, neither clamped nor rounded: samples by yuv_samples, chroma at the luma pixel, then yy = cy (Y - y_off), cb = U - c_off,
+    cr = V - c_off, R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with ops.yuv_coefficients_depth rounded to f32 -- one
+    rounded f32 operation after another, the order the kernels keep.  CPU or GPU tensors."""
+    from .ops import yuv_coefficients_depth
+    y_off, cy, c_off, crv, cgu, cgv, cbu = (float(np.float32(c)) for c in yuv_coefficients_depth(matrix, range, depth))
+    sx, sy = _yuv_subsampling(subsampling)
+    T, h0, w0 = y.shape
+    want = (T, (h0 + sy - 1) // sy, (w0 + sx - 1) // sx)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)} subsampled {(sx, sy)}, got {tuple(u.shape)} and "
+                         f"{tuple(v.shape)}")
+    yy = cy * (yuv_samples(y, depth, shift) - y_off)
+    cb = yuv_chroma_at_luma(yuv_samples(u, depth, shift), h0, w0, (sx, sy), siting) - c_off
+    cr = yuv_chroma_at_luma(yuv_samples(v, depth, shift), h0, w0, (sx, sy), siting) - c_off
+    return torch.stack([yy + crv * cr, (yy + cgu * cb) + cgv * cr, yy + cbu * cb], 1)
+
+
+def yuv_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+                matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
+    """-> (T, h0, w0, 3) uint8: yuv_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_planes_to_rgb8 computes)."""
+    rgb = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    return rgb.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def preprocess_yuv_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+                          matrix: str = "bt601", range: str = "limited", siting: str = "left", size=None) -> torch.Tensor:
+    """The same planes -> (1, T, 3, h, w) float32 network input: yuv_to_rgb, then preprocess_yuv420_frames' steps on the unclamped R'G'B'
+    (bilinear resize to `size`, None = the frames' own; / 255 and clamp; RGB -> Lab; (x - [50, 0, 0]) / [50, 127, 127]).  The contract
+    ops.yuv_planes_to_lab is held to."""
+    x = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    if size is not None and tuple(x.shape[-2:]) != tuple(size):
+        x = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
+    lab = rgb_to_lab((x / 255.0).clamp(0, 1))
+    mean = torch.tensor([50.0, 0.0, 0.0], device=lab.device).view(1, 3, 1, 1)
+    std = torch.tensor([50.0, 127.0, 127.0], device=lab.device).view(1, 3, 1, 1)
+    return ((lab - mean) / std).unsqueeze(0)
+
+
+# a Y4M chroma tag -> (format: a ops.YUV_PIXEL_FORMATS name or 'i420', siting)
+_Y4M_PLANES = {"420jpeg": ("i420", "center"), "420mpeg2": ("i420", "left"), "420": ("i420", "left"),
+               "422": ("yuv422p", "left"), "444": ("yuv444p", "left"),
+               "420p10": ("yuv420p10", "left"), "420p12": ("yuv420p12", "left"),
+               "422p10": ("yuv422p10", "left"), "422p12": ("yuv422p12", "left"),
+               "444p10": ("yuv444p10", "left"), "444p12": ("yuv444p12", "left")}
+_Y4M_TAGS = {"yuv422p": "422", "yuv444p": "444", "yuv420p10": "420p10", "yuv420p12": "420p12", "yuv422p10": "422p10",
+             "yuv422p12": "422p12", "yuv444p10": "444p10", "yuv444p12": "444p12"}
+
+
+def _y4m_format(fmt: str):
+    """-> (sub_x, sub_y, depth, numpy dtype of a stored sample) of 'i420' or a planar ops.YUV_PIXEL_FORMATS name."""
+    from .ops import YUV_PIXEL_FORMATS
+    if fmt == "i420":
+        return 2, 2, 8, np.dtype(np.uint8)
+    _, sx, sy, depth, _, dtype = YUV_PIXEL_FORMATS[fmt]
+    return sx, sy, depth, np.dtype("<u2") if dtype == torch.uint16 else np.dtype(np.uint8)
+
+
+def read_y4m_header(path) -> str:
+    """The chroma tag of a YUV4MPEG2 file's header ('420jpeg' where it has none).  ValueError for another file."""
+    with open(path, "rb") as fh:
+        head = fh.readline(4096)
+    tags = head.rstrip(b"\n").split(b" ")
+    if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
+        raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
+    chroma = "420jpeg"
+    for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
+        if tag[0] == "C":
+            chroma = tag[1:]
+    return chroma
+
+
+def read_y4m_planes(path, max_frames=None):
+    """A YUV4MPEG2 file of progressive frames, 8 to 12 bits, 4:2:0 / 4:2:2 / 4:4:4 -> (frames (T, rows, w) in the file's own arrangement --
+    the luma rows, then the u plane and the v plane: what ops.yuv_planes takes apart (ops.yuv420_planes for 'i420') -- uint8, or uint16
+    from the file's little-endian words; info = read_y4m's keys plus format (an ops.YUV_PIXEL_FORMATS name, or 'i420') and depth).
+    C420jpeg, C420mpeg2, C420 and no C tag as read_y4m reads them; C422, C444; C420p10, C420p12, C422p10, C422p12, C444p10, C444p12, siting
+    'left'.  ValueError that names the tag or the fact for any other chroma tag (Cmono*, C411, C444alpha, C420paldv, ..), interlaced
+    material, a side that is odd on a subsampled axis and a truncated frame.  `max_frames`: stop after that many."""
+    with open(path, "rb") as fh:
+        head = fh.readline(4096)
+        tags = head.rstrip(b"\n").split(b" ")
+        if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
+            raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
+        w = h = None
+        fps, chroma, rng = (0, 0), "420jpeg", "limited"
+        for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
+            k, val = tag[0], tag[1:]
+            if k == "W":
+                w = int(val)
+            elif k == "H":
+                h = int(val)
+            elif k == "F":
+                num, _, den = val.partition(":")
+                fps = (int(num), int(den or 1))
+            elif k == "I" and val not in ("p", "?"):
+                raise ValueError(f"{path}: interlaced material (I{val}) is not supported; deinterlace it first")
+            elif k == "C":
+                chroma = val
+            elif k == "X" and val.upper().startswith("COLORRANGE="):
+                rng = val[11:].lower()
+                if rng not in ("full", "limited"):
+                    raise ValueError(f"{path}: XCOLORRANGE={val[11:]} (FULL or LIMITED)")
+        if chroma not in _Y4M_PLANES:
+            raise ValueError(f"{path}: chroma tag C{chroma} is not supported (planar 4:2:0, 4:2:2 and 4:4:4 at 8, 10 or 12 bits: "
+                             f"{', '.join('C' + t for t in _Y4M_PLANES)})")
+        fmt, siting = _Y4M_PLANES[chroma]
+        sx, sy, depth, dt = _y4m_format(fmt)
+        if w is None or h is None or w < 1 or h < 1:
+            raise ValueError(f"{path}: the header gives no frame size (W, H)")
+        if w % sx or h % sy:
+            raise ValueError(f"{path}: odd size {w} x {h}; a C{chroma} frame with an odd side on a subsampled axis has no packed form")
+        rows = h + 2 * h // (sx * sy)
+        n = rows * w * dt.itemsize
+        frames = []
+        while max_frames is None or len(frames) < max_frames:
+            line = fh.readline(4096)
+            if not line:
+                break
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise ValueError(f"{path}: frame {len(frames)}: expected a FRAME header")
+            data = fh.read(n)
+            if len(data) != n:
+                raise ValueError(f"{path}: frame {len(frames)} is truncated ({len(data)} of {n} bytes)")
+            frames.append(np.frombuffer(data, dt))
+    native = np.dtype(dt.type)                                                # (the words in host order)
+    arr = np.stack(frames).reshape(len(frames), rows, w).astype(native) if frames else np.zeros((0, rows, w), native)
+    return torch.from_numpy(arr.copy()), dict(width=w, height=h, fps=fps, siting=siting, range=rng, format=fmt, depth=depth)
+
+
+def write_y4m_planes(path, frames, format: str = "i420", fps=(30, 1), siting: str = "left", range: str = "limited") -> None:
+    """read_y4m_planes' inverse: frames (T, rows, w) of 'i420' or a planar ops.YUV_PIXEL_FORMATS name, in its dtype (tensor or array), ->
+    a YUV4MPEG2 file: progressive, square pixels, 16-bit samples as little-endian words, XCOLORRANGE=LIMITED | FULL.  'i420' writes
+    C420mpeg2 ('left') or C420jpeg ('center'); the other tags have no siting, and a file of them reads back as 'left'.  ValueError for a
+    semi-planar format (Y4M has none) and a shape that is no packed frame; TypeError for another dtype."""
+    if format != "i420" and format not in _Y4M_TAGS:
+        raise ValueError(f"write_y4m_planes: format={format!r} (Y4M holds planar frames: one of {('i420',) + tuple(_Y4M_TAGS)})")
+    if siting not in ("left", "center") or range not in ("limited", "full"):
+        raise ValueError(f"write_y4m_planes: siting={siting!r} ('left' | 'center'), range={range!r} ('limited' | 'full')")
+    sx, sy, _, dt = _y4m_format(format)
+    f = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if f.dtype != np.dtype(dt.type):
+        raise TypeError(f"write_y4m_planes: expected {np.dtype(dt.type)} frames for {format}, got {f.dtype}")
+    k = sx * sy
+    if f.ndim != 3 or f.shape[1] == 0 or f.shape[2] == 0 or f.shape[1] * k % (k + 2):
+        raise ValueError(f"write_y4m_planes: packed {format} frames (T, h (1 + 2 / {k}), w), got {f.shape}")
+    h, w = f.shape[1] * k // (k + 2), f.shape[2]
+    if h % sy or w % sx:
+        raise ValueError(f"write_y4m_planes: odd size {h} x {w} on a subsampled axis of {format}")
+    chroma = ("420mpeg2" if siting == "left" else "420jpeg") if format == "i420" else _Y4M_TAGS[format]
+    with open(path, "wb") as fh:
+        fh.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{chroma} XCOLORRANGE={range.upper()}\n".encode("ascii"))
+        for frame in f:
+            fh.write(b"FRAME\n")
+            fh.write(np.ascontiguousarray(frame, dt).tobytes())

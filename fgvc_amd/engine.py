@@ -1315,7 +1315,9 @@ class InputConfig:
     """test_cfg.input, parsed (an extension key, DESIGN.md sections 14 and 19): the trackers then take uint8 frames wherever they take float
     ones.  dict(type='rgb8', size=(h, w) | None, layout='thwc' | 'tchw'): RGB bytes, converted with ops.frames_to_lab.
     dict(type='nv12' | 'i420', size=, matrix='bt601' | 'bt709', range='limited' | 'full', siting='left' | 'center'): packed 8-bit YUV 4:2:0
-    frames (T, 3 h0 / 2, w0), converted with ops.yuv_frames_to_lab.  `size`: the network size the frames are resized to (None: their own);
+    frames (T, 3 h0 / 2, w0), converted with ops.yuv_frames_to_lab.  dict(type=<an ops.YUV_PIXEL_FORMATS name>, size=, matrix=, range=,
+    siting=): packed frames of that format in its dtype (uint16 for 10 to 16 bits), (T, 3 h0 / 2 | 2 h0 | 3 h0, w0), converted with
+    ops.yuv_planes_to_lab (DESIGN.md section 26); `matrix` has no default there and `siting` is refused with a 4:4:4 type.  `size`: the network size the frames are resized to (None: their own);
     `layout`: where an RGB frame tensor keeps its channels."""
     size: Optional[Tuple[int, int]] = None
     layout: str = "thwc"
@@ -1329,12 +1331,18 @@ class InputConfig:
         return self.type != "rgb8"
 
 
-INPUT_TYPES = ("rgb8",) + ops.YUV_FORMATS
+INPUT_TYPES = ("rgb8",) + ops.YUV_FORMATS + tuple(ops.YUV_PIXEL_FORMATS)
+
+
+def input_dtype(typ: str) -> torch.dtype:
+    """The dtype of the raw frames a test_cfg.input type names: uint8, or uint16 for the 10- to 16-bit formats."""
+    return ops.YUV_PIXEL_FORMATS[typ][5] if typ in ops.YUV_PIXEL_FORMATS else torch.uint8
 
 
 def parse_input(spec) -> Optional[InputConfig]:
-    """None -> None (the option is off: float frames only).  A mapping with type='rgb8' | 'nv12' | 'i420' -> InputConfig; any other `type`
-    (or none), a key its type does not have (`layout` with a YUV type; `matrix`, `range`, `siting` with 'rgb8'), an unknown value, or a size
+    """None -> None (the option is off: float frames only).  A mapping with type='rgb8' | 'nv12' | 'i420' | an ops.YUV_PIXEL_FORMATS
+    name -> InputConfig; any other `type` (or none), a key its type does not have (`layout` with a YUV type; `matrix`, `range`, `siting` with
+    'rgb8'; `siting` with a 4:4:4 type), an ops.YUV_PIXEL_FORMATS type without its `matrix`, an unknown value, or a size
     that is not two positive integers raises ValueError, a non-mapping TypeError."""
     if spec is None:
         return None
@@ -1343,7 +1351,8 @@ def parse_input(spec) -> Optional[InputConfig]:
     spec = dict(spec)
     typ = spec.pop("type", None)
     if typ not in INPUT_TYPES:
-        raise ValueError(f"test_cfg.input: type={typ!r} (one of {INPUT_TYPES}: uint8 RGB frames, packed 8-bit YUV 4:2:0 frames)")
+        raise ValueError(f"test_cfg.input: type={typ!r} (one of {INPUT_TYPES}: uint8 RGB frames, packed 8-bit YUV 4:2:0 frames, packed "
+                         "4:2:0 / 4:2:2 / 4:4:4 frames at 8 to 16 bits)")
     size = spec.pop("size", None)
     if typ == "rgb8":
         layout = spec.pop("layout", "thwc")
@@ -1353,11 +1362,21 @@ def parse_input(spec) -> Optional[InputConfig]:
             raise ValueError(f"test_cfg.input: layout={layout!r} (one of {ops.INPUT_LAYOUTS})")
         ic = InputConfig(None, layout)
     else:
-        matrix, rng, siting = spec.pop("matrix", "bt601"), spec.pop("range", "limited"), spec.pop("siting", "left")
+        if "siting" in spec and typ in ops.YUV_PIXEL_FORMATS and ops.YUV_PIXEL_FORMATS[typ][1] == 1:
+            raise ValueError(f"test_cfg.input: siting= has no meaning for type={typ!r} (4:4:4: every pixel has its own chroma sample); remove it")
+        # 'nv12' / 'i420' default to bt601 as they always did; the newer types have no default matrix -- 10-bit, 4:2:2 and 4:4:4 material is
+        # HD, UHD or camera footage, for which a silent bt601 is wrong more often than right -- so the type alone (dict(type='p010')) stays
+        # the ValueError it was before these types existed
+        matrix = spec.pop("matrix", None if typ in ops.YUV_PIXEL_FORMATS else "bt601")
+        rng, siting = spec.pop("range", "limited"), spec.pop("siting", "left")
         if "layout" in spec:
-            raise ValueError(f"test_cfg.input: layout= belongs to type='rgb8'; {typ!r} frames are packed (T, 3 h0 / 2, w0)")
+            shape = ops._packed_shape(typ) if typ in ops.YUV_PIXEL_FORMATS else "(T, 3 h0 / 2, w0)"
+            raise ValueError(f"test_cfg.input: layout= belongs to type='rgb8'; {typ!r} frames are packed {shape}")
         if spec:
             raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, matrix, range, siting)")
+        if matrix is None:
+            raise ValueError(f"test_cfg.input: type={typ!r} needs matrix= (one of {tuple(ops.YUV_MATRICES)}): the stream's own, there is no "
+                             "default for this type")
         if matrix not in ops.YUV_MATRICES:
             raise ValueError(f"test_cfg.input: matrix={matrix!r} (one of {tuple(ops.YUV_MATRICES)})")
         if rng not in ops.YUV_RANGES:

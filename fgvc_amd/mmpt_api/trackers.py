@@ -82,6 +82,17 @@ class BaseTracker(BaseModel):
         return x
 
 
+_RAW_DTYPES = (torch.uint8, torch.uint16)      # what test_cfg.input converts: bytes, and the 16-bit words of a 10- to 16-bit YUV type
+
+
+def _packed_desc(ic, lead: str) -> str:
+    """'uint8 nv12 frames of shape (1, T, 3 h0 / 2, w0)' and its kin, for the refusals of a misshapen packed clip."""
+    if ic.type in ops.YUV_PIXEL_FORMATS:
+        dt = str(ops.YUV_PIXEL_FORMATS[ic.type][5]).replace("torch.", "")
+        return f"{dt} {ic.type} frames of shape ({lead}{ops._packed_shape(ic.type)[1:]}"
+    return f"uint8 {ic.type} frames of shape ({lead}T, 3 h0 / 2, w0)"
+
+
 class LabelSession:
     """A clip encoded once, index maps propagated any number of times (model.open_label_session).  The affinity lists depend on the
     features only, so the session keeps one engine.LabelSweep per (first annotated frame, time direction): a second propagate with the
@@ -384,14 +395,14 @@ class VanillaTracker(BaseTracker):
         if cc.visibility == "consistency" and fc.occlusion is None:
             fc.occlusion = "consistency"
         # packed YUV frames are (1, T, 3 h0 / 2, w0); without the key, uint8 frames of either form go on to the flow call's TypeError
-        packed = rgbs.dtype == torch.uint8 and (self.input_cfg is None or self.input_cfg.yuv) and rgbs.dim() == 4
+        packed = rgbs.dtype in _RAW_DTYPES and (self.input_cfg is None or self.input_cfg.yuv) and rgbs.dim() == 4
         if (not packed and rgbs.dim() != 5) or rgbs.shape[0] != 1:
             raise ValueError(f"rgbs: frames of shape (1, T, 3, h, w), or uint8 ones as test_cfg.input lays them out, got {tuple(rgbs.shape)}")
         if query_points.dim() != 3 or query_points.shape[0] != 1 or query_points.shape[2] != 3:
             raise ValueError(f"query_points: (1, P, 3) = (t, x, y), got {tuple(query_points.shape)}")
         engine.check_query_times(query_points[0, :, 0], rgbs.shape[1])
         # the flow call's layout: float (1, 1, 3, T, h, w) -- a view --, uint8 (1, 1, T, ...)
-        imgs = rgbs.unsqueeze(1) if rgbs.dtype == torch.uint8 else rgbs.transpose(1, 2).unsqueeze(1)
+        imgs = rgbs.unsqueeze(1) if rgbs.dtype in _RAW_DTYPES else rgbs.transpose(1, 2).unsqueeze(1)
         self.last_flow = flow = self.forward_test_flow(imgs, fc=fc)
         ok_fw, ok_bw = engine.chain_masks(flow) if cc.visibility == "consistency" else (None, None)
         traj, vis = engine.chain_points(flow["flow_fw"], flow["flow_bw"], query_points[0], ok_fw, ok_bw, cc.visibility)
@@ -421,14 +432,19 @@ class VanillaTracker(BaseTracker):
 
     # ---- raw frames: test_cfg.input (an extension key) -------------------------------------------------------------
     def _raw_input(self, frames: torch.Tensor, name: str) -> Optional[engine.InputConfig]:
-        """None for float frames (they run as ever, with or without the key); self.input_cfg for uint8 ones, TypeError without the key."""
-        if frames is None or frames.dtype != torch.uint8:
+        """None for float frames (they run as ever, with or without the key); self.input_cfg for uint8 ones (uint16 ones where its type's
+        samples are 16-bit words), TypeError without the key or for frames of another dtype than the type's."""
+        if frames is None or frames.dtype not in _RAW_DTYPES:
             return None
         ic = self.input_cfg
+        dt = str(frames.dtype).replace("torch.", "")
         if ic is None:
-            raise TypeError(f"{type(self).__name__}: {name} is uint8, and float frames are expected (Lab-normalised network input); raw RGB "
+            raise TypeError(f"{type(self).__name__}: {name} is {dt}, and float frames are expected (Lab-normalised network input); raw RGB "
                             "frames are taken with the extension key test_cfg.input = dict(type='rgb8', size=(h, w) | None, "
                             "layout='thwc' | 'tchw')")
+        if frames.dtype != engine.input_dtype(ic.type):
+            raise TypeError(f"{type(self).__name__}: {name} is {dt}, and test_cfg.input type={ic.type!r} takes "
+                            f"{str(engine.input_dtype(ic.type)).replace('torch.', '')} frames")
         if not frames.is_cuda:
             raise RuntimeError(f"fgvc_amd.{type(self).__name__} runs on the GPU only (no CPU fallback)")
         return ic
@@ -440,21 +456,35 @@ class VanillaTracker(BaseTracker):
             return rgbs
         if ic.yuv:
             if rgbs.dim() != 4 or rgbs.shape[0] != 1:
-                raise ValueError(f"rgbs: uint8 {ic.type} frames of shape (1, T, 3 h0 / 2, w0), got {tuple(rgbs.shape)}")
+                raise ValueError(f"rgbs: {_packed_desc(ic, '1, ')}, got {tuple(rgbs.shape)}")
             return self._yuv_to_lab(ic, rgbs[0], "rgbs", ic.size).unsqueeze(0)
         if rgbs.dim() != 5 or rgbs.shape[0] != 1:
             raise ValueError(f"rgbs: uint8 frames of shape (1, T, h0, w0, 3) ('thwc') or (1, T, 3, h0, w0) ('tchw'), got {tuple(rgbs.shape)}")
         return ops.frames_to_lab(rgbs[0], ic.size, layout=ic.layout).unsqueeze(0)
 
-    def _yuv_to_lab(self, ic, packed: torch.Tensor, name: str, size, pad=(0, 0, 0, 0)) -> torch.Tensor:
-        """Packed NV12 / I420 frames (T, 3 h0 / 2, w0) of test_cfg.input's type -> ops.yuv_frames_to_lab of their planes (T, 3, hp, wp)."""
+    def _yuv_planes(self, ic, packed: torch.Tensor, name: str):
+        """Packed frames of test_cfg.input's type -> their plane views (y, u, v): NV12 / I420 (T, 3 h0 / 2, w0), an ops.YUV_PIXEL_FORMATS
+        type (T, 3 h0 / 2 | 2 h0 | 3 h0, w0).  A shape that is no packed frame is a ValueError that states the expected one."""
+        lead = "1, " if name == "rgbs" else "1, 1, "
         try:
-            y, u, v = ops.yuv420_planes(packed, ic.type)
+            return ops.yuv_planes(packed, ic.type) if ic.type in ops.YUV_PIXEL_FORMATS else ops.yuv420_planes(packed, ic.type)
         except ValueError as e:
-            lead = "1, " if name == "rgbs" else "1, 1, "
+            if ic.type in ops.YUV_PIXEL_FORMATS:
+                raise ValueError(f"{name}: {_packed_desc(ic, lead)}, got the frames {tuple(packed.shape)} ({e})") from None
             raise ValueError(f"{name}: uint8 {ic.type} frames of shape ({lead}T, 3 h0 / 2, w0) with h0 and w0 even, got the frames "
                              f"{tuple(packed.shape)} ({e})") from None
-        return ops.yuv_frames_to_lab(y, u, v, size, pad, ic.matrix, ic.range, ic.siting)
+
+    def _planes_to_lab(self, ic, planes, size, pad=(0, 0, 0, 0)) -> torch.Tensor:
+        """_yuv_planes' views -> (T, 3, hp, wp): ops.yuv_frames_to_lab for NV12 / I420, ops.yuv_planes_to_lab with the format's depth, shift
+        and subsampling for an ops.YUV_PIXEL_FORMATS type."""
+        fmt = ops.YUV_PIXEL_FORMATS.get(ic.type)
+        if fmt is None:
+            return ops.yuv_frames_to_lab(*planes, size, pad, ic.matrix, ic.range, ic.siting)
+        return ops.yuv_planes_to_lab(*planes, fmt[3], fmt[4], (fmt[1], fmt[2]), size, pad, ic.matrix, ic.range, ic.siting)
+
+    def _yuv_to_lab(self, ic, packed: torch.Tensor, name: str, size) -> torch.Tensor:
+        """Packed frames of test_cfg.input's type -> the unpadded float frames (T, 3, h, w); size=None: the frames' own."""
+        return self._planes_to_lab(ic, self._yuv_planes(ic, packed, name), size)
 
     def _label_frames(self, imgs: torch.Tensor):
         """The label-map call's imgs -> the frames padded to a multiple of _pad_unit() (T, 3, hp, wp), the network size (h, w), the pad.
@@ -467,11 +497,11 @@ class VanillaTracker(BaseTracker):
             return torch.nn.functional.pad(imgs[0, 0], pad).transpose(0, 1), (h, w), pad
         if ic.yuv:
             if imgs.dim() != 5 or imgs.shape[0] != 1 or imgs.shape[1] != 1:
-                raise ValueError(f"imgs: uint8 {ic.type} frames of shape (1, 1, T, 3 h0 / 2, w0), got {tuple(imgs.shape)}")
-            v = imgs[0, 0]
-            h, w = ic.size if ic.size is not None else (v.shape[1] // 3 * 2, v.shape[2])
+                raise ValueError(f"imgs: {_packed_desc(ic, '1, 1, ')}, got {tuple(imgs.shape)}")
+            planes = self._yuv_planes(ic, imgs[0, 0], "imgs")
+            h, w = ic.size if ic.size is not None else tuple(planes[0].shape[1:])      # (the luma plane: the height by the format's rows)
             _, pad = engine.pad_divide_by(h, w, self._pad_unit())
-            return self._yuv_to_lab(ic, v, "imgs", (h, w), pad), (h, w), pad
+            return self._planes_to_lab(ic, planes, (h, w), pad), (h, w), pad
         if imgs.dim() != 6:
             raise ValueError(f"imgs: uint8 frames of shape (1, 1, T, h0, w0, 3) ('thwc') or (1, 1, T, 3, h0, w0) ('tchw'), got {tuple(imgs.shape)}")
         v = imgs[0, 0]
@@ -901,7 +931,7 @@ class HRVanillaTracker(VanillaTracker):
         ic = self._raw_input(imgs, "imgs")
         if ic is not None and ic.yuv:                                                  # uint8 (1, 1, T, 3 h0 / 2, w0): packed NV12 / I420
             if imgs.dim() != 5 or imgs.shape[0] != 1 or imgs.shape[1] != 1:
-                raise ValueError(f"imgs: uint8 {ic.type} frames of shape (1, 1, T, 3 h0 / 2, w0), got {tuple(imgs.shape)}")
+                raise ValueError(f"imgs: {_packed_desc(ic, '1, 1, ')}, got {tuple(imgs.shape)}")
             frames = self._yuv_to_lab(ic, imgs[0, 0], "imgs", ic.size)                 # (T, 3, h, w)
         elif ic is not None:                                                           # uint8 (B, 1, T, h0, w0, 3) | (B, 1, T, 3, h0, w0): test_cfg.input
             assert imgs.dim() == 6 and imgs.shape[0] * imgs.shape[1] == 1, "batch size must be 1 (get_feats, vanilla_tracker.py:134)"

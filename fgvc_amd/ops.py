@@ -1818,6 +1818,176 @@ def yuv_frames_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix
     return out
 
 
+# ---- the input stage for planar and semi-planar Y'CbCr at 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4 -------------------------
+
+# ffmpeg's name -> (layout 'planar' | 'semi', sub_x, sub_y, depth, shift, dtype); 16-bit samples are host-endian (little-endian) words.
+# 'nv12' and 'i420' stay in YUV_FORMATS and go through the 8-bit 4:2:0 entries.
+YUV_PIXEL_FORMATS = {
+    "p010": ("semi", 2, 2, 10, 6, torch.uint16), "p012": ("semi", 2, 2, 12, 4, torch.uint16), "p016": ("semi", 2, 2, 16, 0, torch.uint16),
+    "yuv420p10": ("planar", 2, 2, 10, 0, torch.uint16), "yuv420p12": ("planar", 2, 2, 12, 0, torch.uint16),
+    "yuv422p10": ("planar", 2, 1, 10, 0, torch.uint16), "yuv422p12": ("planar", 2, 1, 12, 0, torch.uint16),
+    "yuv444p10": ("planar", 1, 1, 10, 0, torch.uint16), "yuv444p12": ("planar", 1, 1, 12, 0, torch.uint16),
+    "yuv422p": ("planar", 2, 1, 8, 0, torch.uint8), "yuv444p": ("planar", 1, 1, 8, 0, torch.uint8),
+    "nv16": ("semi", 2, 1, 8, 0, torch.uint8),
+}
+_YUV_DTYPES = (torch.uint8, torch.uint16)
+
+
+def yuv_coefficients_depth(matrix: str = "bt601", range: str = "limited",
+                           depth: int = 8) -> Tuple[float, float, float, float, float, float, float]:
+    """(y_off, cy, c_off, crv, cgu, cgv, cbu) for samples of `depth` bits (8..16), R'G'B' on the 0..255 scale: with s = 2^(depth - 8),
+    'limited' y_off = 16 s, cy = 255 / (219 s), c_off = 128 s, chroma scale 255 / (224 s); 'full' y_off = 0, cy = 255 / (2^depth - 1),
+    c_off = 2^(depth - 1), chroma scale 255 / (2^depth - 1).  Computed in float64 as Python floats; the kernels take them rounded to f32 once.
+    At depth 8 they are yuv_coefficients' numbers around c_off = 128; the limited-range ones at any depth differ from those by powers of two."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix={matrix!r}: one of {tuple(YUV_MATRICES)}")
+    if range not in YUV_RANGES:
+        raise ValueError(f"range={range!r}: one of {tuple(YUV_RANGES)}")
+    depth = int(depth)
+    if not 8 <= depth <= 16:
+        raise ValueError(f"depth={depth}: 8..16")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    s = float(1 << (depth - 8))
+    if range == "limited":
+        y_off, cy, c_off, sc = 16.0 * s, 255.0 / (219.0 * s), 128.0 * s, 255.0 / (224.0 * s)
+    else:
+        top = float((1 << depth) - 1)
+        y_off, cy, c_off, sc = 0.0, 255.0 / top, float(1 << (depth - 1)), 255.0 / top
+    return (y_off, cy, c_off, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
+
+
+def yuv_packed_rows(fmt: str, h0: int) -> int:
+    """Rows of a packed `fmt` frame of h0 luma rows: h0 (1 + 2 / (sub_x sub_y))."""
+    _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
+    return h0 + 2 * h0 // (sx * sy)
+
+
+def yuv_packed_height(fmt: str, rows: int) -> int:
+    """The luma rows h0 of a packed `fmt` frame of `rows` rows (3 h0 / 2, 2 h0 or 3 h0 rows), or -1 where no whole h0 gives them."""
+    _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
+    k = sx * sy
+    return rows * k // (k + 2) if rows * k % (k + 2) == 0 else -1
+
+
+def _packed_shape(fmt: str) -> str:
+    _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
+    return {4: "(T, 3 h0 / 2, w0)", 2: "(T, 2 h0, w0)", 1: "(T, 3 h0, w0)"}[sx * sy]
+
+
+def yuv_planes(frames: torch.Tensor, fmt: str):
+    """Packed frames (T, rows, w0) of a YUV_PIXEL_FORMATS name, in its dtype -- h0 luma rows, then the chroma as the file's samples follow:
+    a planar format's u plane and v plane, a semi-planar one's rows of interleaved (u, v) pairs; rows = h0 (1 + 2 / (sub_x sub_y)) -- -> the
+    views (y (T, h0, w0), u, v (T, h0 / sub_y, w0 / sub_x)); nothing is copied.  TypeError for another dtype; ValueError unless the rows are
+    whole, the sides even on every subsampled axis and (for subsampled planar chroma) a frame's samples adjacent."""
+    if fmt not in YUV_PIXEL_FORMATS:
+        raise ValueError(f"fmt={fmt!r}: one of {tuple(YUV_PIXEL_FORMATS)}")
+    layout, sx, sy, _, _, dtype = YUV_PIXEL_FORMATS[fmt]
+    if frames.dtype != dtype:
+        raise TypeError(f"frames: expected {dtype} for {fmt}, got {frames.dtype}")
+    shape = _packed_shape(fmt)
+    if frames.dim() != 3:
+        raise ValueError(f"frames: packed {fmt} frames of shape {shape}, got {tuple(frames.shape)}")
+    T, rows, w0 = frames.shape
+    h0 = yuv_packed_height(fmt, rows)
+    if h0 <= 0 or w0 == 0 or h0 % sy or w0 % sx:
+        even = {(2, 2): " with h0 and w0 even", (2, 1): " with w0 even", (1, 1): ""}[(sx, sy)]
+        raise ValueError(f"frames: packed {fmt} frames of shape {shape}{even}, got {tuple(frames.shape)}")
+    ch, cw = h0 // sy, w0 // sx
+    y, c = frames[:, :h0], frames[:, h0:]
+    if layout == "semi":                                                              # ch rows of cw (u, v) pairs
+        uv = c.unflatten(2, (cw, 2))
+        return y, uv[..., 0], uv[..., 1]
+    if sx == 1:                                                                       # a plane's rows are packed rows
+        return y, c[:, :ch], c[:, ch:]
+    if T > 0 and (c.stride(1), c.stride(2)) != (w0, 1):                               # (a row of the u plane is half a packed row)
+        raise ValueError(f"frames: the samples of a packed {fmt} frame must be adjacent (strides (.., {w0}, 1)), got {frames.stride()}; "
+                         "pass the planes of a crop instead")
+    pl = c.as_strided((T, 2, ch, cw), (c.stride(0), ch * cw, cw, 1), c.storage_offset())
+    return y, pl[:, 0], pl[:, 1]
+
+
+def _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting):
+    """The checks the two yuv_planes_* calls share -> (T, h0, w0, the kernel's format, stride and coefficient arguments)."""
+    for name, p in (("y", y), ("u", u), ("v", v)):
+        if not p.is_cuda:
+            raise _lib.FgvcHipError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
+        if p.dtype not in _YUV_DTYPES:
+            raise TypeError(f"{name}: expected torch.uint8 or torch.uint16, got {p.dtype}")
+        if p.dim() != 3:
+            raise ValueError(f"{name}: 3 dimensions ({'T, h0, w0' if name == 'y' else 'T, ceil(h0 / sub_y), ceil(w0 / sub_x)'}), got {tuple(p.shape)}")
+    if u.dtype != y.dtype or v.dtype != y.dtype:
+        raise TypeError(f"y, u, v: one dtype, got {y.dtype}, {u.dtype}, {v.dtype}")
+    if siting not in YUV_SITINGS:
+        raise ValueError(f"siting={siting!r}: one of {YUV_SITINGS}")
+    try:
+        sx, sy = (int(s) for s in subsampling)
+    except (TypeError, ValueError):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2") from None
+    if sx not in (1, 2) or sy not in (1, 2):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2")
+    depth, shift = int(depth), int(shift)
+    bits = 8 * y.element_size()
+    if not 8 <= depth <= 16 or shift < 0 or depth + shift > bits:
+        raise ValueError(f"depth={depth}, shift={shift}: depth 8..16 and depth + shift within the {bits} bits of {y.dtype}")
+    coef = yuv_coefficients_depth(matrix, range, depth)
+    T, h0, w0 = y.shape
+    want = (T, (h0 + sy - 1) // sy, (w0 + sx - 1) // sx)
+    if tuple(u.shape) != want or tuple(v.shape) != want:
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)} subsampled {(sx, sy)}, got {tuple(u.shape)} and "
+                         f"{tuple(v.shape)}")
+    if u.device != y.device or v.device != y.device:
+        raise ValueError(f"y, u, v: one device, got {y.device}, {u.device}, {v.device}")
+    if w0 > 1 and y.stride(2) != 1:
+        raise ValueError(f"y: luma columns must be adjacent (last stride 1), got strides {y.stride()}")
+    if any(n > 1 and su != sv for n, su, sv in zip(want, u.stride(), v.stride())):    # (an axis of one sample: its stride is never used)
+        raise ValueError(f"u, v: the same strides (the kernel takes one set for both planes), got {u.stride()} and {v.stride()}")
+    fmt = (y.element_size(), depth, shift, sx, sy)
+    return T, h0, w0, fmt, (y.stride(0), y.stride(1), u.stride(0), u.stride(1), u.stride(2)), coef, YUV_SITINGS.index(siting)
+
+
+def yuv_planes_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0,
+                      subsampling: Tuple[int, int] = (2, 2), size: Optional[Tuple[int, int]] = None,
+                      pad: Tuple[int, int, int, int] = (0, 0, 0, 0), matrix: str = "bt601", range: str = "limited", siting: str = "left",
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y'CbCr planes y (T, h0, w0), u, v (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) -- uint8 or uint16, one dtype; a sample is
+    (word >> shift) & (2^depth - 1); subsampling = (sub_x, sub_y), each 1 or 2 -- -> (T, 3, hp, wp) f32: per frame exactly
+    datasets.preprocess_yuv_frames at (top, left) of a border of exact zeros, one launch of fgvc_frames_yuvp_to_lab_f32.  The planes are read
+    through their strides (yuv_planes' views of packed frames, crops, time slices): nothing is copied; the luma columns must be adjacent
+    and u, v share their strides.  `siting` places the chroma of a horizontally subsampled format only.  Swapped chroma (NV21-style): pass the
+    planes swapped.  `size`, `pad`, `out`: as frames_to_lab's."""
+    T, h0, w0, fmt, strides, coef, sit = _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
+    left, right, top, bottom = (int(p) for p in pad)
+    shape = (T, 3, top + h + bottom, left + w + right)
+    if out is None:
+        out = torch.empty(shape, device=y.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    _lib.call("fgvc_frames_yuvp_to_lab_f32", _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *strides, *coef, sit, h, w, left, right, top, bottom,
+              _ptr(out), _stream(y))
+    return out
+
+
+def yuv_planes_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0,
+                       subsampling: Tuple[int, int] = (2, 2), matrix: str = "bt601", range: str = "limited", siting: str = "left",
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same planes -> (T, h0, w0, 3) uint8 RGB: rint (half to even) of the unclamped R'G'B' clamped to [0, 255], exactly
+    datasets.yuv_to_rgb8 -- one launch of fgvc_frames_yuvp_to_rgb8.  `out`: a contiguous uint8 tensor of that shape on the planes' device."""
+    T, h0, w0, fmt, strides, coef, sit = _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    shape = (T, h0, w0, 3)
+    if out is None:
+        out = torch.empty(shape, device=y.device, dtype=torch.uint8)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != y.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous uint8 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    _lib.call("fgvc_frames_yuvp_to_rgb8", _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *strides, *coef, sit, _ptr(out), _stream(y))
+    return out
+
+
 # ---- the output stage for 8-bit YUV 4:2:0 video: RGB bytes -> NV12 / I420 (DESIGN.md section 20) ------------------------------------------
 
 YUV_OUT_TILE = (8, 512)  # luma rows, columns one workgroup of fgvc_frames_rgb8_to_yuv420 owns (= fgvc_yuv_out_tile_rows/_cols(); the tests go one past them)

@@ -424,6 +424,28 @@ int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t
                                int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy, float crv,
                                float cgu, float cgv, float cbu, int siting, uint8_t* out, void* stream);
 
+/* ---- The input stage for planar and semi-planar Y'CbCr at 8 to 16 bits, 4:2:0 / 4:2:2 / 4:4:4: the two entries above
+ * generalised.  Per frame what datasets.preprocess_yuv_frames and datasets.yuv_to_rgb8 define.
+ *   sample_bytes 1 | 2: the planes hold uint8_t or (host-endian) uint16_t words; EVERY stride is in samples.  A sample is
+ *           (word >> shift) & (2^depth - 1), depth 8..16, shift 0..(8 sample_bytes - depth): P010 is depth 10, shift 6 (its low six bits are
+ *           ignored), yuv420p10le depth 10, shift 0 (bits above the depth are masked off).
+ *   sub_x, sub_y 1 | 2: chroma planes u, v [T][ch][cw], ch = ceil(h0 / sub_y), cw = ceil(w0 / sub_x), by (frame, row, pixel) strides as above.
+ *           A subsampled axis is interpolated as above (vertically between the rows, horizontally by `siting`); a full-resolution axis takes
+ *           the sample at the luma index, unchanged (`siting` is not used where sub_x = 1).
+ *   Decode: yy = cy (Y - y_off), cb = U' - c_off, cr = V' - c_off, then as above: the seven coefficients come by value
+ *           (ops.yuv_coefficients_depth).  At depth 8 with sub_x = sub_y = 2 the outputs equal the 8-bit entries' bit for bit.
+ * FGVC_ERR_INVALID_ARG as above, and for sample_bytes other than 1 or 2, a depth outside 8..16, depth + shift beyond the sample's bits, a
+ * negative shift, sub_x / sub_y other than 1 or 2, a 16-bit plane at an odd address -- all before any launch.  No workspace, no atomics, no
+ * LDS. */
+int fgvc_frames_yuvp_to_lab_f32(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
+                                int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
+                                int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
+                                int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out, void* stream);
+int fgvc_frames_yuvp_to_rgb8(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
+                             int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
+                             int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
+                             uint8_t* out, void* stream);
+
 /* ---- The output stage for 8-bit YUV 4:2:0 video, the mirror image of fgvc_frames_yuv420_to_rgb8: RGB bytes -> Y'CbCr
  * planes in one launch for all T frames; per frame what datasets.rgb8_to_yuv420 defines, byte for byte.
  *   frames [T][h0][w0][3] bytes by four BYTE strides (frame, row, pixel, channel): packed pixels are (.., .., 3, 1), planar frames

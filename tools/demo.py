@@ -20,7 +20,9 @@ the device -- through test_cfg.input = dict(type='rgb8') (DESIGN.md section 14);
 fgvc_amd.viz.flow_to_rgb on the host, flow_%05d.png.
 CLIP.y4m (what `ffmpeg -i clip.mp4 clip.y4m` writes: uncompressed 8-bit 4:2:0) goes to the model as the file holds it -- packed I420, through
 test_cfg.input = dict(type='i420', ...) with the file's chroma siting and range -- and is painted on
-ops.yuv_frames_to_rgb8's bytes.  A Y4M file does not say which matrix made its YUV: --yuv-matrix, by default bt709 from 720 rows up, else bt601.
+ops.yuv_frames_to_rgb8's bytes.  A file whose C tag is 4:2:2, 4:4:4 or 10 / 12 bits (C422, C444, C420p10, ..: `ffmpeg -pix_fmt yuv422p10le`) goes
+through datasets.read_y4m_planes, test_cfg.input = dict(type='yuv422p10', ...) and ops.yuv_planes_to_rgb8 (section 26); what is written stays
+8-bit.  A Y4M file does not say which matrix made its YUV: --yuv-matrix, by default bt709 from 720 rows up, else bt601.
 --out-video OUT.y4m also writes the result as video, for all three tasks (for --task flow the coloured flow frames): the painted frames go
 through fgvc_amd.viz.frames_to_yuv420 -- one launch of fgvc_frames_rgb8_to_yuv420 on the device unless --host-render is given (DESIGN.md
 section 20) -- and only the packed I420 frames, 1.5 bytes a pixel, cross to the host, where datasets.write_y4m writes them with the clip's frame
@@ -93,6 +95,8 @@ def load_y4m(a, dev):
     """CLIP.y4m -> (packed I420 frames (T, 3 H / 2, W) uint8 on the device, their RGB bytes (T, H, W, 3) on the device,
     test_cfg.input for them without its size)."""
     from fgvc_amd import datasets, ops
+    if datasets.read_y4m_header(a.frames) not in datasets._Y4M_SITING:        # not 8-bit 4:2:0: 4:2:2 / 4:4:4, 10 or 12 bits
+        return load_y4m_planes(a, dev)
     packed, info = datasets.read_y4m(a.frames)
     if packed.shape[0] == 0:
         raise ValueError(f"{a.frames}: no frames")
@@ -104,6 +108,27 @@ def load_y4m(a, dev):
     kw = dict(matrix=matrix, range=info["range"], siting=info["siting"])
     rgb = ops.yuv_frames_to_rgb8(*ops.yuv420_planes(packed, "i420"), **kw)
     return packed, rgb, dict(type="i420", **kw)
+
+
+def load_y4m_planes(a, dev):
+    """A CLIP.y4m whose C tag is not 8-bit 4:2:0 (C422, C444, C420p10, ..) -> what load_y4m returns: the packed frames as the file holds
+    them (uint8, or uint16 words) on the device, their RGB bytes by ops.yuv_planes_to_rgb8, test_cfg.input of the file's format."""
+    from fgvc_amd import datasets, ops
+    packed, info = datasets.read_y4m_planes(a.frames)
+    if packed.shape[0] == 0:
+        raise ValueError(f"{a.frames}: no frames")
+    fmt = info["format"]
+    _, sx, sy, depth, shift, _ = ops.YUV_PIXEL_FORMATS[fmt]
+    matrix = a.yuv_matrix or yuv_matrix_default(info["height"])
+    print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, {fmt} ({depth} bits), {info['range']} range; matrix {matrix} "
+          f"({'--yuv-matrix' if a.yuv_matrix else 'by the height: the file does not say'})")
+    a.yuv_info = dict(info, matrix=matrix)
+    packed = packed.to(dev)
+    kw = dict(matrix=matrix, range=info["range"])
+    if sx == 2:                                                               # (4:4:4 has no siting: test_cfg.input refuses the key)
+        kw["siting"] = info["siting"]
+    rgb = ops.yuv_planes_to_rgb8(*ops.yuv_planes(packed, fmt), depth, shift, (sx, sy), **kw)
+    return packed, rgb, dict(type=fmt, **kw)
 
 
 def _input(a, size):
