@@ -47,14 +47,10 @@ int flow_chain_launch(const float*, const float*, const uint8_t*, const uint8_t*
                       hipStream_t);
 int frames_rgb8_to_lab_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, int, int, int, int, int, int, float*,
                               hipStream_t);
-int frames_yuv420_to_lab_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
-                                long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
-int frames_yuv420_to_rgb8_launch(const uint8_t*, const uint8_t*, const uint8_t*, int, int, int, long long, long long, long long, long long,
-                                 long long, const float*, int, uint8_t*, hipStream_t);
-int frames_yuvp_to_lab_launch(const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long, long long, long long,
-                              long long, long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
-int frames_yuvp_to_rgb8_launch(const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long, long long, long long,
-                               long long, long long, const float*, int, uint8_t*, hipStream_t);
+int frames_yuv_to_lab_launch(const char*, bool, const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long, long long,
+                             long long, long long, long long, const float*, int, int, int, int, int, int, int, float*, hipStream_t);
+int frames_yuv_to_rgb8_launch(const char*, bool, const void*, const void*, const void*, int, int, int, int, int, int, int, int, long long,
+                              long long, long long, long long, long long, const float*, int, uint8_t*, hipStream_t);
 int frames_rgb8_to_yuv420_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, uint8_t*, long long, long long,
                                  uint8_t*, uint8_t*, long long, long long, long long, const float*, int, hipStream_t);
 void yuv_out_tile(int*, int*);
@@ -660,92 +656,101 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
                                    out, (hipStream_t)stream);
 }
 
-int fgvc_frames_yuv420_to_lab_f32(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
-                                  int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy,
-                                  float crv, float cgu, float cgv, float cbu, int siting, int h, int w, int pad_left, int pad_right,
-                                  int pad_top, int pad_bottom, float* out, void* stream) {
-  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_lab_f32: null pointer");
-  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_lab_f32: non-positive size (T=%d, %d x %d -> %d x %d)", T, h0, w0, h, w);
-  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_lab_f32: negative pad (%d, %d, %d, %d)", pad_left, pad_right, pad_top, pad_bottom);
+struct YuvFormat {                                         // the yuvp pair's format arguments
+  int sample_bytes, depth, shift, sub_x, sub_y;
+};
+static const YuvFormat YUV420 = {1, 8, 0, 2, 2};           // what the 8-bit 4:2:0 pair's planes are in those words
+
+// what the four fgvc_frames_yuv* entries check alike: pointers, the siting and -- `fmt`: the yuvp pair's, null for the 8-bit 4:2:0 pair --
+// the sample format, the subsampling and the planes' alignment
+static int yuv_check(const char* fn, const void* y, const void* u, const void* v, const void* out, const YuvFormat* fmt, int siting) {
+  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "%s: null pointer", fn);
+  if (fmt) {
+    FGVC_REQUIRE(fmt->sample_bytes == 1 || fmt->sample_bytes == 2, FGVC_ERR_INVALID_ARG, "%s: sample_bytes=%d (1 or 2)", fn, fmt->sample_bytes);
+    FGVC_REQUIRE(fmt->depth >= 8 && fmt->depth <= 16 && fmt->shift >= 0 && fmt->depth + fmt->shift <= 8 * fmt->sample_bytes,
+                 FGVC_ERR_INVALID_ARG, "%s: depth=%d, shift=%d (depth 8..16, shift >= 0, depth + shift within the %d bits of a sample)", fn,
+                 fmt->depth, fmt->shift, 8 * fmt->sample_bytes);
+    FGVC_REQUIRE((fmt->sub_x == 1 || fmt->sub_x == 2) && (fmt->sub_y == 1 || fmt->sub_y == 2), FGVC_ERR_INVALID_ARG,
+                 "%s: sub_x=%d, sub_y=%d (1 or 2 each)", fn, fmt->sub_x, fmt->sub_y);
+  }
   FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_lab_f32: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", siting);
+               "%s: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", fn, siting);
+  FGVC_REQUIRE(!fmt || fmt->sample_bytes == 1 || ((((uintptr_t)y) | ((uintptr_t)u) | ((uintptr_t)v)) & 1) == 0, FGVC_ERR_INVALID_ARG,
+               "%s: alignment (16-bit planes at even addresses)", fn);
+  return FGVC_OK;
+}
+
+// the Lab pair: checks, then the launch.  fmt: as yuv_check's; coef = (y_off, cy, c_off, crv, cgu, cgv, cbu)
+static int yuv_to_lab(const char* fn, const void* y, const void* u, const void* v, const YuvFormat* fmt, int T, int h0, int w0, int64_t y_stride_t,
+                      int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, const float* coef, int siting, int h, int w,
+                      int pad_left, int pad_right, int pad_top, int pad_bottom, float* out, void* stream) {
+  const int rc = yuv_check(fn, y, u, v, out, fmt, siting);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG, "%s: non-positive size (T=%d, %d x %d -> %d x %d)", fn, T, h0,
+               w0, h, w);
+  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG, "%s: negative pad (%d, %d, %d, %d)",
+               fn, pad_left, pad_right, pad_top, pad_bottom);
   const long long hp = (long long)pad_top + h + pad_bottom, wp = (long long)pad_left + w + pad_right;
   // the grid of fgvc_frames_rgb8_to_lab_f32; a source column's position in quarter chroma samples, 2 x, stays inside an int
   FGVC_REQUIRE(T <= 65535 && hp <= 4 * 65535ll && wp < (1ll << 30) && hp * wp < (1ll << 31) && h0 < (1 << 30) && w0 < (1 << 30),
                FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels, "
-               "source sides < 2^30)");
-  const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
-  return frames_yuv420_to_lab_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, h, w,
-                                     pad_left, pad_right, pad_top, pad_bottom, out, (hipStream_t)stream);
+               "%s: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels, source sides < 2^30)", fn);
+  const YuvFormat& f = fmt ? *fmt : YUV420;
+  return frames_yuv_to_lab_launch(fn, !fmt, y, u, v, f.sample_bytes, f.depth, f.shift, f.sub_x, f.sub_y, T, h0, w0, y_stride_t, y_stride_y,
+                                  c_stride_t, c_stride_y, c_stride_x, coef, siting, h, w, pad_left, pad_right, pad_top, pad_bottom, out,
+                                  (hipStream_t)stream);
+}
+
+// the bytes pair
+static int yuv_to_rgb8(const char* fn, const void* y, const void* u, const void* v, const YuvFormat* fmt, int T, int h0, int w0, int64_t y_stride_t,
+                       int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, const float* coef, int siting,
+                       uint8_t* out, void* stream) {
+  const int rc = yuv_check(fn, y, u, v, out, fmt, siting);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "%s: non-positive size (T=%d, %d x %d)", fn, T, h0, w0);
+  FGVC_REQUIRE(T <= 65535 && h0 <= 4 * 65535ll && w0 < (1 << 30) && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_INVALID_ARG,
+               "%s: shape beyond the launch grid (T <= 65535, rows <= 262140, frame < 2^31 pixels)", fn);
+  const YuvFormat& f = fmt ? *fmt : YUV420;
+  return frames_yuv_to_rgb8_launch(fn, !fmt, y, u, v, f.sample_bytes, f.depth, f.shift, f.sub_x, f.sub_y, T, h0, w0, y_stride_t, y_stride_y,
+                                   c_stride_t, c_stride_y, c_stride_x, coef, siting, out, (hipStream_t)stream);
+}
+
+// the 8-bit 4:2:0 pair launches the fixed-format instances (no fmt), the yuvp pair the run-time ones -- also at depth 8, (2, 2), shift 0
+int fgvc_frames_yuv420_to_lab_f32(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
+                                  int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy,
+                                  float crv, float cgu, float cgv, float cbu, int siting, int h, int w, int pad_left, int pad_right,
+                                  int pad_top, int pad_bottom, float* out, void* stream) {
+  const float coef[7] = {y_off, cy, 128.0f, crv, cgu, cgv, cbu};
+  return yuv_to_lab("fgvc_frames_yuv420_to_lab_f32", y, u, v, nullptr, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x,
+                    coef, siting, h, w, pad_left, pad_right, pad_top, pad_bottom, out, stream);
 }
 
 int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
                                int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y, int64_t c_stride_x, float y_off, float cy, float crv,
                                float cgu, float cgv, float cbu, int siting, uint8_t* out, void* stream) {
-  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_rgb8: null pointer");
-  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuv420_to_rgb8: non-positive size (T=%d, %d x %d)", T, h0, w0);
-  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_rgb8: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", siting);
-  FGVC_REQUIRE(T <= 65535 && h0 <= 4 * 65535ll && w0 < (1 << 30) && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuv420_to_rgb8: shape beyond the launch grid (T <= 65535, rows <= 262140, frame < 2^31 pixels)");
-  const float coef[6] = {y_off, cy, crv, cgu, cgv, cbu};
-  return frames_yuv420_to_rgb8_launch(y, u, v, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting, out,
-                                      (hipStream_t)stream);
-}
-
-// what the two fgvc_frames_yuvp_* entries check alike: pointers, the sample format, the subsampling, the siting
-static int yuvp_check(const char* fn, const void* y, const void* u, const void* v, const void* out, int sample_bytes, int depth, int shift,
-                      int sub_x, int sub_y, int siting) {
-  FGVC_REQUIRE(y && u && v && out, FGVC_ERR_INVALID_ARG, "%s: null pointer", fn);
-  FGVC_REQUIRE(sample_bytes == 1 || sample_bytes == 2, FGVC_ERR_INVALID_ARG, "%s: sample_bytes=%d (1 or 2)", fn, sample_bytes);
-  FGVC_REQUIRE(depth >= 8 && depth <= 16 && shift >= 0 && depth + shift <= 8 * sample_bytes, FGVC_ERR_INVALID_ARG,
-               "%s: depth=%d, shift=%d (depth 8..16, shift >= 0, depth + shift within the %d bits of a sample)", fn, depth, shift,
-               8 * sample_bytes);
-  FGVC_REQUIRE((sub_x == 1 || sub_x == 2) && (sub_y == 1 || sub_y == 2), FGVC_ERR_INVALID_ARG, "%s: sub_x=%d, sub_y=%d (1 or 2 each)", fn, sub_x,
-               sub_y);
-  FGVC_REQUIRE(siting == FGVC_YUV_SITING_LEFT || siting == FGVC_YUV_SITING_CENTER, FGVC_ERR_INVALID_ARG,
-               "%s: siting=%d (FGVC_YUV_SITING_LEFT or FGVC_YUV_SITING_CENTER)", fn, siting);
-  FGVC_REQUIRE(sample_bytes == 1 || ((((uintptr_t)y) | ((uintptr_t)u) | ((uintptr_t)v)) & 1) == 0, FGVC_ERR_INVALID_ARG,
-               "%s: alignment (16-bit planes at even addresses)", fn);
-  return FGVC_OK;
+  const float coef[7] = {y_off, cy, 128.0f, crv, cgu, cgv, cbu};
+  return yuv_to_rgb8("fgvc_frames_yuv420_to_rgb8", y, u, v, nullptr, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef,
+                     siting, out, stream);
 }
 
 int fgvc_frames_yuvp_to_lab_f32(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
                                 int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
                                 int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
                                 int h, int w, int pad_left, int pad_right, int pad_top, int pad_bottom, float* out, void* stream) {
-  const int rc = yuvp_check("fgvc_frames_yuvp_to_lab_f32", y, u, v, out, sample_bytes, depth, shift, sub_x, sub_y, siting);
-  if (rc != FGVC_OK) return rc;
-  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0 && h > 0 && w > 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuvp_to_lab_f32: non-positive size (T=%d, %d x %d -> %d x %d)", T, h0, w0, h, w);
-  FGVC_REQUIRE(pad_left >= 0 && pad_right >= 0 && pad_top >= 0 && pad_bottom >= 0, FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuvp_to_lab_f32: negative pad (%d, %d, %d, %d)", pad_left, pad_right, pad_top, pad_bottom);
-  const long long hp = (long long)pad_top + h + pad_bottom, wp = (long long)pad_left + w + pad_right;
-  // the grid of fgvc_frames_yuv420_to_lab_f32
-  FGVC_REQUIRE(T <= 65535 && hp <= 4 * 65535ll && wp < (1ll << 30) && hp * wp < (1ll << 31) && h0 < (1 << 30) && w0 < (1 << 30),
-               FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuvp_to_lab_f32: shape beyond the launch grid (T <= 65535, padded rows <= 262140, padded plane < 2^31 pixels, "
-               "source sides < 2^30)");
+  const YuvFormat fmt = {sample_bytes, depth, shift, sub_x, sub_y};
   const float coef[7] = {y_off, cy, c_off, crv, cgu, cgv, cbu};
-  return frames_yuvp_to_lab_launch(y, u, v, sample_bytes, depth, shift, sub_x, sub_y, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y,
-                                   c_stride_x, coef, siting, h, w, pad_left, pad_right, pad_top, pad_bottom, out, (hipStream_t)stream);
+  return yuv_to_lab("fgvc_frames_yuvp_to_lab_f32", y, u, v, &fmt, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef,
+                    siting, h, w, pad_left, pad_right, pad_top, pad_bottom, out, stream);
 }
 
 int fgvc_frames_yuvp_to_rgb8(const void* y, const void* u, const void* v, int sample_bytes, int depth, int shift, int sub_x, int sub_y, int T,
                              int h0, int w0, int64_t y_stride_t, int64_t y_stride_y, int64_t c_stride_t, int64_t c_stride_y,
                              int64_t c_stride_x, float y_off, float cy, float c_off, float crv, float cgu, float cgv, float cbu, int siting,
                              uint8_t* out, void* stream) {
-  const int rc = yuvp_check("fgvc_frames_yuvp_to_rgb8", y, u, v, out, sample_bytes, depth, shift, sub_x, sub_y, siting);
-  if (rc != FGVC_OK) return rc;
-  FGVC_REQUIRE(T > 0 && h0 > 0 && w0 > 0, FGVC_ERR_INVALID_ARG, "fgvc_frames_yuvp_to_rgb8: non-positive size (T=%d, %d x %d)", T, h0, w0);
-  FGVC_REQUIRE(T <= 65535 && h0 <= 4 * 65535ll && w0 < (1 << 30) && (long long)h0 * w0 < (1ll << 31), FGVC_ERR_INVALID_ARG,
-               "fgvc_frames_yuvp_to_rgb8: shape beyond the launch grid (T <= 65535, rows <= 262140, frame < 2^31 pixels)");
+  const YuvFormat fmt = {sample_bytes, depth, shift, sub_x, sub_y};
   const float coef[7] = {y_off, cy, c_off, crv, cgu, cgv, cbu};
-  return frames_yuvp_to_rgb8_launch(y, u, v, sample_bytes, depth, shift, sub_x, sub_y, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y,
-                                    c_stride_x, coef, siting, out, (hipStream_t)stream);
+  return yuv_to_rgb8("fgvc_frames_yuvp_to_rgb8", y, u, v, &fmt, T, h0, w0, y_stride_t, y_stride_y, c_stride_t, c_stride_y, c_stride_x, coef, siting,
+                     out, stream);
 }
 
 int fgvc_yuv_out_tile_rows(void) {

@@ -1,4 +1,4 @@
-// What the two input kernels share (input.hip: uint8 RGB; input_yuv.hip: 8-bit YUV 4:2:0): the arithmetic from R'G'B' on the 0..255 scale to
+// What the two input kernels share (input.hip: uint8 RGB; input_yuv.hip: Y'CbCr planes): the arithmetic from R'G'B' on the 0..255 scale to
 // the normalised Lab planes, the resize taps and the launch geometry.  One definition, so that the same R'G'B' gives the same bits through
 // either kernel (DESIGN.md sections 14 and 19).
 #pragma once

@@ -751,7 +751,7 @@ def read_flo(path) -> np.ndarray:
     return np.ascontiguousarray(data.reshape(h, w, 2).transpose(2, 0, 1)).astype(np.float32)
 
 
-# ---- 8-bit YUV 4:2:0 video: the input contract as torch ops, and Y4M files -----------------------------------------
+# ---- Y'CbCr video at 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4: the input contract as torch ops (DESIGN.md sections 19 and 26) ----------------------
 def _chroma_taps(n_luma: int, n: int, back: bool, device):
     """Chroma samples around every luma index of one axis: s = p / 2 - 0.25 (`back`) or p / 2, clamped to [0, n - 1] -> i0, i1, weight of i1."""
     p = torch.arange(n_luma, device=device, dtype=torch.float32)
@@ -760,57 +760,113 @@ def _chroma_taps(n_luma: int, n: int, back: bool, device):
     return i0.long(), (i0.long() + 1).clamp(max=n - 1), s - i0
 
 
-def yuv420_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, siting: str = "left") -> torch.Tensor:
-    """One chroma plane (T, ch, cw) uint8 -> its value at every luma pixel (T, h0, w0) f32: bilinear, edge clamped, vertically between the
-    luma rows, horizontally on the even luma columns ('left': MPEG-2, H.264, HEVC) or between them ('center': JPEG, MPEG-1).  Exact: quarter
-    weights on byte samples."""
+def _yuv_subsampling(subsampling):
+    try:
+        sx, sy = (int(s) for s in subsampling)
+    except (TypeError, ValueError):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2") from None
+    if sx not in (1, 2) or sy not in (1, 2):
+        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2")
+    return sx, sy
+
+
+def yuv_samples(p: torch.Tensor, depth: int = 8, shift: int = 0) -> torch.Tensor:
+    """A plane of uint8 / uint16 words -> its samples as f32: (word >> shift) & (2^depth - 1) -- P010 keeps its sample in the high bits
+    (shift 6), a low-aligned format may carry anything above the depth.  (Through int32: torch has no shifts on uint16.)"""
+    if p.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"expected torch.uint8 or torch.uint16, got {p.dtype}")
+    depth, shift = int(depth), int(shift)
+    if not 8 <= depth <= 16 or shift < 0 or depth + shift > 8 * p.element_size():
+        raise ValueError(f"depth={depth}, shift={shift}: depth 8..16 and depth + shift within the {8 * p.element_size()} bits of {p.dtype}")
+    return ((p.to(torch.int32) >> shift) & ((1 << depth) - 1)).to(torch.float32)
+
+
+def yuv_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, subsampling=(2, 2), siting: str = "left") -> torch.Tensor:
+    """One chroma plane (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of sample values -> its value at every luma pixel (T, h0, w0) f32.  A
+    subsampled axis is interpolated bilinearly, edge clamped: vertically between the luma rows, horizontally on the even luma columns
+    ('left': MPEG-2, H.264, HEVC) or between them ('center': JPEG, MPEG-1); a full-resolution axis takes the sample at the luma index and no
+    arithmetic touches it.  Exact: sixteenths on integers below 2^16 are 20 bits at most."""
     if siting not in ("left", "center"):
         raise ValueError(f"siting={siting!r}: 'left' or 'center'")
+    sx, sy = _yuv_subsampling(subsampling)
     c = c.to(torch.float32)
+
+    def across(r):
+        if sx == 1:
+            return r
+        x0, x1, lx = _chroma_taps(w0, c.shape[2], siting == "center", c.device)
+        return (1 - lx) * r[:, :, x0] + lx * r[:, :, x1]
+    if sy == 1:
+        return across(c)
     y0, y1, ly = _chroma_taps(h0, c.shape[1], True, c.device)
-    x0, x1, lx = _chroma_taps(w0, c.shape[2], siting == "center", c.device)
-    r0, r1 = c[:, y0], c[:, y1]
-    top = (1 - lx) * r0[:, :, x0] + lx * r0[:, :, x1]
-    bot = (1 - lx) * r1[:, :, x0] + lx * r1[:, :, x1]
-    return (1 - ly)[:, None] * top + ly[:, None] * bot
+    return (1 - ly)[:, None] * across(c[:, y0]) + ly[:, None] * across(c[:, y1])
 
 
-def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
-                  siting: str = "left") -> torch.Tensor:
-    """Planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> R'G'B' (T, 3, h0, w0) f32 on the 0..255 scale, neither clamped
-    nor rounded: chroma at the luma pixel, then yy = cy (Y - y_off), R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with
-    ops.yuv_coefficients rounded to f32 -- one rounded f32 operation after another, the order the kernels keep.  CPU or GPU tensors."""
-    from .ops import yuv_coefficients
-    y_off, cy, crv, cgu, cgv, cbu = (float(np.float32(c)) for c in yuv_coefficients(matrix, range))
+def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+               matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
+    """Planes y (T, h0, w0), u, v (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of uint8 / uint16 words -> R'G'B' (T, 3, h0, w0) f32 on the 0..255
+    scale, neither clamped nor rounded: samples by yuv_samples, chroma at the luma pixel, then yy = cy (Y - y_off), cb = U - c_off,
+    cr = V - c_off, R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with ops.yuv_coefficients_depth rounded to f32 -- one
+    rounded f32 operation after another, the order the kernels keep.  CPU or GPU tensors."""
+    from .ops import yuv_coefficients_depth
+    y_off, cy, c_off, crv, cgu, cgv, cbu = (float(np.float32(c)) for c in yuv_coefficients_depth(matrix, range, depth))
+    sx, sy = _yuv_subsampling(subsampling)
     T, h0, w0 = y.shape
-    want = (T, (h0 + 1) // 2, (w0 + 1) // 2)
+    want = (T, (h0 + sy - 1) // sy, (w0 + sx - 1) // sx)
     if tuple(u.shape) != want or tuple(v.shape) != want:
-        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)}, got {tuple(u.shape)} and {tuple(v.shape)}")
-    yy = cy * (y.to(torch.float32) - y_off)
-    cb = yuv420_chroma_at_luma(u, h0, w0, siting) - 128.0
-    cr = yuv420_chroma_at_luma(v, h0, w0, siting) - 128.0
+        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)} subsampled {(sx, sy)}, got {tuple(u.shape)} and "
+                         f"{tuple(v.shape)}")
+    yy = cy * (yuv_samples(y, depth, shift) - y_off)
+    cb = yuv_chroma_at_luma(yuv_samples(u, depth, shift), h0, w0, (sx, sy), siting) - c_off
+    cr = yuv_chroma_at_luma(yuv_samples(v, depth, shift), h0, w0, (sx, sy), siting) - c_off
     return torch.stack([yy + crv * cr, (yy + cgu * cb) + cgv * cr, yy + cbu * cb], 1)
 
 
-def yuv420_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
-                   siting: str = "left") -> torch.Tensor:
-    """-> (T, h0, w0, 3) uint8: yuv420_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_frames_to_rgb8 computes)."""
-    rgb = yuv420_to_rgb(y, u, v, matrix, range, siting)
+def yuv_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+                matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
+    """-> (T, h0, w0, 3) uint8: yuv_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_planes_to_rgb8 computes)."""
+    rgb = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
     return rgb.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
-def preprocess_yuv420_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size=None, matrix: str = "bt601", range: str = "limited",
-                             siting: str = "left") -> torch.Tensor:
-    """8-bit YUV 4:2:0 planes -> (1, T, 3, h, w) float32 network input: yuv420_to_rgb, then preprocess_tapvid_frames' steps on the unclamped
-    R'G'B' (bilinear resize to `size`, None = the frames' own; / 255 and clamp; RGB -> Lab; (x - [50, 0, 0]) / [50, 127, 127]).  The contract
-    ops.yuv_frames_to_lab is held to."""
-    x = yuv420_to_rgb(y, u, v, matrix, range, siting)
+def preprocess_yuv_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
+                          matrix: str = "bt601", range: str = "limited", siting: str = "left", size=None) -> torch.Tensor:
+    """The same planes -> (1, T, 3, h, w) float32 network input: yuv_to_rgb, then preprocess_tapvid_frames' steps on the unclamped R'G'B'
+    (bilinear resize to `size`, None = the frames' own; / 255 and clamp; RGB -> Lab; (x - [50, 0, 0]) / [50, 127, 127]).  The contract
+    ops.yuv_planes_to_lab is held to."""
+    x = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
     if size is not None and tuple(x.shape[-2:]) != tuple(size):
         x = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
     lab = rgb_to_lab((x / 255.0).clamp(0, 1))
     mean = torch.tensor([50.0, 0.0, 0.0], device=lab.device).view(1, 3, 1, 1)
     std = torch.tensor([50.0, 127.0, 127.0], device=lab.device).view(1, 3, 1, 1)
     return ((lab - mean) / std).unsqueeze(0)
+
+
+# 8-bit 4:2:0 (NV12 / I420 planes, section 19): the same contract at depth 8, shift 0, (2, 2) -- bit for bit what these were on their own
+def yuv420_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, siting: str = "left") -> torch.Tensor:
+    """One chroma plane (T, ch, cw) uint8 -> its value at every luma pixel (T, h0, w0) f32: yuv_chroma_at_luma with both axes subsampled."""
+    return yuv_chroma_at_luma(c, h0, w0, (2, 2), siting)
+
+
+def yuv420_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                  siting: str = "left") -> torch.Tensor:
+    """Planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> R'G'B' (T, 3, h0, w0) f32 on the 0..255 scale, neither clamped
+    nor rounded: yuv_to_rgb of 8-bit 4:2:0 planes."""
+    return yuv_to_rgb(y, u, v, 8, 0, (2, 2), matrix, range, siting)
+
+
+def yuv420_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                   siting: str = "left") -> torch.Tensor:
+    """-> (T, h0, w0, 3) uint8: yuv420_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_frames_to_rgb8 computes)."""
+    return yuv_to_rgb8(y, u, v, 8, 0, (2, 2), matrix, range, siting)
+
+
+def preprocess_yuv420_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size=None, matrix: str = "bt601", range: str = "limited",
+                             siting: str = "left") -> torch.Tensor:
+    """8-bit YUV 4:2:0 planes -> (1, T, 3, h, w) float32 network input: preprocess_yuv_frames of them.  The contract ops.yuv_frames_to_lab
+    is held to."""
+    return preprocess_yuv_frames(y, u, v, 8, 0, (2, 2), matrix, range, siting, size)
 
 
 # ---- the way out: RGB bytes -> 8-bit YUV 4:2:0, the output contract as torch ops (DESIGN.md section 20) -----------------------------------
@@ -878,170 +934,16 @@ def pack_yuv420(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: str = "i
     return torch.cat([y, c], 1).contiguous()
 
 
+# ---- Y4M files: progressive planar frames, 8 to 12 bits, 4:2:0 / 4:2:2 / 4:4:4 (DESIGN.md sections 19 and 26) -------------------------------
 Y4M_MAGIC = b"YUV4MPEG2"
-_Y4M_SITING = {"420jpeg": "center", "420mpeg2": "left", "420": "left"}
-
-
-def read_y4m(path, max_frames=None):
-    """A YUV4MPEG2 file of progressive 8-bit 4:2:0 frames -> (frames (T, 3 h / 2, w) uint8 tensor, packed I420 as the file holds them; info =
-    dict(width, height, fps=(num, den), siting, range)).  C420jpeg and no C tag: siting 'center'; C420mpeg2 and C420: 'left'.
-    XCOLORRANGE=FULL | LIMITED: range 'full' | 'limited', absent 'limited'.  ValueError that names the tag or the fact for any other chroma
-    tag, interlaced material (It / Ib / Im), an odd size and a truncated frame.  `max_frames`: stop after that many."""
-    with open(path, "rb") as fh:
-        head = fh.readline(4096)
-        tags = head.rstrip(b"\n").split(b" ")
-        if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
-            raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
-        w = h = None
-        fps, chroma, rng = (0, 0), "420jpeg", "limited"
-        for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
-            k, val = tag[0], tag[1:]
-            if k == "W":
-                w = int(val)
-            elif k == "H":
-                h = int(val)
-            elif k == "F":
-                num, _, den = val.partition(":")
-                fps = (int(num), int(den or 1))
-            elif k == "I" and val not in ("p", "?"):
-                raise ValueError(f"{path}: interlaced material (I{val}) is not supported; deinterlace it first")
-            elif k == "C":
-                chroma = val
-            elif k == "X" and val.upper().startswith("COLORRANGE="):
-                rng = val[11:].lower()
-                if rng not in ("full", "limited"):
-                    raise ValueError(f"{path}: XCOLORRANGE={val[11:]} (FULL or LIMITED)")
-        if chroma not in _Y4M_SITING:
-            raise ValueError(f"{path}: chroma tag C{chroma} is not supported (8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420)")
-        if w is None or h is None or w < 1 or h < 1:
-            raise ValueError(f"{path}: the header gives no frame size (W, H)")
-        if w % 2 or h % 2:
-            raise ValueError(f"{path}: odd size {w} x {h}; a 4:2:0 frame with an odd side has no packed form")
-        n = w * h * 3 // 2
-        frames = []
-        while max_frames is None or len(frames) < max_frames:
-            line = fh.readline(4096)
-            if not line:
-                break
-            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
-                raise ValueError(f"{path}: frame {len(frames)}: expected a FRAME header")
-            data = fh.read(n)
-            if len(data) != n:
-                raise ValueError(f"{path}: frame {len(frames)} is truncated ({len(data)} of {n} bytes)")
-            frames.append(np.frombuffer(data, np.uint8))
-    arr = np.stack(frames).reshape(len(frames), h * 3 // 2, w) if frames else np.zeros((0, h * 3 // 2, w), np.uint8)
-    return torch.from_numpy(arr.copy()), dict(width=w, height=h, fps=fps, siting=_Y4M_SITING[chroma], range=rng)
-
-
-def write_y4m(path, frames, fps=(30, 1), siting: str = "left", range: str = "limited") -> None:
-    """Packed I420 frames (T, 3 h / 2, w) uint8 (tensor or array) -> a YUV4MPEG2 file: progressive, square pixels, C420mpeg2 ('left') or
-    C420jpeg ('center'), XCOLORRANGE=LIMITED | FULL."""
-    f = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
-    if f.ndim != 3 or f.dtype != np.uint8 or f.shape[1] % 3 or (f.shape[1] // 3 * 2) % 2 or f.shape[2] % 2:
-        raise ValueError(f"write_y4m: packed I420 frames (T, 3 h / 2, w) uint8 with h and w even, got {f.dtype} {f.shape}")
-    if siting not in ("left", "center") or range not in ("limited", "full"):
-        raise ValueError(f"write_y4m: siting={siting!r} ('left' | 'center'), range={range!r} ('limited' | 'full')")
-    h, w = f.shape[1] // 3 * 2, f.shape[2]
-    chroma = "420mpeg2" if siting == "left" else "420jpeg"
-    with open(path, "wb") as fh:
-        fh.write(f"YUV4MPEG2 W{w} H{h} F{int(fps[0])}:{int(fps[1])} Ip A1:1 C{chroma} XCOLORRANGE={range.upper()}\n".encode("ascii"))
-        for frame in f:
-            fh.write(b"FRAME\n")
-            fh.write(np.ascontiguousarray(frame).tobytes())
-
-
-# ---- Y'CbCr at 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4: the input contract as torch ops, and Y4M files (DESIGN.md section 26) ---------------------
-def _yuv_subsampling(subsampling):
-    try:
-        sx, sy = (int(s) for s in subsampling)
-    except (TypeError, ValueError):
-        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2") from None
-    if sx not in (1, 2) or sy not in (1, 2):
-        raise ValueError(f"subsampling={subsampling!r}: (sub_x, sub_y), each 1 or 2")
-    return sx, sy
-
-
-def yuv_samples(p: torch.Tensor, depth: int = 8, shift: int = 0) -> torch.Tensor:
-    """A plane of uint8 / uint16 words -> its samples as f32: (word >> shift) & (2^depth - 1) -- P010 keeps its sample in the high bits
-    (shift 6), a low-aligned format may carry anything above the depth.  (Through int32: torch has no shifts on uint16.)"""
-    if p.dtype not in (torch.uint8, torch.uint16):
-        raise TypeError(f"expected torch.uint8 or torch.uint16, got {p.dtype}")
-    depth, shift = int(depth), int(shift)
-    if not 8 <= depth <= 16 or shift < 0 or depth + shift > 8 * p.element_size():
-        raise ValueError(f"depth={depth}, shift={shift}: depth 8..16 and depth + shift within the {8 * p.element_size()} bits of {p.dtype}")
-    return ((p.to(torch.int32) >> shift) & ((1 << depth) - 1)).to(torch.float32)
-
-
-def yuv_chroma_at_luma(c: torch.Tensor, h0: int, w0: int, subsampling=(2, 2), siting: str = "left") -> torch.Tensor:
-    """One chroma plane (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of sample values -> its value at every luma pixel (T, h0, w0) f32.  A
-    subsampled axis is interpolated as yuv420_chroma_at_luma does (bilinear, edge clamped; vertically between the luma rows, horizontally by
-    `siting`); a full-resolution axis takes the sample at the luma index and no arithmetic touches it.  Exact: sixteenths on integers below
-    2^16 are 20 bits at most."""
-    if siting not in ("left", "center"):
-        raise ValueError(f"siting={siting!r}: 'left' or 'center'")
-    sx, sy = _yuv_subsampling(subsampling)
-    c = c.to(torch.float32)
-
-    def across(r):
-        if sx == 1:
-            return r
-        x0, x1, lx = _chroma_taps(w0, c.shape[2], siting == "center", c.device)
-        return (1 - lx) * r[:, :, x0] + lx * r[:, :, x1]
-    if sy == 1:
-        return across(c)
-    y0, y1, ly = _chroma_taps(h0, c.shape[1], True, c.device)
-    return (1 - ly)[:, None] * across(c[:, y0]) + ly[:, None] * across(c[:, y1])
-
-
-def yuv_to_rgb(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
-               matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
-    """Planes y (T, h0, w0), u, v (T, ceil(h0 / sub_y), ceil(w0 / sub_x)) of uint8 / uint16 words -> R'G'B' (T, 3, h0, w0) f32 on the 0..255
-    scale, neither clamped nor rounded: samples by yuv_samples, chroma at the luma pixel, then yy = cy (Y - y_off), cb = U - c_off,
-    cr = V - c_off, R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with ops.yuv_coefficients_depth rounded to f32 -- one
-    rounded f32 operation after another, the order the kernels keep.  CPU or GPU tensors."""
-    from .ops import yuv_coefficients_depth
-    y_off, cy, c_off, crv, cgu, cgv, cbu = (float(np.float32(c)) for c in yuv_coefficients_depth(matrix, range, depth))
-    sx, sy = _yuv_subsampling(subsampling)
-    T, h0, w0 = y.shape
-    want = (T, (h0 + sy - 1) // sy, (w0 + sx - 1) // sx)
-    if tuple(u.shape) != want or tuple(v.shape) != want:
-        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)} subsampled {(sx, sy)}, got {tuple(u.shape)} and "
-                         f"{tuple(v.shape)}")
-    yy = cy * (yuv_samples(y, depth, shift) - y_off)
-    cb = yuv_chroma_at_luma(yuv_samples(u, depth, shift), h0, w0, (sx, sy), siting) - c_off
-    cr = yuv_chroma_at_luma(yuv_samples(v, depth, shift), h0, w0, (sx, sy), siting) - c_off
-    return torch.stack([yy + crv * cr, (yy + cgu * cb) + cgv * cr, yy + cbu * cb], 1)
-
-
-def yuv_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
-                matrix: str = "bt601", range: str = "limited", siting: str = "left") -> torch.Tensor:
-    """-> (T, h0, w0, 3) uint8: yuv_to_rgb clamped to [0, 255] and rounded half to even (what ops.yuv_planes_to_rgb8 computes)."""
-    rgb = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
-    return rgb.clamp(0, 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous()
-
-
-def preprocess_yuv_frames(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0, subsampling=(2, 2),
-                          matrix: str = "bt601", range: str = "limited", siting: str = "left", size=None) -> torch.Tensor:
-    """The same planes -> (1, T, 3, h, w) float32 network input: yuv_to_rgb, then preprocess_yuv420_frames' steps on the unclamped R'G'B'
-    (bilinear resize to `size`, None = the frames' own; / 255 and clamp; RGB -> Lab; (x - [50, 0, 0]) / [50, 127, 127]).  The contract
-    ops.yuv_planes_to_lab is held to."""
-    x = yuv_to_rgb(y, u, v, depth, shift, subsampling, matrix, range, siting)
-    if size is not None and tuple(x.shape[-2:]) != tuple(size):
-        x = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=False)
-    lab = rgb_to_lab((x / 255.0).clamp(0, 1))
-    mean = torch.tensor([50.0, 0.0, 0.0], device=lab.device).view(1, 3, 1, 1)
-    std = torch.tensor([50.0, 127.0, 127.0], device=lab.device).view(1, 3, 1, 1)
-    return ((lab - mean) / std).unsqueeze(0)
-
-
 # a Y4M chroma tag -> (format: a ops.YUV_PIXEL_FORMATS name or 'i420', siting)
 _Y4M_PLANES = {"420jpeg": ("i420", "center"), "420mpeg2": ("i420", "left"), "420": ("i420", "left"),
                "422": ("yuv422p", "left"), "444": ("yuv444p", "left"),
                "420p10": ("yuv420p10", "left"), "420p12": ("yuv420p12", "left"),
                "422p10": ("yuv422p10", "left"), "422p12": ("yuv422p12", "left"),
                "444p10": ("yuv444p10", "left"), "444p12": ("yuv444p12", "left")}
-_Y4M_TAGS = {"yuv422p": "422", "yuv444p": "444", "yuv420p10": "420p10", "yuv420p12": "420p12", "yuv422p10": "422p10",
-             "yuv422p12": "422p12", "yuv444p10": "444p10", "yuv444p12": "444p12"}
+_Y4M_SITING = {tag: siting for tag, (fmt, siting) in _Y4M_PLANES.items() if fmt == "i420"}       # the 8-bit 4:2:0 tags: what read_y4m takes
+_Y4M_TAGS = {fmt: tag for tag, (fmt, _) in _Y4M_PLANES.items() if fmt != "i420"}
 
 
 def _y4m_format(fmt: str):
@@ -1053,58 +955,46 @@ def _y4m_format(fmt: str):
     return sx, sy, depth, np.dtype("<u2") if dtype == torch.uint16 else np.dtype(np.uint8)
 
 
-def read_y4m_header(path) -> str:
-    """The chroma tag of a YUV4MPEG2 file's header ('420jpeg' where it has none).  ValueError for another file."""
-    with open(path, "rb") as fh:
-        head = fh.readline(4096)
+def _y4m_header(fh, path):
+    """The header line of an open YUV4MPEG2 file -> (width, height, fps, chroma tag ('420jpeg' where it has none), range).  ValueError for
+    another signature, interlaced material, an XCOLORRANGE that is neither FULL nor LIMITED and a header without a size."""
+    head = fh.readline(4096)
     tags = head.rstrip(b"\n").split(b" ")
     if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
         raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
-    chroma = "420jpeg"
+    w = h = None
+    fps, chroma, rng = (0, 0), "420jpeg", "limited"
     for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
-        if tag[0] == "C":
-            chroma = tag[1:]
-    return chroma
+        k, val = tag[0], tag[1:]
+        if k == "W":
+            w = int(val)
+        elif k == "H":
+            h = int(val)
+        elif k == "F":
+            num, _, den = val.partition(":")
+            fps = (int(num), int(den or 1))
+        elif k == "I" and val not in ("p", "?"):
+            raise ValueError(f"{path}: interlaced material (I{val}) is not supported; deinterlace it first")
+        elif k == "C":
+            chroma = val
+        elif k == "X" and val.upper().startswith("COLORRANGE="):
+            rng = val[11:].lower()
+            if rng not in ("full", "limited"):
+                raise ValueError(f"{path}: XCOLORRANGE={val[11:]} (FULL or LIMITED)")
+    if w is None or h is None or w < 1 or h < 1:
+        raise ValueError(f"{path}: the header gives no frame size (W, H)")
+    return w, h, fps, chroma, rng
 
 
-def read_y4m_planes(path, max_frames=None):
-    """A YUV4MPEG2 file of progressive frames, 8 to 12 bits, 4:2:0 / 4:2:2 / 4:4:4 -> (frames (T, rows, w) in the file's own arrangement --
-    the luma rows, then the u plane and the v plane: what ops.yuv_planes takes apart (ops.yuv420_planes for 'i420') -- uint8, or uint16
-    from the file's little-endian words; info = read_y4m's keys plus format (an ops.YUV_PIXEL_FORMATS name, or 'i420') and depth).
-    C420jpeg, C420mpeg2, C420 and no C tag as read_y4m reads them; C422, C444; C420p10, C420p12, C422p10, C422p12, C444p10, C444p12, siting
-    'left'.  ValueError that names the tag or the fact for any other chroma tag (Cmono*, C411, C444alpha, C420paldv, ..), interlaced
-    material, a side that is odd on a subsampled axis and a truncated frame.  `max_frames`: stop after that many."""
+def _read_y4m(path, max_frames, tags, supported: str):
+    """What read_y4m and read_y4m_planes share: the file's frames as it holds them and read_y4m_planes' info; `tags`: the chroma tags taken,
+    `supported`: what the refusal of another says they are."""
     with open(path, "rb") as fh:
-        head = fh.readline(4096)
-        tags = head.rstrip(b"\n").split(b" ")
-        if tags[0] != Y4M_MAGIC or not head.endswith(b"\n"):
-            raise ValueError(f"{path}: not a YUV4MPEG2 file (signature)")
-        w = h = None
-        fps, chroma, rng = (0, 0), "420jpeg", "limited"
-        for tag in (t.decode("ascii", "replace") for t in tags[1:] if t):
-            k, val = tag[0], tag[1:]
-            if k == "W":
-                w = int(val)
-            elif k == "H":
-                h = int(val)
-            elif k == "F":
-                num, _, den = val.partition(":")
-                fps = (int(num), int(den or 1))
-            elif k == "I" and val not in ("p", "?"):
-                raise ValueError(f"{path}: interlaced material (I{val}) is not supported; deinterlace it first")
-            elif k == "C":
-                chroma = val
-            elif k == "X" and val.upper().startswith("COLORRANGE="):
-                rng = val[11:].lower()
-                if rng not in ("full", "limited"):
-                    raise ValueError(f"{path}: XCOLORRANGE={val[11:]} (FULL or LIMITED)")
-        if chroma not in _Y4M_PLANES:
-            raise ValueError(f"{path}: chroma tag C{chroma} is not supported (planar 4:2:0, 4:2:2 and 4:4:4 at 8, 10 or 12 bits: "
-                             f"{', '.join('C' + t for t in _Y4M_PLANES)})")
+        w, h, fps, chroma, rng = _y4m_header(fh, path)
+        if chroma not in tags:
+            raise ValueError(f"{path}: chroma tag C{chroma} is not supported ({supported})")
         fmt, siting = _Y4M_PLANES[chroma]
         sx, sy, depth, dt = _y4m_format(fmt)
-        if w is None or h is None or w < 1 or h < 1:
-            raise ValueError(f"{path}: the header gives no frame size (W, H)")
         if w % sx or h % sy:
             raise ValueError(f"{path}: odd size {w} x {h}; a C{chroma} frame with an odd side on a subsampled axis has no packed form")
         rows = h + 2 * h // (sx * sy)
@@ -1123,6 +1013,33 @@ def read_y4m_planes(path, max_frames=None):
     native = np.dtype(dt.type)                                                # (the words in host order)
     arr = np.stack(frames).reshape(len(frames), rows, w).astype(native) if frames else np.zeros((0, rows, w), native)
     return torch.from_numpy(arr.copy()), dict(width=w, height=h, fps=fps, siting=siting, range=rng, format=fmt, depth=depth)
+
+
+def read_y4m_header(path) -> str:
+    """The chroma tag of a YUV4MPEG2 file's header ('420jpeg' where it has none).  ValueError for a file whose header no reader here takes."""
+    with open(path, "rb") as fh:
+        return _y4m_header(fh, path)[3]
+
+
+def read_y4m(path, max_frames=None):
+    """A YUV4MPEG2 file of progressive 8-bit 4:2:0 frames -> (frames (T, 3 h / 2, w) uint8 tensor, packed I420 as the file holds them; info =
+    dict(width, height, fps=(num, den), siting, range)).  C420jpeg and no C tag: siting 'center'; C420mpeg2 and C420: 'left'.
+    XCOLORRANGE=FULL | LIMITED: range 'full' | 'limited', absent 'limited'.  ValueError that names the tag or the fact for any other chroma
+    tag, interlaced material (It / Ib / Im), an odd size and a truncated frame.  `max_frames`: stop after that many."""
+    frames, info = _read_y4m(path, max_frames, _Y4M_SITING, "8-bit 4:2:0 only: C420jpeg, C420mpeg2, C420")
+    del info["format"], info["depth"]
+    return frames, info
+
+
+def read_y4m_planes(path, max_frames=None):
+    """A YUV4MPEG2 file of progressive frames, 8 to 12 bits, 4:2:0 / 4:2:2 / 4:4:4 -> (frames (T, rows, w) in the file's own arrangement --
+    the luma rows, then the u plane and the v plane: what ops.yuv_planes takes apart (ops.yuv420_planes for 'i420') -- uint8, or uint16
+    from the file's little-endian words; info = read_y4m's keys plus format (an ops.YUV_PIXEL_FORMATS name, or 'i420') and depth).
+    C420jpeg, C420mpeg2, C420 and no C tag as read_y4m reads them; C422, C444; C420p10, C420p12, C422p10, C422p12, C444p10, C444p12, siting
+    'left'.  ValueError that names the tag or the fact for any other chroma tag (Cmono*, C411, C444alpha, C420paldv, ..), interlaced
+    material, a side that is odd on a subsampled axis and a truncated frame.  `max_frames`: stop after that many."""
+    return _read_y4m(path, max_frames, _Y4M_PLANES, "planar 4:2:0, 4:2:2 and 4:4:4 at 8, 10 or 12 bits: "
+                     + ", ".join("C" + t for t in _Y4M_PLANES))
 
 
 def write_y4m_planes(path, frames, format: str = "i420", fps=(30, 1), siting: str = "left", range: str = "limited") -> None:
@@ -1150,3 +1067,12 @@ def write_y4m_planes(path, frames, format: str = "i420", fps=(30, 1), siting: st
         for frame in f:
             fh.write(b"FRAME\n")
             fh.write(np.ascontiguousarray(frame, dt).tobytes())
+
+
+def write_y4m(path, frames, fps=(30, 1), siting: str = "left", range: str = "limited") -> None:
+    """Packed I420 frames (T, 3 h / 2, w) uint8 (tensor or array) -> a YUV4MPEG2 file: write_y4m_planes of 'i420' -- progressive, square
+    pixels, C420mpeg2 ('left') or C420jpeg ('center'), XCOLORRANGE=LIMITED | FULL.  ValueError for anything else."""
+    f = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if f.ndim != 3 or f.dtype != np.uint8 or f.shape[1] % 3 or f.shape[2] % 2:
+        raise ValueError(f"write_y4m: packed I420 frames (T, 3 h / 2, w) uint8 with h and w even, got {f.dtype} {f.shape}")
+    write_y4m_planes(path, f, "i420", fps, siting, range)

@@ -1370,8 +1370,7 @@ def parse_input(spec) -> Optional[InputConfig]:
         matrix = spec.pop("matrix", None if typ in ops.YUV_PIXEL_FORMATS else "bt601")
         rng, siting = spec.pop("range", "limited"), spec.pop("siting", "left")
         if "layout" in spec:
-            shape = ops._packed_shape(typ) if typ in ops.YUV_PIXEL_FORMATS else "(T, 3 h0 / 2, w0)"
-            raise ValueError(f"test_cfg.input: layout= belongs to type='rgb8'; {typ!r} frames are packed {shape}")
+            raise ValueError(f"test_cfg.input: layout= belongs to type='rgb8'; {typ!r} frames are packed {ops._packed_shape(typ)}")
         if spec:
             raise ValueError(f"test_cfg.input: unknown key(s) {sorted(spec)} (type, size, matrix, range, siting)")
         if matrix is None:

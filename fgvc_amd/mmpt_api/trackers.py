@@ -87,10 +87,8 @@ _RAW_DTYPES = (torch.uint8, torch.uint16)      # what test_cfg.input converts: b
 
 def _packed_desc(ic, lead: str) -> str:
     """'uint8 nv12 frames of shape (1, T, 3 h0 / 2, w0)' and its kin, for the refusals of a misshapen packed clip."""
-    if ic.type in ops.YUV_PIXEL_FORMATS:
-        dt = str(ops.YUV_PIXEL_FORMATS[ic.type][5]).replace("torch.", "")
-        return f"{dt} {ic.type} frames of shape ({lead}{ops._packed_shape(ic.type)[1:]}"
-    return f"uint8 {ic.type} frames of shape ({lead}T, 3 h0 / 2, w0)"
+    dt = str(engine.input_dtype(ic.type)).replace("torch.", "")
+    return f"{dt} {ic.type} frames of shape ({lead}{ops._packed_shape(ic.type)[1:]}"
 
 
 class LabelSession:
@@ -466,13 +464,12 @@ class VanillaTracker(BaseTracker):
         """Packed frames of test_cfg.input's type -> their plane views (y, u, v): NV12 / I420 (T, 3 h0 / 2, w0), an ops.YUV_PIXEL_FORMATS
         type (T, 3 h0 / 2 | 2 h0 | 3 h0, w0).  A shape that is no packed frame is a ValueError that states the expected one."""
         lead = "1, " if name == "rgbs" else "1, 1, "
+        nv12_i420 = ic.type in ops.YUV_FORMATS
         try:
-            return ops.yuv_planes(packed, ic.type) if ic.type in ops.YUV_PIXEL_FORMATS else ops.yuv420_planes(packed, ic.type)
+            return (ops.yuv420_planes if nv12_i420 else ops.yuv_planes)(packed, ic.type)
         except ValueError as e:
-            if ic.type in ops.YUV_PIXEL_FORMATS:
-                raise ValueError(f"{name}: {_packed_desc(ic, lead)}, got the frames {tuple(packed.shape)} ({e})") from None
-            raise ValueError(f"{name}: uint8 {ic.type} frames of shape ({lead}T, 3 h0 / 2, w0) with h0 and w0 even, got the frames "
-                             f"{tuple(packed.shape)} ({e})") from None
+            even = " with h0 and w0 even" if nv12_i420 else ""
+            raise ValueError(f"{name}: {_packed_desc(ic, lead)}{even}, got the frames {tuple(packed.shape)} ({e})") from None
 
     def _planes_to_lab(self, ic, planes, size, pad=(0, 0, 0, 0)) -> torch.Tensor:
         """_yuv_planes' views -> (T, 3, hp, wp): ops.yuv_frames_to_lab for NV12 / I420, ops.yuv_planes_to_lab with the format's depth, shift

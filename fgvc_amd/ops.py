@@ -1675,6 +1675,22 @@ def softmap_readout(bank: Optional[torch.Tensor], heat: torch.Tensor, Hf: int, W
 INPUT_LAYOUTS = ("thwc", "tchw")
 
 
+def _out(out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    """A fresh tensor, or the caller's `out` where it is a contiguous one of that shape, dtype and device."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous {str(dtype)[6:]} tensor of shape {tuple(shape)} on {device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def _lab_out(T: int, h0: int, w0: int, size, pad, out, device):
+    """`size`, `pad`, `out` of the Lab calls -> (h, w, (left, right, top, bottom), the (T, 3, hp, wp) f32 tensor to write)."""
+    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
+    left, right, top, bottom = (int(p) for p in pad)
+    return h, w, (left, right, top, bottom), _out(out, (T, 3, top + h + bottom, left + w + right), torch.float32, device)
+
+
 def frames_to_lab(frames_u8: torch.Tensor, size: Optional[Tuple[int, int]] = None, pad: Tuple[int, int, int, int] = (0, 0, 0, 0),
                   layout: str = "thwc", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """uint8 RGB frames (T, h0, w0, 3) ('thwc') or (T, 3, h0, w0) ('tchw') -> (T, 3, hp, wp) f32: per frame exactly
@@ -1694,131 +1710,22 @@ def frames_to_lab(frames_u8: torch.Tensor, size: Optional[Tuple[int, int]] = Non
     T, h0, w0, ch = f.shape
     if ch != 3:
         raise ValueError(f"frames_u8: 3 channels (RGB) in layout {layout!r}, got {ch} (shape {tuple(frames_u8.shape)})")
-    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
-    left, right, top, bottom = (int(p) for p in pad)
-    shape = (T, 3, top + h + bottom, left + w + right)
-    if out is None:
-        out = torch.empty(shape, device=f.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != f.device or not out.is_contiguous():
-        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {f.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    h, w, pad, out = _lab_out(T, h0, w0, size, pad, out, f.device)
     if T == 0:
         return out
     st, sy, sx, sc = f.stride()                                                       # (uint8: elements are bytes)
-    _lib.call("fgvc_frames_rgb8_to_lab_f32", _ptr(f), T, h0, w0, st, sy, sx, sc, h, w, left, right, top, bottom, _ptr(out), _stream(f))
+    _lib.call("fgvc_frames_rgb8_to_lab_f32", _ptr(f), T, h0, w0, st, sy, sx, sc, h, w, *pad, _ptr(out), _stream(f))
     return out
 
 
-# ---- the input stage for 8-bit YUV 4:2:0 video: NV12 / I420 -> the network input, or RGB bytes --------------------
+# ---- the input stage for Y'CbCr video: planes -> the network input, or RGB bytes (DESIGN.md sections 19 and 26) ---------------------------
+# Two families of entries over one checker and one splitter: yuv_frames_* take 8-bit 4:2:0 planes (YUV_FORMATS) to the fixed-format
+# kernels of fgvc_frames_yuv420_*; yuv_planes_* take 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4 (YUV_PIXEL_FORMATS) to fgvc_frames_yuvp_*.
 
 YUV_FORMATS = ("nv12", "i420")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # (Kr, Kb)
-YUV_RANGES = {"limited": (16.0, 255.0 / 219.0, 255.0 / 224.0), "full": (0.0, 1.0, 1.0)}    # (y_off, cy, sc)
+YUV_RANGES = {"limited": (16.0, 255.0 / 219.0, 255.0 / 224.0), "full": (0.0, 1.0, 1.0)}    # (y_off, cy, sc) at 8 bits
 YUV_SITINGS = ("left", "center")                                            # = FGVC_YUV_SITING_LEFT, FGVC_YUV_SITING_CENTER
-
-
-def yuv_coefficients(matrix: str = "bt601", range: str = "limited") -> Tuple[float, float, float, float, float, float]:
-    """(y_off, cy, crv, cgu, cgv, cbu) of R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with yy = cy (Y - y_off), cb = U - 128,
-    cr = V - 128: computed in float64 from Kr, Kb of `matrix` ('bt601' | 'bt709') and the scales of `range` ('limited': 16..235 / 16..240;
-    'full'), as Python floats.  The kernels take them rounded to f32 once."""
-    if matrix not in YUV_MATRICES:
-        raise ValueError(f"matrix={matrix!r}: one of {tuple(YUV_MATRICES)}")
-    if range not in YUV_RANGES:
-        raise ValueError(f"range={range!r}: one of {tuple(YUV_RANGES)}")
-    kr, kb = YUV_MATRICES[matrix]
-    kg = 1.0 - kr - kb
-    y_off, cy, sc = YUV_RANGES[range]
-    return (y_off, cy, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
-
-
-def yuv420_planes(frames: torch.Tensor, fmt: str):
-    """Packed 4:2:0 frames (T, 3 h0 / 2, w0) uint8 -- h0 luma rows, then NV12's h0 / 2 rows of interleaved (u, v) pairs or I420's u plane
-    and v plane -- -> the views (y (T, h0, w0), u, v (T, h0 / 2, w0 / 2)); nothing is copied.  ValueError unless the rows are a multiple of
-    3 and h0, w0 are even (an odd frame has no packed form: pass its planes)."""
-    if fmt not in YUV_FORMATS:
-        raise ValueError(f"fmt={fmt!r}: one of {YUV_FORMATS}")
-    if frames.dim() != 3:
-        raise ValueError(f"frames: packed {fmt} frames of shape (T, 3 h0 / 2, w0), got {tuple(frames.shape)}")
-    T, rows, w0 = frames.shape
-    h0 = rows // 3 * 2
-    if rows % 3 or h0 % 2 or w0 % 2 or h0 == 0 or w0 == 0:
-        raise ValueError(f"frames: packed {fmt} frames of shape (T, 3 h0 / 2, w0) with h0 and w0 even, got {tuple(frames.shape)}")
-    y, c = frames[:, :h0], frames[:, h0:]
-    if fmt == "nv12":
-        uv = c.unflatten(2, (w0 // 2, 2))                                             # (T, h0 / 2, w0 / 2, 2)
-        return y, uv[..., 0], uv[..., 1]
-    if T > 0 and (c.stride(1), c.stride(2)) != (w0, 1):                               # (a row of the u plane is half a packed row)
-        raise ValueError(f"frames: the bytes of a packed i420 frame must be adjacent (strides (.., {w0}, 1)), got {frames.stride()}; "
-                         "pass the planes of a crop instead")
-    pl = c.as_strided((T, 2, h0 // 2, w0 // 2), (c.stride(0), (h0 // 2) * (w0 // 2), w0 // 2, 1), c.storage_offset())
-    return y, pl[:, 0], pl[:, 1]
-
-
-def _yuv_args(y, u, v, matrix, range, siting):
-    """The checks the two YUV calls share -> (T, h0, w0, the kernel's stride and coefficient arguments)."""
-    for name, p in (("y", y), ("u", u), ("v", v)):
-        if not p.is_cuda:
-            raise _lib.FgvcHipError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
-        if p.dtype != torch.uint8:
-            raise TypeError(f"{name}: expected torch.uint8, got {p.dtype}")
-        if p.dim() != 3:
-            raise ValueError(f"{name}: 3 dimensions ({'T, h0, w0' if name == 'y' else 'T, (h0 + 1) // 2, (w0 + 1) // 2'}), got {tuple(p.shape)}")
-    if siting not in YUV_SITINGS:
-        raise ValueError(f"siting={siting!r}: one of {YUV_SITINGS}")
-    coef = yuv_coefficients(matrix, range)
-    T, h0, w0 = y.shape
-    want = (T, (h0 + 1) // 2, (w0 + 1) // 2)
-    if tuple(u.shape) != want or tuple(v.shape) != want:
-        raise ValueError(f"u, v: chroma planes of shape {want} for luma {tuple(y.shape)}, got {tuple(u.shape)} and {tuple(v.shape)}")
-    if u.device != y.device or v.device != y.device:
-        raise ValueError(f"y, u, v: one device, got {y.device}, {u.device}, {v.device}")
-    if w0 > 1 and y.stride(2) != 1:
-        raise ValueError(f"y: luma columns must be adjacent (last stride 1), got strides {y.stride()}")
-    if any(n > 1 and su != sv for n, su, sv in zip(want, u.stride(), v.stride())):    # (an axis of one sample: its stride is never used)
-        raise ValueError(f"u, v: the same strides (the kernel takes one set for both planes), got {u.stride()} and {v.stride()}")
-    return T, h0, w0, (y.stride(0), y.stride(1), u.stride(0), u.stride(1), u.stride(2)), coef, YUV_SITINGS.index(siting)
-
-
-def yuv_frames_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size: Optional[Tuple[int, int]] = None,
-                      pad: Tuple[int, int, int, int] = (0, 0, 0, 0), matrix: str = "bt601", range: str = "limited", siting: str = "left",
-                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """8-bit YUV 4:2:0 planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> (T, 3, hp, wp) f32: per frame exactly
-    datasets.preprocess_yuv420_frames (chroma bilinear at the luma pixel by `siting`; R'G'B' by `matrix` and `range`, unclamped; then
-    frames_to_lab's steps) at (top, left) of a border of exact zeros -- one launch of fgvc_frames_yuv420_to_lab_f32.  The planes are read
-    through their strides (yuv420_planes' views of packed NV12 / I420 frames, crops, time slices): nothing is copied; the luma columns
-    must be adjacent and u, v share their strides.  NV21 / YV12: pass the planes swapped.  `size`, `pad`, `out`: as frames_to_lab's."""
-    T, h0, w0, strides, coef, sit = _yuv_args(y, u, v, matrix, range, siting)
-    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
-    left, right, top, bottom = (int(p) for p in pad)
-    shape = (T, 3, top + h + bottom, left + w + right)
-    if out is None:
-        out = torch.empty(shape, device=y.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
-        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if T == 0:
-        return out
-    _lib.call("fgvc_frames_yuv420_to_lab_f32", _ptr(y), _ptr(u), _ptr(v), T, h0, w0, *strides, *coef, sit, h, w, left, right, top, bottom,
-              _ptr(out), _stream(y))
-    return out
-
-
-def yuv_frames_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
-                       siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The same planes -> (T, h0, w0, 3) uint8 RGB: rint (half to even) of the unclamped R'G'B' clamped to [0, 255], exactly
-    datasets.yuv420_to_rgb8 -- one launch of fgvc_frames_yuv420_to_rgb8.  What render_frames draws on.  `out`: a contiguous uint8 tensor
-    of that shape on the planes' device."""
-    T, h0, w0, strides, coef, sit = _yuv_args(y, u, v, matrix, range, siting)
-    shape = (T, h0, w0, 3)
-    if out is None:
-        out = torch.empty(shape, device=y.device, dtype=torch.uint8)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != y.device or not out.is_contiguous():
-        raise ValueError(f"out: a contiguous uint8 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if T == 0:
-        return out
-    _lib.call("fgvc_frames_yuv420_to_rgb8", _ptr(y), _ptr(u), _ptr(v), T, h0, w0, *strides, *coef, sit, _ptr(out), _stream(y))
-    return out
-
-
-# ---- the input stage for planar and semi-planar Y'CbCr at 8..16 bits, 4:2:0 / 4:2:2 / 4:4:4 (DESIGN.md section 26) -------------------------
 
 # ffmpeg's name -> (layout 'planar' | 'semi', sub_x, sub_y, depth, shift, dtype); 16-bit samples are host-endian (little-endian) words.
 # 'nv12' and 'i420' stay in YUV_FORMATS and go through the 8-bit 4:2:0 entries.
@@ -1830,15 +1737,17 @@ YUV_PIXEL_FORMATS = {
     "yuv422p": ("planar", 2, 1, 8, 0, torch.uint8), "yuv444p": ("planar", 1, 1, 8, 0, torch.uint8),
     "nv16": ("semi", 2, 1, 8, 0, torch.uint8),
 }
+_YUV420_FORMATS = {"nv12": ("semi", 2, 2, 8, 0, torch.uint8), "i420": ("planar", 2, 2, 8, 0, torch.uint8)}     # YUV_FORMATS in that table's words
 _YUV_DTYPES = (torch.uint8, torch.uint16)
 
 
 def yuv_coefficients_depth(matrix: str = "bt601", range: str = "limited",
                            depth: int = 8) -> Tuple[float, float, float, float, float, float, float]:
-    """(y_off, cy, c_off, crv, cgu, cgv, cbu) for samples of `depth` bits (8..16), R'G'B' on the 0..255 scale: with s = 2^(depth - 8),
-    'limited' y_off = 16 s, cy = 255 / (219 s), c_off = 128 s, chroma scale 255 / (224 s); 'full' y_off = 0, cy = 255 / (2^depth - 1),
-    c_off = 2^(depth - 1), chroma scale 255 / (2^depth - 1).  Computed in float64 as Python floats; the kernels take them rounded to f32 once.
-    At depth 8 they are yuv_coefficients' numbers around c_off = 128; the limited-range ones at any depth differ from those by powers of two."""
+    """(y_off, cy, c_off, crv, cgu, cgv, cbu) of R = yy + crv cr, G = (yy + cgu cb) + cgv cr, B = yy + cbu cb with yy = cy (Y - y_off),
+    cb = U - c_off, cr = V - c_off for samples of `depth` bits (8..16), R'G'B' on the 0..255 scale: from Kr, Kb of `matrix` ('bt601' |
+    'bt709') and, with s = 2^(depth - 8), 'limited' y_off = 16 s, cy = 255 / (219 s), c_off = 128 s, chroma scale 255 / (224 s); 'full'
+    y_off = 0, cy = 255 / (2^depth - 1), c_off = 2^(depth - 1), chroma scale 255 / (2^depth - 1).  Computed in float64 as Python floats; the
+    kernels take them rounded to f32 once.  The limited-range ones at any depth differ from the 8-bit ones by powers of two."""
     if matrix not in YUV_MATRICES:
         raise ValueError(f"matrix={matrix!r}: one of {tuple(YUV_MATRICES)}")
     if range not in YUV_RANGES:
@@ -1857,39 +1766,40 @@ def yuv_coefficients_depth(matrix: str = "bt601", range: str = "limited",
     return (y_off, cy, c_off, 2.0 * (1.0 - kr) * sc, -2.0 * kb * (1.0 - kb) / kg * sc, -2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
 
 
+def yuv_coefficients(matrix: str = "bt601", range: str = "limited") -> Tuple[float, float, float, float, float, float]:
+    """(y_off, cy, crv, cgu, cgv, cbu): yuv_coefficients_depth at 8 bits without its c_off = 128, what the 8-bit 4:2:0 entries take."""
+    c = yuv_coefficients_depth(matrix, range, 8)
+    return c[:2] + c[3:]
+
+
 def yuv_packed_rows(fmt: str, h0: int) -> int:
     """Rows of a packed `fmt` frame of h0 luma rows: h0 (1 + 2 / (sub_x sub_y))."""
     _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
     return h0 + 2 * h0 // (sx * sy)
 
 
-def yuv_packed_height(fmt: str, rows: int) -> int:
-    """The luma rows h0 of a packed `fmt` frame of `rows` rows (3 h0 / 2, 2 h0 or 3 h0 rows), or -1 where no whole h0 gives them."""
-    _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
-    k = sx * sy
+def _packed_height(rows: int, k: int) -> int:
     return rows * k // (k + 2) if rows * k % (k + 2) == 0 else -1
 
 
-def _packed_shape(fmt: str) -> str:
+def yuv_packed_height(fmt: str, rows: int) -> int:
+    """The luma rows h0 of a packed `fmt` frame of `rows` rows (3 h0 / 2, 2 h0 or 3 h0 rows), or -1 where no whole h0 gives them."""
     _, sx, sy = YUV_PIXEL_FORMATS[fmt][:3]
+    return _packed_height(rows, sx * sy)
+
+
+def _packed_shape(fmt: str) -> str:
+    _, sx, sy = (_YUV420_FORMATS.get(fmt) or YUV_PIXEL_FORMATS[fmt])[:3]
     return {4: "(T, 3 h0 / 2, w0)", 2: "(T, 2 h0, w0)", 1: "(T, 3 h0, w0)"}[sx * sy]
 
 
-def yuv_planes(frames: torch.Tensor, fmt: str):
-    """Packed frames (T, rows, w0) of a YUV_PIXEL_FORMATS name, in its dtype -- h0 luma rows, then the chroma as the file's samples follow:
-    a planar format's u plane and v plane, a semi-planar one's rows of interleaved (u, v) pairs; rows = h0 (1 + 2 / (sub_x sub_y)) -- -> the
-    views (y (T, h0, w0), u, v (T, h0 / sub_y, w0 / sub_x)); nothing is copied.  TypeError for another dtype; ValueError unless the rows are
-    whole, the sides even on every subsampled axis and (for subsampled planar chroma) a frame's samples adjacent."""
-    if fmt not in YUV_PIXEL_FORMATS:
-        raise ValueError(f"fmt={fmt!r}: one of {tuple(YUV_PIXEL_FORMATS)}")
-    layout, sx, sy, _, _, dtype = YUV_PIXEL_FORMATS[fmt]
-    if frames.dtype != dtype:
-        raise TypeError(f"frames: expected {dtype} for {fmt}, got {frames.dtype}")
+def _split_planes(frames: torch.Tensor, fmt: str, layout: str, sx: int, sy: int):
+    """Packed frames (T, rows, w0) -> the views (y, u, v): what yuv420_planes and yuv_planes share."""
     shape = _packed_shape(fmt)
     if frames.dim() != 3:
         raise ValueError(f"frames: packed {fmt} frames of shape {shape}, got {tuple(frames.shape)}")
     T, rows, w0 = frames.shape
-    h0 = yuv_packed_height(fmt, rows)
+    h0 = _packed_height(rows, sx * sy)
     if h0 <= 0 or w0 == 0 or h0 % sy or w0 % sx:
         even = {(2, 2): " with h0 and w0 even", (2, 1): " with w0 even", (1, 1): ""}[(sx, sy)]
         raise ValueError(f"frames: packed {fmt} frames of shape {shape}{even}, got {tuple(frames.shape)}")
@@ -1907,13 +1817,36 @@ def yuv_planes(frames: torch.Tensor, fmt: str):
     return y, pl[:, 0], pl[:, 1]
 
 
-def _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting):
-    """The checks the two yuv_planes_* calls share -> (T, h0, w0, the kernel's format, stride and coefficient arguments)."""
+def yuv420_planes(frames: torch.Tensor, fmt: str):
+    """Packed 4:2:0 frames (T, 3 h0 / 2, w0) uint8 -- h0 luma rows, then NV12's h0 / 2 rows of interleaved (u, v) pairs or I420's u plane
+    and v plane -- -> the views (y (T, h0, w0), u, v (T, h0 / 2, w0 / 2)); nothing is copied.  ValueError unless the rows are a multiple of
+    3 and h0, w0 are even (an odd frame has no packed form: pass its planes)."""
+    if fmt not in YUV_FORMATS:
+        raise ValueError(f"fmt={fmt!r}: one of {YUV_FORMATS}")
+    return _split_planes(frames, fmt, *_YUV420_FORMATS[fmt][:3])
+
+
+def yuv_planes(frames: torch.Tensor, fmt: str):
+    """Packed frames (T, rows, w0) of a YUV_PIXEL_FORMATS name, in its dtype -- h0 luma rows, then the chroma as the file's samples follow:
+    a planar format's u plane and v plane, a semi-planar one's rows of interleaved (u, v) pairs; rows = h0 (1 + 2 / (sub_x sub_y)) -- -> the
+    views (y (T, h0, w0), u, v (T, h0 / sub_y, w0 / sub_x)); nothing is copied.  TypeError for another dtype; ValueError unless the rows are
+    whole, the sides even on every subsampled axis and (for subsampled planar chroma) a frame's samples adjacent."""
+    if fmt not in YUV_PIXEL_FORMATS:
+        raise ValueError(f"fmt={fmt!r}: one of {tuple(YUV_PIXEL_FORMATS)}")
+    layout, sx, sy, _, _, dtype = YUV_PIXEL_FORMATS[fmt]
+    if frames.dtype != dtype:
+        raise TypeError(f"frames: expected {dtype} for {fmt}, got {frames.dtype}")
+    return _split_planes(frames, fmt, layout, sx, sy)
+
+
+def _yuv_plane_args(y, u, v, depth, shift, subsampling, matrix, range, siting, dtypes=_YUV_DTYPES):
+    """The checks every YUV input call shares -> the kernel's arguments before (T, h0, w0) -- the format -- and after them: the strides, the
+    seven coefficients and the siting.  `dtypes`: what the planes may be (the 8-bit 4:2:0 calls: uint8 alone, at depth 8, shift 0, (2, 2))."""
     for name, p in (("y", y), ("u", u), ("v", v)):
         if not p.is_cuda:
             raise _lib.FgvcHipError(f"{name} must be on the GPU (fgvc_amd has no CPU path)")
-        if p.dtype not in _YUV_DTYPES:
-            raise TypeError(f"{name}: expected torch.uint8 or torch.uint16, got {p.dtype}")
+        if p.dtype not in dtypes:
+            raise TypeError(f"{name}: expected {' or '.join(str(d) for d in dtypes)}, got {p.dtype}")
         if p.dim() != 3:
             raise ValueError(f"{name}: 3 dimensions ({'T, h0, w0' if name == 'y' else 'T, ceil(h0 / sub_y), ceil(w0 / sub_x)'}), got {tuple(p.shape)}")
     if u.dtype != y.dtype or v.dtype != y.dtype:
@@ -1942,8 +1875,50 @@ def _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting):
         raise ValueError(f"y: luma columns must be adjacent (last stride 1), got strides {y.stride()}")
     if any(n > 1 and su != sv for n, su, sv in zip(want, u.stride(), v.stride())):    # (an axis of one sample: its stride is never used)
         raise ValueError(f"u, v: the same strides (the kernel takes one set for both planes), got {u.stride()} and {v.stride()}")
-    fmt = (y.element_size(), depth, shift, sx, sy)
-    return T, h0, w0, fmt, (y.stride(0), y.stride(1), u.stride(0), u.stride(1), u.stride(2)), coef, YUV_SITINGS.index(siting)
+    return (y.element_size(), depth, shift, sx, sy), (y.stride(0), y.stride(1), u.stride(0), u.stride(1), u.stride(2), *coef, YUV_SITINGS.index(siting))
+
+
+def _yuv420_plane_args(y, u, v, matrix, range, siting):
+    """-> what fgvc_frames_yuv420_* take after (T, h0, w0): no format, and the tail without c_off."""
+    _, tail = _yuv_plane_args(y, u, v, 8, 0, (2, 2), matrix, range, siting, dtypes=(torch.uint8,))
+    return (), tail[:7] + tail[8:]
+
+
+def _planes_to_lab(entry: str, y, u, v, args, size, pad, out):
+    fmt, tail = args
+    T, h0, w0 = y.shape
+    h, w, pad, out = _lab_out(T, h0, w0, size, pad, out, y.device)
+    if T > 0:
+        _lib.call(entry, _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *tail, h, w, *pad, _ptr(out), _stream(y))
+    return out
+
+
+def _planes_to_rgb8(entry: str, y, u, v, args, out):
+    fmt, tail = args
+    T, h0, w0 = y.shape
+    out = _out(out, (T, h0, w0, 3), torch.uint8, y.device)
+    if T > 0:
+        _lib.call(entry, _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *tail, _ptr(out), _stream(y))
+    return out
+
+
+def yuv_frames_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, size: Optional[Tuple[int, int]] = None,
+                      pad: Tuple[int, int, int, int] = (0, 0, 0, 0), matrix: str = "bt601", range: str = "limited", siting: str = "left",
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """8-bit YUV 4:2:0 planes y (T, h0, w0), u, v (T, (h0 + 1) // 2, (w0 + 1) // 2) uint8 -> (T, 3, hp, wp) f32: per frame exactly
+    datasets.preprocess_yuv420_frames (chroma bilinear at the luma pixel by `siting`; R'G'B' by `matrix` and `range`, unclamped; then
+    frames_to_lab's steps) at (top, left) of a border of exact zeros -- one launch of fgvc_frames_yuv420_to_lab_f32.  The planes are read
+    through their strides (yuv420_planes' views of packed NV12 / I420 frames, crops, time slices): nothing is copied; the luma columns
+    must be adjacent and u, v share their strides.  NV21 / YV12: pass the planes swapped.  `size`, `pad`, `out`: as frames_to_lab's."""
+    return _planes_to_lab("fgvc_frames_yuv420_to_lab_f32", y, u, v, _yuv420_plane_args(y, u, v, matrix, range, siting), size, pad, out)
+
+
+def yuv_frames_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, matrix: str = "bt601", range: str = "limited",
+                       siting: str = "left", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The same planes -> (T, h0, w0, 3) uint8 RGB: rint (half to even) of the unclamped R'G'B' clamped to [0, 255], exactly
+    datasets.yuv420_to_rgb8 -- one launch of fgvc_frames_yuv420_to_rgb8.  What render_frames draws on.  `out`: a contiguous uint8 tensor
+    of that shape on the planes' device."""
+    return _planes_to_rgb8("fgvc_frames_yuv420_to_rgb8", y, u, v, _yuv420_plane_args(y, u, v, matrix, range, siting), out)
 
 
 def yuv_planes_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0,
@@ -1956,19 +1931,8 @@ def yuv_planes_to_lab(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: 
     through their strides (yuv_planes' views of packed frames, crops, time slices): nothing is copied; the luma columns must be adjacent
     and u, v share their strides.  `siting` places the chroma of a horizontally subsampled format only.  Swapped chroma (NV21-style): pass the
     planes swapped.  `size`, `pad`, `out`: as frames_to_lab's."""
-    T, h0, w0, fmt, strides, coef, sit = _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
-    h, w = (h0, w0) if size is None else (int(size[0]), int(size[1]))
-    left, right, top, bottom = (int(p) for p in pad)
-    shape = (T, 3, top + h + bottom, left + w + right)
-    if out is None:
-        out = torch.empty(shape, device=y.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != y.device or not out.is_contiguous():
-        raise ValueError(f"out: a contiguous float32 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if T == 0:
-        return out
-    _lib.call("fgvc_frames_yuvp_to_lab_f32", _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *strides, *coef, sit, h, w, left, right, top, bottom,
-              _ptr(out), _stream(y))
-    return out
+    args = _yuv_plane_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    return _planes_to_lab("fgvc_frames_yuvp_to_lab_f32", y, u, v, args, size, pad, out)
 
 
 def yuv_planes_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth: int = 8, shift: int = 0,
@@ -1976,16 +1940,8 @@ def yuv_planes_to_rgb8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, depth:
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The same planes -> (T, h0, w0, 3) uint8 RGB: rint (half to even) of the unclamped R'G'B' clamped to [0, 255], exactly
     datasets.yuv_to_rgb8 -- one launch of fgvc_frames_yuvp_to_rgb8.  `out`: a contiguous uint8 tensor of that shape on the planes' device."""
-    T, h0, w0, fmt, strides, coef, sit = _yuvp_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
-    shape = (T, h0, w0, 3)
-    if out is None:
-        out = torch.empty(shape, device=y.device, dtype=torch.uint8)
-    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != y.device or not out.is_contiguous():
-        raise ValueError(f"out: a contiguous uint8 tensor of shape {shape} on {y.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if T == 0:
-        return out
-    _lib.call("fgvc_frames_yuvp_to_rgb8", _ptr(y), _ptr(u), _ptr(v), *fmt, T, h0, w0, *strides, *coef, sit, _ptr(out), _stream(y))
-    return out
+    args = _yuv_plane_args(y, u, v, depth, shift, subsampling, matrix, range, siting)
+    return _planes_to_rgb8("fgvc_frames_yuvp_to_rgb8", y, u, v, args, out)
 
 
 # ---- the output stage for 8-bit YUV 4:2:0 video: RGB bytes -> NV12 / I420 (DESIGN.md section 20) ------------------------------------------

@@ -413,7 +413,8 @@ int fgvc_frames_rgb8_to_lab_f32(const uint8_t* frames, int T, int h0, int w0, in
  *           coordinates, / 255 and clamp, sRGB -> Lab, normalise, zero border); out as there.  The sRGB transfer is evaluated per value.
  *   ..._to_rgb8: rint (half to even) of clamp(R'G'B', 0, 255); out [T][h0][w0][3] bytes, contiguous.
  * FGVC_ERR_INVALID_ARG for a null pointer, a non-positive size, a negative pad, a siting other than the two, and a shape beyond the launch
- * grid (as fgvc_frames_rgb8_to_lab_f32; source sides below 2^30) -- all before any launch.  No workspace, no atomics, no LDS. */
+ * grid (as fgvc_frames_rgb8_to_lab_f32; source sides below 2^30) -- all before any launch.  No workspace, no atomics, no LDS.  These two
+ * entries launch the fixed-format instances of csrc/input_yuv.hip's kernels (nothing of the format is an argument). */
 #define FGVC_YUV_SITING_LEFT 0
 #define FGVC_YUV_SITING_CENTER 1
 int fgvc_frames_yuv420_to_lab_f32(const uint8_t* y, const uint8_t* u, const uint8_t* v, int T, int h0, int w0, int64_t y_stride_t,
@@ -433,7 +434,8 @@ int fgvc_frames_yuv420_to_rgb8(const uint8_t* y, const uint8_t* u, const uint8_t
  *           A subsampled axis is interpolated as above (vertically between the rows, horizontally by `siting`); a full-resolution axis takes
  *           the sample at the luma index, unchanged (`siting` is not used where sub_x = 1).
  *   Decode: yy = cy (Y - y_off), cb = U' - c_off, cr = V' - c_off, then as above: the seven coefficients come by value
- *           (ops.yuv_coefficients_depth).  At depth 8 with sub_x = sub_y = 2 the outputs equal the 8-bit entries' bit for bit.
+ *           (ops.yuv_coefficients_depth).  At depth 8 with sub_x = sub_y = 2 the outputs equal the 8-bit entries' bit for bit -- from the
+ *           run-time-format instances of the same kernels (csrc/input_yuv.hip): the entry chooses the instance, the values never do.
  * FGVC_ERR_INVALID_ARG as above, and for sample_bytes other than 1 or 2, a depth outside 8..16, depth + shift beyond the sample's bits, a
  * negative shift, sub_x / sub_y other than 1 or 2, a 16-bit plane at an odd address -- all before any launch.  No workspace, no atomics, no
  * LDS. */

@@ -331,15 +331,18 @@ def test_yuv_symbols_declared_and_validate_their_arguments():
 
 
 def test_yuv_kernels_use_no_scratch():
-    """The three kernels (Lab: resize and same size; bytes) in the code-object notes of the built library: no scratch memory, no spilled
-    register, no LDS."""
+    """The three fixed-format kernels (Yuv420 -- Lab: resize and same size; bytes) in the code-object notes of the built library: no scratch
+    memory, no spilled register, no LDS, and no more registers than they had as a file of their own (153 / 72 / 65 VGPRs: the next
+    occupancy steps)."""
     notes = _tool("kernel_notes").kernel_notes()
-    lab = {k: v for k, v in notes.items() if "frames_yuv420_to_lab_kernel" in k}
-    rgb = {k: v for k, v in notes.items() if "frames_yuv420_to_rgb8_kernel" in k}
+    lab = {k: v for k, v in notes.items() if "frames_yuv_to_lab_kernel" in k and "Yuv420" in k}
+    rgb = {k: v for k, v in notes.items() if "frames_yuv_to_rgb8_kernel" in k and "Yuv420" in k}
     assert len(lab) == 2 and len(rgb) == 1, (sorted(lab), sorted(rgb))
     for k, v in {**lab, **rgb}.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, (k, v)
         assert v["group_segment_fixed_size"] == 0, (k, v)
+    resize, same = (next(v for k, v in lab.items() if flag in k) for flag in ("Lb1E", "Lb0E"))       # <Yuv420, RESIZE>
+    assert resize["vgpr_count"] <= 153 and same["vgpr_count"] <= 72 and next(iter(rgb.values()))["vgpr_count"] <= 65, (lab, rgb)
 
 
 # ---- the demo -----------------------------------------------------------------------------------------------------------------------------------

@@ -378,11 +378,11 @@ def test_y4m_planes_refusals(tmp_path):
 
 # ---- the library --------------------------------------------------------------------------------------------------------------------------------
 def test_yuvp_symbols_declared_and_validate_their_arguments():
-    """Both entry points are exported and listed in _lib.SIGNATURES, input_yuvp.hip is a build source, and every bad argument of the
-    header's list returns FGVC_ERR_INVALID_ARG with a message that names the entry point, before any launch (no GPU here: a launch would
-    fail with another code)."""
+    """Both entry points are exported and listed in _lib.SIGNATURES, input_yuv.hip (the one YUV input file) is a build source, and every
+    bad argument of the header's list returns FGVC_ERR_INVALID_ARG with a message that names the entry point, before any launch (no GPU
+    here: a launch would fail with another code)."""
     from fgvc_amd import _lib, build
-    assert "input_yuvp.hip" in build.SOURCES and "input_yuv.hip" in build.SOURCES
+    assert "input_yuv.hip" in build.SOURCES
     lib = _lib.load()
     p = C.c_void_p(4096)                     # never dereferenced: every call below is refused on the host
     coef = (64.0, 0.29, 512.0, 0.4, -0.1, -0.2, 0.5)
@@ -426,11 +426,11 @@ def test_yuvp_symbols_declared_and_validate_their_arguments():
 
 
 def test_yuvp_kernels_use_no_scratch():
-    """The six kernels (Lab: resize and same size, bytes; each for 8- and 16-bit words) in the code-object notes of the built library: no
-    scratch memory, no spilled register, no LDS."""
+    """The six run-time-format kernels (Yuvp -- Lab: resize and same size, bytes; each for 8- and 16-bit words) in the code-object notes of
+    the built library: no scratch memory, no spilled register, no LDS."""
     notes = _tool("kernel_notes").kernel_notes()
-    lab = {k: v for k, v in notes.items() if "frames_yuvp_to_lab_kernel" in k}
-    rgb = {k: v for k, v in notes.items() if "frames_yuvp_to_rgb8_kernel" in k}
+    lab = {k: v for k, v in notes.items() if "frames_yuv_to_lab_kernel" in k and "Yuvp" in k}
+    rgb = {k: v for k, v in notes.items() if "frames_yuv_to_rgb8_kernel" in k and "Yuvp" in k}
     assert len(lab) == 4 and len(rgb) == 2, (sorted(lab), sorted(rgb))
     for k, v in {**lab, **rgb}.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["sgpr_spill_count"] == 0, (k, v)

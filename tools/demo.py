@@ -92,43 +92,32 @@ def yuv_matrix_default(height: int) -> str:
 
 
 def load_y4m(a, dev):
-    """CLIP.y4m -> (packed I420 frames (T, 3 H / 2, W) uint8 on the device, their RGB bytes (T, H, W, 3) on the device,
-    test_cfg.input for them without its size)."""
-    from fgvc_amd import datasets, ops
-    if datasets.read_y4m_header(a.frames) not in datasets._Y4M_SITING:        # not 8-bit 4:2:0: 4:2:2 / 4:4:4, 10 or 12 bits
-        return load_y4m_planes(a, dev)
-    packed, info = datasets.read_y4m(a.frames)
-    if packed.shape[0] == 0:
-        raise ValueError(f"{a.frames}: no frames")
-    matrix = a.yuv_matrix or yuv_matrix_default(info["height"])
-    print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, siting {info['siting']}, {info['range']} range; matrix {matrix} "
-          f"({'--yuv-matrix' if a.yuv_matrix else 'by the height: the file does not say'})")
-    a.yuv_info = dict(info, matrix=matrix)
-    packed = packed.to(dev)
-    kw = dict(matrix=matrix, range=info["range"], siting=info["siting"])
-    rgb = ops.yuv_frames_to_rgb8(*ops.yuv420_planes(packed, "i420"), **kw)
-    return packed, rgb, dict(type="i420", **kw)
-
-
-def load_y4m_planes(a, dev):
-    """A CLIP.y4m whose C tag is not 8-bit 4:2:0 (C422, C444, C420p10, ..) -> what load_y4m returns: the packed frames as the file holds
-    them (uint8, or uint16 words) on the device, their RGB bytes by ops.yuv_planes_to_rgb8, test_cfg.input of the file's format."""
+    """CLIP.y4m -> (the packed frames as the file holds them -- I420 (T, 3 H / 2, W) uint8, or a planar ops.YUV_PIXEL_FORMATS arrangement in
+    uint8 / uint16 words for a C tag of 4:2:2, 4:4:4, 10 or 12 bits -- on the device, their RGB bytes (T, H, W, 3) on the device,
+    test_cfg.input of the file's format without its size)."""
     from fgvc_amd import datasets, ops
     packed, info = datasets.read_y4m_planes(a.frames)
     if packed.shape[0] == 0:
         raise ValueError(f"{a.frames}: no frames")
-    fmt = info["format"]
-    _, sx, sy, depth, shift, _ = ops.YUV_PIXEL_FORMATS[fmt]
+    fmt, depth = info.pop("format"), info.pop("depth")
+    what = f"siting {info['siting']}" if fmt == "i420" else f"{fmt} ({depth} bits)"
     matrix = a.yuv_matrix or yuv_matrix_default(info["height"])
-    print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, {fmt} ({depth} bits), {info['range']} range; matrix {matrix} "
+    print(f"{a.frames}: {packed.shape[0]} frames of {info['height']} x {info['width']}, {what}, {info['range']} range; matrix {matrix} "
           f"({'--yuv-matrix' if a.yuv_matrix else 'by the height: the file does not say'})")
     a.yuv_info = dict(info, matrix=matrix)
     packed = packed.to(dev)
-    kw = dict(matrix=matrix, range=info["range"])
-    if sx == 2:                                                               # (4:4:4 has no siting: test_cfg.input refuses the key)
-        kw["siting"] = info["siting"]
-    rgb = ops.yuv_planes_to_rgb8(*ops.yuv_planes(packed, fmt), depth, shift, (sx, sy), **kw)
+    kw = dict(matrix=matrix, range=info["range"], siting=info["siting"])
+    if fmt == "i420":                                                         # 8-bit 4:2:0: the fixed-format entries
+        rgb = ops.yuv_frames_to_rgb8(*ops.yuv420_planes(packed, fmt), **kw)
+    else:
+        _, sx, sy, depth, shift, _ = ops.YUV_PIXEL_FORMATS[fmt]
+        if sx == 1:                                                           # (4:4:4 has no siting: test_cfg.input refuses the key)
+            del kw["siting"]
+        rgb = ops.yuv_planes_to_rgb8(*ops.yuv_planes(packed, fmt), depth, shift, (sx, sy), **kw)
     return packed, rgb, dict(type=fmt, **kw)
+
+
+load_y4m_planes = load_y4m            # (the name a 4:2:2 / 4:4:4 / 10- or 12-bit file's loader had on its own)
 
 
 def _input(a, size):
