@@ -109,10 +109,12 @@ SIGNATURES = {
     "fgvc_yuv_out_tile_cols": (_i, []),
     "fgvc_jf_tile_rows": (_i, []),
     "fgvc_jf_counts_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_seg_object_stats_u8": (_i, [_p, C.c_int64, C.c_int64, _i, _i, _i, _i, _p, _p]),
     "fgvc_render_frames_u8": (_i, [*_RENDER_HEAD, _p]),
     "fgvc_render_trails_u8": (_i, [*_RENDER_HEAD, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
     "fgvc_render_pose_u8": (_i, [*_RENDER_HEAD, _p, _i, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p, _i, _i, C.c_int64, C.c_int64,
                                  C.c_int64, _p, C.c_double, C.c_double, _p]),
+    "fgvc_render_boxes_u8": (_i, [*_RENDER_HEAD, _p, C.c_int64, _p, C.c_int64, _p, _i, _i, _i, _p, _i, _p, _p]),
     "fgvc_render_tile_rows": (_i, []),
     "fgvc_render_tile_cols": (_i, []),
     "fgvc_c2f_refine_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

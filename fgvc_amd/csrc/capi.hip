@@ -56,6 +56,7 @@ int frames_rgb8_to_yuv420_launch(const uint8_t*, int, int, int, long long, long 
 void yuv_out_tile(int*, int*);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
+int object_stats_launch(const uint8_t*, long long, long long, int, int, int, int, int64_t*, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -805,6 +806,24 @@ int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int 
   return jf_counts_launch(gt, pred, T, h, w, n_objects, radius, counts, (hipStream_t)stream);
 }
 
+int fgvc_seg_object_stats_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int n_ids, int64_t* stats,
+                             void* stream) {
+  const char* fn = "fgvc_seg_object_stats_u8";
+  FGVC_REQUIRE(ids, FGVC_ERR_INVALID_ARG, "%s: ids: null pointer", fn);
+  FGVC_REQUIRE(stats, FGVC_ERR_INVALID_ARG, "%s: stats: null pointer", fn);
+  FGVC_REQUIRE(n_ids >= 1 && n_ids <= 256, FGVC_ERR_INVALID_ARG, "%s: n_ids=%d (1 .. 256: the ids are bytes)", fn, n_ids);
+  FGVC_REQUIRE(T >= 1, FGVC_ERR_INVALID_ARG, "%s: T=%d (at least 1)", fn, T);
+  FGVC_REQUIRE(h >= 1, FGVC_ERR_INVALID_ARG, "%s: h=%d (at least 1)", fn, h);
+  FGVC_REQUIRE(w >= 1, FGVC_ERR_INVALID_ARG, "%s: w=%d (at least 1)", fn, w);
+  // sum_x and sum_y stay below h w max(h, w): 64-bit sums hold them with room to spare below 2^62
+  FGVC_REQUIRE((unsigned __int128)h * (unsigned)w * (unsigned)(h > w ? h : w) < ((unsigned __int128)1 << 62), FGVC_ERR_INVALID_ARG,
+               "%s: h, w = %d, %d: h w max(h, w) reaches 2^62", fn, h, w);
+  FGVC_REQUIRE(ids_stride_y >= w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+               "%s: ids_stride_y: a row stride of at least w = %d bytes and a non-negative frame stride, got %lld, %lld", fn, w,
+               (long long)ids_stride_y, (long long)ids_stride_t);
+  return object_stats_launch(ids, ids_stride_t, ids_stride_y, T, h, w, n_ids, stats, (hipStream_t)stream);
+}
+
 int fgvc_render_tile_rows(void) {
   int rows, cols;
   render_tile(&rows, &cols);
@@ -946,6 +965,41 @@ int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t 
   const int reach = E > 0 ? (int)ceil(limb_width / 2.0 + 0.5) : 0;    // ceil(ro): what a limb's box is grown by
   return render_pose_launch(c, skeleton, E, limb_colors, reach, ro2, g, limb_alpha, heat, heat_f64 != 0, heat ? K : 0, heat_stride_t,
                             heat_stride_k, heat_stride_y, heat_colors, heat_gain, heat_alpha, (hipStream_t)stream);
+}
+
+int fgvc_render_boxes_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                         int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                         const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                         int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                         const uint8_t* colors, int P, int radius, const double* icon, const int32_t* boxes, int64_t boxes_stride_t,
+                         const uint8_t* box_visibles, int64_t box_visibles_stride_t, const uint8_t* box_colors, int N, int box_width,
+                         int box_alpha, const int32_t* box_labels, int label_scale, const uint8_t* digits, void* stream) {
+  const char* fn = "fgvc_render_boxes_u8";
+  const RenderCall c{frames, frames_stride_t, frames_stride_y, out, out_stride_t, out_stride_y, T, h, w, ids, ids_stride_t, ids_stride_y,
+                     palette, alpha, contour != 0, tracks, tracks_stride_p, tracks_stride_t, visibles, visibles_stride_p, visibles_stride_t,
+                     colors, P, radius, icon};
+  if (int rc = render_check_sizes(fn, c)) return rc;
+  FGVC_REQUIRE(N >= 0 && N <= 255, FGVC_ERR_INVALID_ARG, "%s: N=%d boxes (0 .. 255)", fn, N);
+  FGVC_REQUIRE(box_width >= 1 && box_width <= 16, FGVC_ERR_INVALID_ARG, "%s: box_width=%d (1 .. 16)", fn, box_width);
+  FGVC_REQUIRE(box_alpha >= 0 && box_alpha <= 256, FGVC_ERR_INVALID_ARG, "%s: box_alpha=%d (0 .. 256)", fn, box_alpha);
+  FGVC_REQUIRE(label_scale >= 1 && label_scale <= 4, FGVC_ERR_INVALID_ARG, "%s: label_scale=%d (1 .. 4)", fn, label_scale);
+  if (T == 0 || h == 0 || w == 0) return FGVC_OK;                     // no pixel exists
+  if (int rc = render_check_operands(fn, c, tracks && P > 0)) return rc;
+  if (tracks && P > 0) {
+    FGVC_REQUIRE(colors && icon, FGVC_ERR_INVALID_ARG, "%s: tracks without colors or the icon table", fn);
+    FGVC_REQUIRE(aligned8(tracks, icon), FGVC_ERR_INVALID_ARG, "%s: tracks and icon must be 8-byte aligned", fn);
+  }
+  if (N > 0) {
+    FGVC_REQUIRE(boxes && box_colors, FGVC_ERR_INVALID_ARG, "%s: boxes or box_colors: null pointer", fn);
+    FGVC_REQUIRE((reinterpret_cast<uintptr_t>(boxes) & 3u) == 0 && (reinterpret_cast<uintptr_t>(box_labels) & 3u) == 0, FGVC_ERR_INVALID_ARG,
+                 "%s: boxes and box_labels must be 4-byte aligned", fn);
+    FGVC_REQUIRE(T == 1 || (boxes_stride_t >= 0 && (!box_visibles || box_visibles_stride_t >= 0)), FGVC_ERR_INVALID_ARG,
+                 "%s: boxes, box_visibles: a negative frame stride (%lld, %lld)", fn, (long long)boxes_stride_t,
+                 (long long)box_visibles_stride_t);
+    FGVC_REQUIRE(!box_labels || digits, FGVC_ERR_INVALID_ARG, "%s: box_labels without the digits table", fn);
+  }
+  return render_boxes_launch(c, boxes, boxes_stride_t, box_visibles, box_visibles_stride_t, box_colors, N, box_width, box_alpha, box_labels,
+                             label_scale, digits, (hipStream_t)stream);
 }
 
 int fgvc_c2f_refine_f32(const int32_t* coarse_arg, const float* qfine, const float* kfine, const float* vfine, int T,

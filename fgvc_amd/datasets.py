@@ -616,13 +616,14 @@ class Davis2017:
         return data, dict(name=seq, gt=gt, n_objects=int(gt[0].max()))
 
 
-def davis_evaluate(model, dataset: "Davis2017", backend: str = "host") -> dict:
+def davis_evaluate(model, dataset: "Davis2017", backend: str = "host", boxes: bool = False) -> dict:
     """Run the mask path over the set and score it (metrics.davis_jf).  backend='hip': the counts behind J and F come from
     fgvc_jf_counts_u8; the annotation of a sequence is uploaded once, and a prediction the model returns on the device (test_cfg.masks=
-    'device') is scored where it is."""
+    'device') is scored where it is.  boxes=True: every sequence also gets 'Box-IoU', metrics.mean_box_iou of the predicted against the
+    annotated maps' boxes (on the same backend), and the result 'Box-IoU-Mean', their mean over the sequences."""
     from . import metrics
     hip = metrics._backend(backend)
-    seqs = {}
+    seqs, box_iou = {}, {}
     for i in range(len(dataset)):
         data, meta = dataset[i]
         pred = model(test_mode=True, **data)[0]
@@ -632,7 +633,14 @@ def davis_evaluate(model, dataset: "Davis2017", backend: str = "host") -> dict:
         if hip and isinstance(gt, np.ndarray) and gt.dtype == np.uint8:
             gt = torch.from_numpy(gt).to(pred.device if isinstance(pred, torch.Tensor) and pred.is_cuda else "cuda")
         seqs[meta["name"]] = (gt, pred)
-    return metrics.davis_jf(seqs, backend=backend)
+        if boxes:
+            box_iou[meta["name"]] = metrics.mean_box_iou(gt, pred, int(gt.max()) + 1, backend=backend)
+    jf = metrics.davis_jf(seqs, backend=backend)
+    if boxes:
+        for name, v in box_iou.items():
+            jf["sequences"][name]["Box-IoU"] = v
+        jf["Box-IoU-Mean"] = float(np.nanmean(list(box_iou.values()))) if np.isfinite(list(box_iou.values())).any() else float("nan")
+    return jf
 
 
 class YoutubeVos:
@@ -1076,3 +1084,43 @@ def write_y4m(path, frames, fps=(30, 1), siting: str = "left", range: str = "lim
     if f.ndim != 3 or f.dtype != np.uint8 or f.shape[1] % 3 or f.shape[2] % 2:
         raise ValueError(f"write_y4m: packed I420 frames (T, 3 h / 2, w) uint8 with h and w even, got {f.dtype} {f.shape}")
     write_y4m_planes(path, f, "i420", fps, siting, range)
+
+
+# ---- MOTChallenge text files ----------------------------------------------------------------------------------------
+
+def write_mot(path, tracks, ids=None) -> int:
+    """Write an engine.ObjectTracks as a MOTChallenge text file (the layout restated from its public description; parity unpinned): one line
+    per present object and frame, `frame, id, left, top, width, height, 1, -1, -1, -1` with frames counted from 1, in frame then id order.
+    Only objects of id >= 1 are written (row 0 is the background).  ids: the id to write for every row of `tracks` (N integers; None: the
+    row's own number).  Returns the number of lines."""
+    boxes, present = tracks.boxes, tracks.present
+    T, N = present.shape
+    names = list(range(N)) if ids is None else [int(i) for i in ids]
+    if len(names) != N:
+        raise ValueError(f"ids: {N} integers to go with the tracks, got {len(names)}")
+    lines = []
+    for t in range(T):
+        for o in range(1, N):
+            if present[t, o]:
+                x0, y0, x1, y1 = (int(v) for v in boxes[t, o])
+                lines.append(f"{t + 1},{names[o]},{x0},{y0},{x1 - x0},{y1 - y0},1,-1,-1,-1\n")
+    with open(path, "w") as f:
+        f.writelines(lines)
+    return len(lines)
+
+
+def read_mot(path):
+    """A MOTChallenge text file -> {id: {0-based frame: (x0, y0, x1, y1)}} with half-open integer boxes: write_mot's inverse (the columns after
+    the box are not kept; blank lines are skipped)."""
+    out = {}
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            v = [c.strip() for c in line.split(",")]
+            if len(v) < 6:
+                raise ValueError(f"{path}:{n}: expected `frame, id, left, top, width, height, ...`, got {line.strip()!r}")
+            frame, obj = int(v[0]), int(v[1])
+            left, top, width, height = (int(round(float(c))) for c in v[2:6])
+            out.setdefault(obj, {})[frame - 1] = (left, top, left + width, top + height)
+    return out

@@ -21,6 +21,7 @@ import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -797,14 +798,15 @@ def _mask_readout(soft: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, p
 def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
                     out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
                     events: Optional[dict] = None, affinity_stats: Optional[dict] = None, guide: Optional[torch.Tensor] = None,
-                    readout: Optional[ReadoutConfig] = None) -> torch.Tensor:
+                    readout: Optional[ReadoutConfig] = None, objects_out: Optional[list] = None) -> torch.Tensor:
     """Semi-supervised VOS for one clip.  feats_hwc: the clip's bank as run_affinity (TrackerConfig) or run_local_affinity (LocalConfig)
     takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame index map; pad = (left, right, top, bottom) as
     pad_divide_by gives it; out_shape = (h0, w0).  On the local window the feature grid is whatever the encoder made of the padded
     frame: (Hf, Wf) need not divide (hp, wp).
     Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
     resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output).
-    readout (parse_readout's ReadoutConfig) with guide (T, 3, hp, wp) f32, the padded frames: the edge-aware read-out; None: the plain one."""
+    readout (parse_readout's ReadoutConfig) with guide (T, 3, hp, wp) f32, the padded frames: the edge-aware read-out; None: the plain one.
+    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor (test_cfg.objects)."""
     T, dev = feats_hwc.shape[0], feats_hwc.device
     _record(events, "labels")
     C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
@@ -817,6 +819,8 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     _sweep_labels(bank, soft, sw, Hf, Wf, cfg.hard_prop)
     _record(events, "readout")
     masks = _mask_readout(soft, Hf, Wf, seg_map, pad, out_shape, cfg.norm_mask, guide, readout)
+    if objects_out is not None:
+        objects_out.append(ops.object_stats(masks, C))
     _record(events, "end")
     return masks
 
@@ -1055,7 +1059,7 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
                          out_shape: Tuple[int, int], cfg, rc: RefsConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
                          confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None,
                          guide: Optional[torch.Tensor] = None, readout: Optional[ReadoutConfig] = None, cells: Optional[torch.Tensor] = None,
-                         disagree_out: Optional[list] = None):
+                         disagree_out: Optional[list] = None, objects_out: Optional[list] = None):
     """propagate_masks with index maps at any frames: seg_maps = {frame: padded (hp, wp) uint8 map on the device}; rc names the direction and
     the override rule (sweep_refs_host is the contract).  Returns (T, h0, w0) uint8 on the device; frame s0 (the earliest annotated one) is
     its given map, unpadded and nearest-resized, every other frame the read-out of its rows, frames before s0 under 'forward' zero.
@@ -1065,7 +1069,8 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
     readout / guide as propagate_masks takes them; cells: ops.guide_cells of the whole guide where the caller keeps it (a LabelSession).
     rc.fuse='linear' with more than one annotated frame (fuse_refs_host is the contract): the forward sweep from the first and the backward
     sweep from the last annotated frame, blended between the maps by ops.seg_fuse_rows, then the same read-outs; disagree_out (a list)
-    receives the (T,) int64 device tensor of per-frame disagreement counts.  With one annotated frame the call is direction='both'."""
+    receives the (T,) int64 device tensor of per-frame disagreement counts.  With one annotated frame the call is direction='both'.
+    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor."""
     if readout is not None and guide is None:
         raise ValueError("the guided read-out needs the padded frames (guide=)")
     if isinstance(cfg, LocalConfig):
@@ -1149,6 +1154,8 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
             run(s0 + 1, bw, {}, torch.arange(s0 - 1, -1, -1, device=dev))
     ref = seg_maps[s0][lh:hp - uh, lw:wp - uw].float()[None, None]
     masks[s0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
+    if objects_out is not None:
+        objects_out.append(ops.object_stats(masks, C))
     if not confidence:
         return masks
     conf[s0] = 255
@@ -1403,6 +1410,83 @@ def parse_masks(value) -> str:
     if value not in MASK_FORMS:
         raise ValueError(f"test_cfg.masks={value!r}: one of {MASK_FORMS}")
     return value
+
+
+OBJECTS_KEYS = ("stats",)
+
+
+def parse_objects(spec) -> bool:
+    """test_cfg.objects (an extension key): None -> False; dict(stats=True | False) -> whether the index-map call
+    leaves an ObjectTracks of the masks it returns in model.last_objects.  An unknown sub-key, a non-mapping or a non-bool value raises
+    ValueError naming it."""
+    if spec is None:
+        return False
+    if not hasattr(spec, "keys"):
+        raise ValueError(f"test_cfg.objects={spec!r}: a dict with the keys {OBJECTS_KEYS}")
+    unknown = sorted(set(spec.keys()) - set(OBJECTS_KEYS))
+    if unknown:
+        raise ValueError(f"test_cfg.objects: unknown key(s) {unknown}; the keys are {OBJECTS_KEYS}")
+    stats = spec.get("stats", True)
+    if not isinstance(stats, bool):
+        raise ValueError(f"test_cfg.objects.stats={stats!r}: True or False")
+    return stats
+
+
+@dataclass
+class ObjectTracks:
+    """The objects of a (T, h, w) id map as boxes: a view over stats (T, N, 8) int64 as ops.object_stats / metrics.object_stats_host give
+    them (a tensor on any device or an array; kept as given in `stats`, every property is a numpy array on the host).  Row o is id o, the
+    background (row 0) included.  The host copy is made once, at the first property read: `stats` is not to be written afterwards."""
+    stats: object
+    _host_copy: Optional[np.ndarray] = field(default=None, init=False, repr=False, compare=False)
+
+    def _host(self) -> np.ndarray:
+        if self._host_copy is None:
+            s = self.stats
+            a = s.detach().cpu().numpy() if isinstance(s, torch.Tensor) else np.asarray(s)
+            if a.ndim != 3 or a.shape[2] != 8 or a.dtype != np.int64:
+                raise ValueError(f"stats: (T, N, 8) int64, got {a.dtype} {a.shape}")
+            a = a.view()
+            a.setflags(write=False)
+            self._host_copy = a
+        return self._host_copy
+
+    @property
+    def area(self) -> np.ndarray:
+        """(T, N) int64 pixel counts"""
+        return self._host()[..., 0]
+
+    @property
+    def present(self) -> np.ndarray:
+        """(T, N) bool: the id has a pixel on the frame"""
+        return self._host()[..., 0] > 0
+
+    @property
+    def boxes(self) -> np.ndarray:
+        """(T, N, 4) int64 (x0, y0, x1, y1), half-open; an absent object's is (0, 0, 0, 0), which is empty"""
+        return self._host()[..., 1:5]
+
+    @property
+    def centroids(self) -> np.ndarray:
+        """(T, N, 2) float64 (mean x, mean y) of the pixels' integer coordinates = sum / area; NaN where absent"""
+        a = self._host()
+        area = a[..., 0:1].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(area > 0, a[..., 5:7].astype(np.float64) / area, np.nan)
+
+    @property
+    def border(self) -> np.ndarray:
+        """(T, N) int64: the object's pixels on the frame's outermost rows and columns"""
+        return self._host()[..., 7]
+
+    def centroid_tracks(self):
+        """(tracks (N, T, 2) float64, visibles (N, T) bool) as viz.paint_point_track / viz.paint_trails / viz.render take them.  The
+        painters draw a track coordinate c at c + 0.5 in pixel indices (viz._paint_host: x = track + 0.5, and a dot at track 5.0 is shared
+        equally by pixels 5 and 6; the trails' segments run through track + 0.5 with pixel p at the point p): in the painters' convention
+        the centre of pixel p is the coordinate p - 0.5.  `centroids` are means of pixel indices, so the tracks are centroids - 0.5: an
+        object of the one pixel p gets its dot centred on pixel p.  Absent objects: coordinate 0 and visible False."""
+        c = np.nan_to_num(self.centroids - 0.5, nan=0.0)
+        return np.ascontiguousarray(c.transpose(1, 0, 2)), np.ascontiguousarray(self.present.T)
 
 
 def backward_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, stats: Optional[dict] = None) -> torch.Tensor:

@@ -500,3 +500,65 @@ def flow_epe(pred, gt, valid=None) -> dict:
         return {"epe": float("nan"), "1px": float("nan"), "3px": float("nan"), "5px": float("nan"), "n": 0}
     return {"epe": float(e.mean()), "1px": float((e < 1).double().mean()), "3px": float((e < 3).double().mean()),
             "5px": float((e < 5).double().mean()), "n": n}
+
+
+# ---- objects as boxes ---------------------------------------------------------------------------------------------
+
+def object_stats_host(ids, n_ids: int) -> np.ndarray:
+    """The contract of ops.object_stats (fgvc_seg_object_stats_u8), in plain numpy: ids (T, h, w) integers -> (T, n_ids, 8) int64.  For
+    frame t and id o = 0 .. n_ids - 1 (the background has its row), over the pixels (y, x) with ids[t, y, x] == o:
+        0 area   1 x0 = min x   2 y0 = min y   3 x1 = max x + 1   4 y1 = max y + 1   5 sum of x   6 sum of y
+        7 border = how many of them have x == 0, x == w - 1, y == 0 or y == h - 1
+    An id without a pixel on a frame: eight zeros.  Ids of n_ids or more are counted nowhere."""
+    ids = np.asarray(ids)
+    if ids.ndim != 3:
+        raise ValueError(f"ids: 3 dimensions (T, h, w), got {ids.shape}")
+    if ids.dtype.kind not in "iu":                           # (the mask call's float64 arrays hold small integers)
+        ids = np.rint(ids).astype(np.int64)
+    n_ids = int(n_ids)
+    if not 1 <= n_ids <= 256:
+        raise ValueError(f"n_ids={n_ids}: 1 .. 256")
+    T, h, w = ids.shape
+    out = np.zeros((T, n_ids, 8), np.int64)
+    for t in range(T):
+        present = np.unique(ids[t])
+        for o in present[(present >= 0) & (present < n_ids)].tolist():
+            ys, xs = np.nonzero(ids[t] == o)
+            ys, xs = ys.astype(np.int64), xs.astype(np.int64)
+            edge = (xs == 0) | (xs == w - 1) | (ys == 0) | (ys == h - 1)
+            out[t, o] = (xs.size, xs.min(), ys.min(), xs.max() + 1, ys.max() + 1, xs.sum(), ys.sum(), np.count_nonzero(edge))
+    return out
+
+
+def box_iou(a, b) -> np.ndarray:
+    """Intersection over union of half-open integer boxes (..., 4) = (x0, y0, x1, y1), broadcast against each other -> float64.  A box with
+    x1 <= x0 or y1 <= y0 is empty: against a non-empty box the value is 0, and two empty boxes give NaN (no union to divide by)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.shape[-1] != 4 or b.shape[-1] != 4:
+        raise ValueError(f"boxes: (..., 4) as (x0, y0, x1, y1), got {a.shape} and {b.shape}")
+
+    def area(x0, y0, x1, y1):
+        return np.maximum(x1 - x0, 0.0) * np.maximum(y1 - y0, 0.0)
+    area_a, area_b = area(*np.moveaxis(a, -1, 0)), area(*np.moveaxis(b, -1, 0))
+    inter = area(np.maximum(a[..., 0], b[..., 0]), np.maximum(a[..., 1], b[..., 1]), np.minimum(a[..., 2], b[..., 2]),
+                 np.minimum(a[..., 3], b[..., 3]))
+    inter = np.where((area_a > 0) & (area_b > 0), inter, 0.0)
+    union = area_a + area_b - inter
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(union > 0, inter / union, np.nan)
+
+
+def mean_box_iou(gt_ids, pred_ids, n_ids: int, backend: str = "host") -> float:
+    """The mean box_iou of the objects' boxes in two (T, h, w) id maps, over the objects 1 .. n_ids - 1 and the frames 1 .. T - 1 (frame 0 is
+    the given annotation) on which at least one of the two maps has the object; NaN when there is no such pair.  backend='host': both
+    sets of boxes from object_stats_host; 'hip': from one ops.object_stats call each (fgvc_seg_object_stats_u8), the same integers."""
+    if _backend(backend):
+        from . import ops
+        sg = ops.object_stats(_device_ids(gt_ids, n_ids - 1), n_ids).cpu().numpy()
+        sp = ops.object_stats(_device_ids(pred_ids, n_ids - 1), n_ids).cpu().numpy()
+    else:
+        def host(x):
+            return np.asarray(x.detach().cpu() if hasattr(x, "detach") else x)
+        sg, sp = object_stats_host(host(gt_ids), n_ids), object_stats_host(host(pred_ids), n_ids)
+    iou = box_iou(sg[1:, 1:, 1:5], sp[1:, 1:, 1:5])
+    return float(np.nanmean(iou)) if np.isfinite(iou).any() else float("nan")

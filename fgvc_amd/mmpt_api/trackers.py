@@ -130,6 +130,7 @@ class LabelSession:
         fuse='linear' (with direction='both', override='all'): the frames between two annotated frames blend the forward and the backward
         sweep (engine.fuse_refs_host); the per-frame counts of cells on which the two disagree stay in self.last_disagree, and the session
         keeps the lists of (first annotated frame, 'fw') and (last annotated frame, 'bw') only."""
+        self.model.last_objects = None
         if self.feats is None:
             raise RuntimeError("LabelSession: propagate after close()")
         base = self.model.refs_cfg or engine.RefsConfig()
@@ -139,11 +140,14 @@ class LabelSession:
         maps = engine.check_ref_maps(refs, self.n_frames, self.size)
         segs = {t: torch.nn.functional.pad(m.to(self.device, torch.uint8), self.pad).contiguous() for t, m in maps.items()}
         stats, disagree = [], []
+        objects = [] if self.model.objects_stats else None
         out = engine.propagate_masks_refs(self.feats, self.Hf, self.Wf, segs, self.pad, self.out_shape, self.cfg, rc,
                                           channels=self.model.feat_channels, stats_out=stats, confidence=bool(confidence),
                                           sweeps=self._sweeps, counters=self.counters, guide=self.guide,
                                           readout=self.model.readout_cfg if self.guide is not None else None, cells=self.cells,
-                                          disagree_out=disagree)
+                                          disagree_out=disagree, objects_out=objects)
+        if objects:
+            self.model.last_objects = engine.ObjectTracks(objects[0])
         self.last_disagree = None
         if rc.fuse is not None:            # one annotated frame: nothing was fused, nothing disagrees
             self.last_disagree = disagree[0].cpu() if disagree else torch.zeros(self.n_frames, dtype=torch.int64)
@@ -179,6 +183,8 @@ class VanillaTracker(BaseTracker):
         self.pose_cfg = engine.parse_pose(self.test_cfg.get("pose", None))         # test_cfg.pose (None: the coords=True call returns coordinates only)
         self.last_pose = None              # dict(peak, field) of the last coords=True call with test_cfg.pose set, else None
         self.readout_cfg = engine.parse_readout(self.test_cfg.get("readout", None))   # test_cfg.readout (None / type='bilinear': the plain read-out)
+        self.objects_stats = engine.parse_objects(self.test_cfg.get("objects", None))  # test_cfg.objects = dict(stats=True); the index-map call only
+        self.last_objects = None           # engine.ObjectTracks of the masks the last index-map call returned with test_cfg.objects set, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -592,6 +598,10 @@ class VanillaTracker(BaseTracker):
         self._raw_input(imgs, "imgs")                      # uint8 frames: TypeError without test_cfg.input, the GPU-only rule with it
         self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
         self._refuse_readout(soft=torch.is_tensor(ref_seg_map) and ref_seg_map.ndim == 4)
+        self.last_objects = None
+        if self.objects_stats and (g("coords", False) or g("return_maps", False)):
+            raise NotImplementedError("fgvc_amd: test_cfg.objects describes the id maps of the index-map call; coords=True / return_maps=True "
+                                      "(soft labels) return none -- remove one of the keys")
         if self.refs_cfg is None and hasattr(ref_seg_map, "keys"):
             raise TypeError("ref_seg_map: a mapping {frame index: index map} is taken with the extension key test_cfg.refs = "
                             "dict(direction='forward' | 'both', override='new' | 'all'); without it ref_seg_map is frame 0's tensor")
@@ -634,9 +644,12 @@ class VanillaTracker(BaseTracker):
         seg = torch.nn.functional.pad(ref_seg_map[0].to(imgs.device, torch.uint8), pad).contiguous()
         feats, Hf, Wf = self._label_feats(frames, index_map=True)
         stats, self.label_stats = [], {}
+        objects = [] if self.objects_stats else None
         masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats,
                                        affinity_stats=self.label_stats, guide=self._readout_guide(frames, Hf, Wf),
-                                       readout=self.readout_cfg)
+                                       readout=self.readout_cfg, objects_out=objects)
+        if objects:
+            self.last_objects = engine.ObjectTracks(objects[0])
         self._refine_stats = stats or None
         self._check_kernels()
         if self.masks_form == "device":

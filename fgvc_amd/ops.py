@@ -2077,6 +2077,43 @@ def jf_counts(gt: torch.Tensor, pred: torch.Tensor, n_objects: int, radius: int,
     return out
 
 
+# ---- objects as boxes: area, box, coordinate sums and border count per frame and id -----------------------------
+
+OBJECT_WORDS = ("area", "x0", "y0", "x1", "y1", "sum_x", "sum_y", "border")
+
+
+def object_stats(ids: torch.Tensor, n_ids: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ids (T, h, w) uint8 on the GPU -> (T, n_ids, 8) int64: per frame and id o = 0 .. n_ids - 1 (the background has its row), over the
+    pixels with that id: area, x0 = min x, y0 = min y, x1 = max x + 1, y1 = max y + 1, sum of x, sum of y, and the number of them on the
+    frame's outermost rows and columns -- metrics.object_stats_host word for word, in one launch of fgvc_seg_object_stats_u8 on the current
+    stream.  An absent id: eight zeros; ids of n_ids or more are counted nowhere.  1 <= n_ids <= 256.  The map is read through its frame
+    and row strides (a time slice or a window is not copied; pixels must be packed, else a contiguous copy is made).  `out`: a contiguous
+    (T, n_ids, 8) int64 tensor on ids' device; every element is written, the caller clears nothing."""
+    if not ids.is_cuda:
+        raise _lib.FgvcHipError("ids must be on the GPU (fgvc_amd has no CPU path)")
+    if ids.dtype != torch.uint8:
+        raise TypeError(f"ids: expected torch.uint8 object ids, got {ids.dtype}")
+    if ids.dim() != 3:
+        raise ValueError(f"ids: 3 dimensions (T, h, w), got {tuple(ids.shape)}")
+    n_ids = int(n_ids)
+    if not 1 <= n_ids <= 256:
+        raise ValueError(f"n_ids={n_ids}: 1 .. 256 (the ids are bytes)")
+    T, h, w = ids.shape
+    shape = (T, n_ids, 8)
+    if out is None:
+        out = torch.empty(shape, device=ids.device, dtype=torch.int64)
+    elif tuple(out.shape) != shape or out.dtype != torch.int64 or out.device != ids.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous int64 tensor of shape {shape} on {ids.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0:
+        return out
+    if h == 0 or w == 0:
+        return out.zero_()
+    if not (ids.stride(2) == 1 and ids.stride(1) >= w and ids.stride(0) >= 0):
+        ids = ids.contiguous()
+    _lib.call("fgvc_seg_object_stats_u8", _ptr(ids), ids.stride(0), ids.stride(1), T, h, w, n_ids, _ptr(out), _stream(ids))
+    return out
+
+
 # ---- render: mask overlay and point icons onto uint8 video (DESIGN.md section 16) -------------------------------------------------------
 
 RENDER_TILE = (8, 256)  # rows, columns one workgroup of fgvc_render_frames_u8 owns (= fgvc_render_tile_rows/_cols(); the tests put points on its corners)
@@ -2301,4 +2338,70 @@ def render_pose(frames_u8: torch.Tensor, tracks: Optional[torch.Tensor] = None, 
             limb_colors = col[sk[:, 1].long()].contiguous()                               # the colour of every edge's second joint
         limbs = (_ptr(sk), E, _ptr(limb_colors), lw, ro2, g, l_alpha)
     _lib.call("fgvc_render_pose_u8", *head, *limbs, *maps, _stream(out))
+    return out
+
+
+def render_boxes(frames_u8: torch.Tensor, boxes: torch.Tensor, box_visibles: Optional[torch.Tensor] = None,
+                 box_colors: Optional[torch.Tensor] = None, box_width: int = 2, box_alpha: int = 255, box_labels: Optional[torch.Tensor] = None,
+                 label_scale: int = 1, ids: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None, alpha: int = 128,
+                 contour: bool = True, tracks: Optional[torch.Tensor] = None, visibles: Optional[torch.Tensor] = None,
+                 colors: Optional[torch.Tensor] = None, radius: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """render_frames with boxes: the overlay, then box i of boxes (T, N, 4) integer (x0, y0, x1, y1), half-open, as a
+    ring `box_width` (1 .. 16) pixels wide outside the box in box_colors[i] ((N, 3) uint8; None: palette[i]) at opacity box_alpha
+    (0 .. 256), with a tag of the decimal digits of box_labels[i] ((N,) integers 0 .. 999; None: no tags) at label_scale (1 .. 4), then the
+    dots -- viz.render(boxes=...)'s host backend bit for bit, in one launch of fgvc_render_boxes_u8 on the current stream.  box_visibles
+    (T, N) bool or uint8, None: all; an empty box draws nothing.  N <= 255; a coordinate of 2**20 or more in magnitude is refused (one
+    host read of a flag).  Every tensor is on the frames' device; every other argument is render_frames'."""
+    from . import viz
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"frames_u8: (T, H, W, 3), got {tuple(frames_u8.shape)}")
+    dev = frames_u8.device
+    T = frames_u8.shape[0]
+    if not isinstance(boxes, torch.Tensor) or boxes.device != dev:
+        raise ValueError(f"boxes: a tensor on {dev} with the frames")
+    if boxes.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise TypeError(f"boxes: expected an integer type, got {boxes.dtype}")
+    if boxes.dim() != 3 or boxes.shape[0] != T or boxes.shape[2] != 4:
+        raise ValueError(f"boxes: ({T}, N, 4) to go with the frames, got {tuple(boxes.shape)}")
+    N = boxes.shape[1]
+    if N > viz.MAX_BOXES:
+        raise ValueError(f"boxes: N={N} boxes a frame (0 .. {viz.MAX_BOXES})")
+    if boxes.numel() and bool((boxes.long().abs() >= viz.BOX_LIMIT).any()):
+        raise ValueError("boxes: coordinates below 2**20 in magnitude")
+    b = boxes.to(torch.int32).contiguous()
+    bw = viz._int_in(box_width, viz.BOX_WIDTHS[0], viz.BOX_WIDTHS[1], "box_width")
+    b_alpha = viz._int_in(box_alpha, 0, 256, "box_alpha")
+    scale = viz._int_in(label_scale, viz.LABEL_SCALES[0], viz.LABEL_SCALES[1], "label_scale")
+    vis = None
+    if box_visibles is not None:
+        if box_visibles.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"box_visibles: expected torch.bool (or uint8), got {box_visibles.dtype}")
+        if tuple(box_visibles.shape) != (T, N) or box_visibles.device != dev:
+            raise ValueError(f"box_visibles: {(T, N)} on {dev} to go with the boxes, got {tuple(box_visibles.shape)} on {box_visibles.device}")
+        vis = (box_visibles.view(torch.uint8) if box_visibles.dtype == torch.bool else box_visibles).contiguous()
+    if box_colors is None:
+        pal = _render_table("palette", dev, viz.davis_palette) if palette is None else palette
+        if pal.dtype != torch.uint8 or tuple(pal.shape) != (256, 3) or pal.device != dev:
+            raise ValueError(f"palette: (256, 3) uint8 on {dev} (box_colors=None takes palette[i])")
+        box_colors = pal[:N]
+    if box_colors.dtype != torch.uint8:
+        raise TypeError(f"box_colors: expected torch.uint8, got {box_colors.dtype}")
+    if tuple(box_colors.shape) != (N, 3) or box_colors.device != dev:
+        raise ValueError(f"box_colors: {(N, 3)} on {dev} to go with the boxes, got {tuple(box_colors.shape)} on {box_colors.device}")
+    col = box_colors.contiguous()
+    labels = digits = None
+    if box_labels is not None:
+        if not isinstance(box_labels, torch.Tensor) or box_labels.device != dev or box_labels.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"box_labels: an int32 or int64 tensor on {dev} with the frames")
+        if tuple(box_labels.shape) != (N,):
+            raise ValueError(f"box_labels: {N} integers in 0 .. {viz.MAX_LABEL}, got {tuple(box_labels.shape)}")
+        if N and bool(((box_labels < 0) | (box_labels > viz.MAX_LABEL)).any()):
+            raise ValueError(f"box_labels: integers in 0 .. {viz.MAX_LABEL}")
+        labels = box_labels.to(torch.int32).contiguous()
+        digits = _render_table("digits5x7", dev, lambda: viz.DIGITS_5X7)
+    head, out, _, hold = _render_head(frames_u8, ids, palette, alpha, contour, tracks, visibles, colors, radius, out)
+    if head is not None:
+        _lib.call("fgvc_render_boxes_u8", *head, _ptr(b) if N else None, b.stride(0), None if vis is None else _ptr(vis), 0 if vis is None else vis.stride(0),
+                  _ptr(col) if N else None,
+                  N, bw, b_alpha, None if labels is None else _ptr(labels), scale, None if digits is None else _ptr(digits), _stream(out))
     return out

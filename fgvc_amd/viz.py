@@ -5,6 +5,7 @@
     render(frames, ids=..., tracks=..., visibles=...)            overlay, then points; with trail=L: overlay, trails, points
     paint_trails(frames, point_tracks, visibles, trail=8)        every point's last L steps as a fading poly-line
     paint_pose(frames, joints, visibles, skeleton=, heat=)       joint heat maps, limbs and dots
+    paint_boxes(frames, boxes, box_visibles, box_labels=)        object boxes as rings with id tags
     pose_tracks(coords), pose_visibles(coords, peak, min_conf)   the pose call's (2, K, T) coordinates as what the painters take
     frames_to_yuv420(frames, fmt, matrix, range, siting)         the painted frames as packed 8-bit 4:2:0 video
 
@@ -37,6 +38,19 @@ fgvc_render_frames_u8 (ops.render_frames) and is held to the host backend with `
             order: the trails' segment from A = track[a, t] + 0.5 to B = track[b, t] + 0.5 with linewidth = limb_width, drawn only if both
             ends are visible on t and all four coordinates are below 2**20 in magnitude; op = cov limb_alpha, colour limb_colors[e] (None:
             the colour of joint b), truncated to uint8 after EVERY limb.  a == b and a zero-length limb are discs (L2 == 0).
+  boxes     (boxes=(T, N, 4) integers (x0, y0, x1, y1), half-open; after the overlay, before the points; backend='hip': ONE launch of
+            fgvc_render_boxes_u8, ops.render_boxes)  on frame t, box i = 0 .. N - 1 in order; a box with x1 <= x0 or y1 <= y0 or with
+            box_visibles[t, i] false draws nothing (engine.ObjectTracks' boxes and present are exactly that).  With bw = box_width,
+            a = box_alpha, C = box_colors[i] (None: palette[i]), every step on the pixels inside the frame, integers only:
+              ring    the pixels of [x0 - bw, x1 + bw) x [y0 - bw, y1 + bw) that are NOT in the box (the object stays uncovered):
+                      v_c = (v_c (256 - a) + C_c a + 128) >> 8, the overlay's formula
+              tag     (box_labels given)  d = the decimal digits of box_labels[i], s = label_scale, tw = (6 d + 1) s, th = 9 s;
+                      ty = y0 - bw - th (on top of the ring), or y0 when that is above row 0; tx = x0 - bw, or max(W - tw, 0) when the tag
+                      would end beyond column W.  [tx, tx + tw) x [ty, ty + th) blends as the ring does
+              digits  glyph g = 0 .. d - 1 from the left (most significant digit first) of DIGITS_5X7: its row r, column c (bit 4 - c of the
+                      row) is the s x s block at (tx + (1 + 6 g + c) s, ty + (1 + r) s), set -- opaque -- to white when
+                      299 C_r + 587 C_g + 114 C_b < 128000, else to black
+            boxes= goes with neither trail= nor skeleton= / heat= (one stage per launch).
 Tracks are (x, y) in the pixel frame of `frames` (scale_tracks for tracks predicted at another size) and are converted to float64 first.
 """
 from __future__ import annotations
@@ -58,6 +72,11 @@ MAX_HEAT_MAPS = 256
 # 6 left hip, 7 right elbow, 8 left elbow, 9 right knee, 10 left knee, 11 right wrist, 12 left wrist, 13 right ankle, 14 left ankle.
 _JHMDB_EDGES = ((0, 1), (0, 2), (0, 3), (0, 4), (1, 5), (1, 6), (3, 7), (7, 11), (4, 8), (8, 12), (5, 9), (9, 13), (6, 10), (10, 14))
 DOT_FRACTION = 0.015          # the reference's dot_size_as_fraction_of_min_edge
+MAX_BOXES = 255
+BOX_WIDTHS = (1, 16)
+BOX_LIMIT = 2 ** 20           # a box coordinate at or beyond it in magnitude is refused
+MAX_LABEL = 999
+LABEL_SCALES = (1, 4)
 SHARPNESS = 0.15
 
 
@@ -103,6 +122,22 @@ JHMDB_SKELETON = _jhmdb_skeleton()
 """JHMDB_SKELETON: (14, 2) int32, read-only, zero-based: the limbs of the JHMDB puppet as a tree over its 15 joints (neck, belly, face, right
 and left shoulder, hip, elbow, knee, wrist, ankle).  Restated from the dataset's public description of its joint order; it is UNPINNED:
 no JHMDB data is available offline to check it against.  BADJA has no agreed skeleton: pass the edges."""
+
+
+def _digits_5x7() -> np.ndarray:
+    rows = ("01110 10001 10011 10101 11001 10001 01110", "00100 01100 00100 00100 00100 00100 01110",
+            "01110 10001 00001 00010 00100 01000 11111", "11110 00001 00001 01110 00001 00001 11110",
+            "00010 00110 01010 10010 11111 00010 00010", "11111 10000 11110 00001 00001 10001 01110",
+            "00110 01000 10000 11110 10001 10001 01110", "11111 00001 00010 00100 01000 01000 01000",
+            "01110 10001 10001 01110 10001 10001 01110", "01110 10001 10001 01111 00001 00010 01100")
+    t = np.array([[int(r, 2) for r in g.split()] for g in rows], np.uint8)
+    t.setflags(write=False)
+    return t
+
+
+DIGITS_5X7 = _digits_5x7()
+"""DIGITS_5X7: (10, 7) uint8, read-only: the ten decimal digits as 5 x 7 bitmaps drawn for this project, one byte a row, bit 4 the
+leftmost column."""
 
 
 def default_radius(h: int, w: int) -> int:
@@ -361,6 +396,62 @@ def _check_heat_colors(heat_colors, K: int) -> np.ndarray:
     return heat_colors.astype(np.uint8)
 
 
+def _int_in(value, lo: int, hi: int, name: str) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{name}={value!r}: an integer in {lo} .. {hi}")
+    return int(value)
+
+
+def _check_boxes(frames_shape, boxes, box_visibles, box_colors, box_width, box_alpha, box_labels, label_scale, palette):
+    """-> (boxes (T, N, 4) int32, visibles (T, N) bool | None, colors (N, 3) uint8, box_width, box_alpha, labels (N,) int32 | None,
+    label_scale); every refusal names its argument"""
+    T = int(frames_shape[0])
+    b = np.asarray(boxes)
+    if b.dtype.kind not in "iu":
+        raise TypeError(f"boxes: ({T}, N, 4) integers (x0, y0, x1, y1), got {b.dtype}")
+    if b.ndim != 3 or b.shape[0] != T or b.shape[2] != 4:
+        raise ValueError(f"boxes: ({T}, N, 4) to go with the frames, got {b.shape}")
+    N = b.shape[1]
+    if N > MAX_BOXES:
+        raise ValueError(f"boxes: N={N} boxes a frame (0 .. {MAX_BOXES})")
+    if b.size and int(np.abs(b.astype(np.int64)).max()) >= BOX_LIMIT:
+        raise ValueError(f"boxes: coordinates below 2**20 in magnitude, got {int(np.abs(b.astype(np.int64)).max())}")
+    vis = None
+    if box_visibles is not None:
+        vis = np.asarray(box_visibles)
+        if vis.dtype != np.bool_:
+            raise TypeError(f"box_visibles: expected bool, got {vis.dtype}")
+        if vis.shape != (T, N):
+            raise ValueError(f"box_visibles: {(T, N)} to go with the boxes, got {vis.shape}")
+    if box_colors is None:
+        pal = _davis_palette() if palette is None else np.asarray(palette)
+        if pal.dtype != np.uint8 or pal.shape != (256, 3):
+            raise ValueError(f"palette: (256, 3) uint8 (box_colors=None takes palette[i]), got {pal.dtype} {pal.shape}")
+        col = pal[:N]
+    else:
+        col = np.asarray(box_colors)
+        if col.dtype.kind not in "iu":
+            raise TypeError(f"box_colors: integers in 0 .. 255, got {col.dtype}")
+        if col.shape != (N, 3):
+            raise ValueError(f"box_colors: {(N, 3)} to go with the boxes, got {col.shape}")
+        if col.size and (int(col.min()) < 0 or int(col.max()) > 255):
+            raise ValueError("box_colors: integers in 0 .. 255")
+    bw = _int_in(box_width, BOX_WIDTHS[0], BOX_WIDTHS[1], "box_width")
+    alpha = _int_in(box_alpha, 0, 256, "box_alpha")
+    scale = _int_in(label_scale, LABEL_SCALES[0], LABEL_SCALES[1], "label_scale")
+    labels = None
+    if box_labels is not None:
+        labels = np.asarray(box_labels)
+        if labels.size == 0:
+            labels = labels.astype(np.int32)                                            # (an empty list has no integer type of its own)
+        if labels.dtype.kind not in "iu" or labels.shape != (N,):
+            raise ValueError(f"box_labels: {N} integers in 0 .. {MAX_LABEL}, got {labels.dtype} {labels.shape}")
+        if labels.size and (int(labels.min()) < 0 or int(labels.max()) > MAX_LABEL):
+            raise ValueError(f"box_labels: integers in 0 .. {MAX_LABEL}")
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+    return np.ascontiguousarray(b, dtype=np.int32), vis, np.ascontiguousarray(col, dtype=np.uint8), bw, alpha, labels, scale
+
+
 def _backend(backend: str) -> bool:
     """True for 'hip' (after its refusal), False for 'host'."""
     if backend not in BACKENDS:
@@ -471,6 +562,52 @@ def _limbs_host(video, t, tracks, visibles, skeleton, limb_colors, ro2, g, reach
             _segment_host(video[t], ax, ay, bx, by, ro2, g, reach, limb_alpha, limb_colors[e])
 
 
+def _blend_rect(image, xa, ya, xb, yb, colour, alpha):
+    """The overlay's blend of `colour` into the part of [xa, xb) x [ya, yb) inside image (H, W, 3) uint8."""
+    H, W = image.shape[:2]
+    xa, ya, xb, yb = max(xa, 0), max(ya, 0), min(xb, W), min(yb, H)
+    if xa >= xb or ya >= yb:
+        return
+    region = image[ya:yb, xa:xb].astype(np.int64)
+    image[ya:yb, xa:xb] = ((region * (256 - alpha) + colour.astype(np.int64) * alpha + 128) >> 8).astype(np.uint8)
+
+
+def _boxes_host(video, boxes, visibles, colors, bw, alpha, labels, scale):
+    """The boxes into video (T, H, W, 3) uint8, frame by frame, box by box in index order: ring, tag, digits (the module text's rule)."""
+    T, H, W = video.shape[:3]
+    for t in range(T):
+        image = video[t]
+        for i in range(boxes.shape[1]):
+            x0, y0, x1, y1 = (int(v) for v in boxes[t, i])
+            if x1 <= x0 or y1 <= y0 or (visibles is not None and not visibles[t, i]):
+                continue
+            col = colors[i]
+            # the ring as four bars: above, below, left and right of the box
+            _blend_rect(image, x0 - bw, y0 - bw, x1 + bw, y0, col, alpha)
+            _blend_rect(image, x0 - bw, y1, x1 + bw, y1 + bw, col, alpha)
+            _blend_rect(image, x0 - bw, y0, x0, y1, col, alpha)
+            _blend_rect(image, x1, y0, x1 + bw, y1, col, alpha)
+            if labels is None:
+                continue
+            text = str(int(labels[i]))
+            tw, th = (6 * len(text) + 1) * scale, 9 * scale
+            ty = y0 - bw - th
+            if ty < 0:
+                ty = y0
+            tx = x0 - bw
+            if tx + tw > W:
+                tx = max(W - tw, 0)
+            _blend_rect(image, tx, ty, tx + tw, ty + th, col, alpha)
+            ink = 255 if 299 * int(col[0]) + 587 * int(col[1]) + 114 * int(col[2]) < 128000 else 0
+            for g, ch in enumerate(text):
+                for r in range(7):
+                    bits = int(DIGITS_5X7[int(ch), r])
+                    for c in range(5):
+                        if (bits >> (4 - c)) & 1:
+                            xa, ya = tx + (1 + 6 * g + c) * scale, ty + (1 + r) * scale
+                            image[max(ya, 0):max(min(ya + scale, H), 0), max(xa, 0):max(min(xa + scale, W), 0)] = ink
+
+
 def _heat_host(video, heat, heat_colors, gain, heat_alpha):
     """The maps heat (T, K, H, W) into video (T, H, W, 3) uint8, map after map (the module text's rule)."""
     cols = heat_colors.astype(np.float64)
@@ -490,7 +627,8 @@ def _heat_host(video, heat, heat_colors, gain, heat_alpha):
 def render(frames, ids=None, tracks=None, visibles=None, colors=None, palette=None, alpha: int = 128, contour: bool = True,
            radius: Optional[int] = None, backend: str = "host", *, trail: Optional[int] = None, linewidth: float = 2.0, trail_fade=None,
            trail_color_by: str = "track", skeleton=None, limb_colors=None, limb_width: float = 2.0, limb_alpha: float = 1.0, heat=None,
-           heat_colors=None, heat_gain: float = 1.0, heat_alpha: float = 0.5):
+           heat_colors=None, heat_gain: float = 1.0, heat_alpha: float = 0.5, boxes=None, box_visibles=None, box_colors=None,
+           box_width: int = 2, box_alpha: int = 255, box_labels=None, label_scale: int = 1):
     """Overlay (when `ids` is given), then points (when `tracks` is given) onto frames (T, H, W, 3) uint8; neither: a copy.  ids (T, H, W)
     uint8, palette (256, 3) uint8 (None: davis_palette()), alpha 0 .. 256; tracks (P, T, 2) as (x, y), visibles (P, T) bool (None: all),
     colors (P, 3) integers 0 .. 255 (None: track_colors(P)), radius 1 .. 31 (None: the reference's round(min(H, W) * 0.015)).
@@ -502,10 +640,29 @@ def render(frames, ids=None, tracks=None, visibles=None, colors=None, palette=No
     after the heat, edge e as a line `limb_width` (1 .. 16) pixels wide of opacity limb_alpha in limb_colors[e] ((E, 3); None: the colour
     of the edge's second joint).  The stages run overlay, heat, limbs, points; trail= goes with neither (one stage per launch: paint the
     trails first and the pose onto that output).
+    boxes (T, N, 4) integers (x0, y0, x1, y1), half-open, N <= 255, coordinates below 2**20 in magnitude (None: no boxes): after the
+    overlay and before the points, box i as a ring `box_width` (1 .. 16) pixels wide OUTSIDE the box in box_colors[i] ((N, 3) integers
+    0 .. 255; None: palette[i], so pass row o for object o) at opacity box_alpha (0 .. 256, the overlay's formula), skipped where it is
+    empty or box_visibles[t, i] ((T, N) bool; None: all) is false; box_labels (N integers 0 .. 999; None: no tags) puts the number on a
+    tag above the box, label_scale (1 .. 4) pixels per bitmap pixel -- the module text has the rule.  boxes= goes with neither trail=
+    nor skeleton= / heat=: render the boxes in place, then paint_trails.  boxes=None: the renderer as it was.
     backend='hip': numpy arrays or CUDA tensors, one launch; returns a CUDA uint8 tensor when `frames` is one, numpy otherwise."""
     pose = _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors, heat_gain, heat_alpha, trail, tracks, True)
+    bx = _box_args(boxes, box_visibles, box_colors, box_width, box_alpha, box_labels, label_scale, trail, skeleton, heat)
     return _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, trail_fade,
-                   trail_color_by, True, pose)
+                   trail_color_by, True, pose, bx)
+
+
+def _box_args(boxes, box_visibles, box_colors, box_width, box_alpha, box_labels, label_scale, trail, skeleton, heat):
+    """The box stage's arguments as a dict, None without boxes; its refusals by name, before any work."""
+    if boxes is None:
+        return None
+    for name, other in (("trail", trail), ("skeleton", skeleton), ("heat", heat)):
+        if other is not None:
+            raise ValueError(f"boxes: not together with {name}= (one stage runs per launch: render the boxes first, in place, and paint "
+                             f"the {'trails' if name == 'trail' else 'pose'} onto that output)")
+    return dict(boxes=boxes, box_visibles=box_visibles, box_colors=box_colors, box_width=box_width, box_alpha=box_alpha,
+                box_labels=box_labels, label_scale=label_scale)
 
 
 def _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors, heat_gain, heat_alpha, trail, tracks, dots):
@@ -526,7 +683,7 @@ def _pose_args(skeleton, limb_colors, limb_width, limb_alpha, heat, heat_colors,
 
 
 def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, backend, trail, linewidth, fade, color_by, dots,
-            pose=None):
+            pose=None, boxes=None):
     hip = _backend(backend)
     on_device = hip and _is_cuda(frames)
     trails = None
@@ -536,9 +693,12 @@ def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radi
         L, lw, fd = _check_trails(trail, linewidth, fade, color_by)
         trails = dict(L=L, linewidth=lw, fade=fd, by_time=color_by == "time", dots=bool(dots))
     if hip:
-        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails, pose)
+        return _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails, pose, boxes)
     f = _numpy(frames)
     _check_frames(f)
+    if boxes is not None:
+        bx = _check_boxes(f.shape, _numpy(boxes["boxes"]), _numpy(boxes["box_visibles"]), _numpy(boxes["box_colors"]), boxes["box_width"],
+                          boxes["box_alpha"], _numpy(boxes["box_labels"]), boxes["label_scale"], _numpy(palette))
     hm = hcol = sk = lcol = pts = None
     with_dots = (trails is None or trails["dots"]) and (pose is None or pose["dots"])
     if ids is not None:
@@ -556,6 +716,8 @@ def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radi
     if ids is not None:
         out = _overlay_host(out, m, pal, a, bool(contour))
     out = np.ascontiguousarray(out)
+    if boxes is not None:
+        _boxes_host(out, *bx)
     if hm is not None:
         _heat_host(out, hm, hcol, pose["heat_gain"], pose["heat_alpha"])
     if sk is not None:
@@ -573,7 +735,7 @@ def _render(frames, ids, tracks, visibles, colors, palette, alpha, contour, radi
     return out
 
 
-def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails=None, pose=None):
+def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, radius, on_device, trails=None, pose=None, boxes=None):
     import torch
     from . import ops
     dev = frames.device if on_device else torch.device("cuda", torch.cuda.current_device())
@@ -626,9 +788,26 @@ def _render_hip(frames, ids, tracks, visibles, colors, palette, alpha, contour, 
         tcol = up(spring_colors(f.shape[0])) if trails["by_time"] and f.dim() == 4 else None
         out = ops.render_trails(f, trail=trails["L"], linewidth=trails["linewidth"], fade=up(trails["fade"]), time_colors=tcol,
                                 dots=trails["dots"], **kw)
+    elif boxes is not None:
+        # the boxes are a few integers a frame: checked on the host (a device tensor is read back), then uploaded as the entry takes them
+        b, vis, col, bw, a, labels, scale = _check_boxes(f.shape if f.dim() == 4 else (0,), _numpy(boxes["boxes"]), _numpy(boxes["box_visibles"]),
+                                                         _numpy(boxes["box_colors"]), boxes["box_width"], boxes["box_alpha"],
+                                                         _numpy(boxes["box_labels"]), boxes["label_scale"], _numpy(palette))
+        out = ops.render_boxes(f, up(b), None if vis is None else up(vis), up(col), bw, a, None if labels is None else up(labels), scale, **kw)
     else:
         out = ops.render_frames(f, **kw)
     return out if on_device else out.cpu().numpy()
+
+
+def paint_boxes(frames, boxes, box_visibles=None, box_colors=None, box_width: int = 2, box_alpha: int = 255, box_labels=None,
+                label_scale: int = 1, palette=None, backend: str = "host"):
+    """frames (T, H, W, 3) uint8 with the boxes (T, N, 4) drawn on as rings with optional id tags (see render and the module text).  With
+    tr = engine.ObjectTracks: paint_boxes(frames, tr.boxes, tr.present, box_labels=range(N)) draws every present object's box in its
+    palette colour with its number; row 0 is the background's (pass box_visibles with column 0 false to leave it out)."""
+    if boxes is None:
+        raise ValueError("boxes: (T, N, 4), got None")
+    return render(frames, palette=palette, backend=backend, boxes=boxes, box_visibles=box_visibles, box_colors=box_colors,
+                  box_width=box_width, box_alpha=box_alpha, box_labels=box_labels, label_scale=label_scale)
 
 
 def paint_trails(frames, point_tracks, visibles=None, colors=None, trail: int = 8, linewidth: float = 2.0, fade=None, color_by: str = "track",

@@ -487,6 +487,20 @@ int fgvc_yuv_out_tile_cols(void);
 int fgvc_jf_counts_u8(const uint8_t* gt, const uint8_t* pred, int T, int h, int w, int n_objects, int radius, int64_t* counts, void* stream);
 int fgvc_jf_tile_rows(void);
 
+/* ---- Objects as boxes: per frame and id, the object's area, box, coordinate sums and border count, all T frames in
+ * one launch; metrics.object_stats_host word for word.
+ *   ids   [T][h][w] uint8 through its own frame and row strides in bytes (pixels are packed: a time slice or a window is read in place).
+ *   stats [T][n_ids][8] int64.  For frame t and id o = 0 .. n_ids - 1 (the background, id 0, has its row like any other), over the pixels
+ *         with ids[t][y][x] == o:  0 area,  1 x0 = min x,  2 y0 = min y,  3 x1 = max x + 1,  4 y1 = max y + 1,  5 sum of x,  6 sum of y,
+ *         7 border = the number of those pixels with x == 0, x == w - 1, y == 0 or y == h - 1.  An id with no pixel on a frame: eight
+ *         zeros.  A pixel whose id is n_ids or more is counted nowhere.
+ * Every element of `stats` is written by one plain store (nothing to clear, no global atomic, no workspace): integer sums, minima and
+ * maxima, the same in any order.  Runs on `stream`; the entry neither allocates nor synchronises.  FGVC_ERR_INVALID_ARG, with a message
+ * naming the argument, for a null ids or stats, n_ids outside 1 .. 256, T, h or w below 1, h w max(h, w) of 2^62 or more, a row stride below w
+ * or a negative frame stride -- all before any launch. */
+int fgvc_seg_object_stats_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int n_ids, int64_t* stats,
+                             void* stream);
+
 /* ---- Render: mask overlay and point icons onto uint8 RGB video, all T frames in one launch; fgvc_amd/viz.py's host
  * backend bit for bit.
  *   frames, out [T][h][w][3] uint8, each through its own frame and row strides in bytes (pixels are packed: 3 bytes); `out` may be `frames`
@@ -559,6 +573,30 @@ int fgvc_render_pose_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t 
                         const uint8_t* limb_colors, double limb_width, double ro2, double g, double limb_alpha, const void* heat, int heat_f64,
                         int K, int64_t heat_stride_t, int64_t heat_stride_k, int64_t heat_stride_y, const uint8_t* heat_colors,
                         double heat_gain, double heat_alpha, void* stream);
+
+/* ---- Boxes and id tags: the renderer above with every object's box drawn between the overlay and the dots -- overlay,
+ * boxes, dots -- still one launch; fgvc_amd/viz.py's host backend bit for bit.  Every argument up to `icon` is the renderer's.
+ *   boxes   [T][N][4] int32 (x0, y0, x1, y1), half-open, frame t at boxes + t boxes_stride_t (in int32s); 0 <= N <= 255.  On frame t the boxes
+ *           are drawn in index order; box i draws nothing when x1 <= x0 or y1 <= y0, when box_visibles[t box_visibles_stride_t + i] == 0
+ *           (null: all are drawn), or when a coordinate is 2^20 or more in magnitude.  Otherwise, with bw = box_width (1 .. 16),
+ *           a = box_alpha (0 .. 256) and C = box_colors[i] ([N][3] uint8), each step on the pixels inside the frame:
+ *   ring    the pixels of [x0 - bw, x1 + bw) x [y0 - bw, y1 + bw) that are not in the box: v_c = (v_c (256 - a) + C_c a + 128) >> 8.
+ *   tag     when box_labels ([N] int32 in 0 .. 999; null: no tags) is given: label has d decimal digits, s = label_scale (1 .. 4),
+ *           tw = (6 d + 1) s, th = 9 s;  ty = y0 - bw - th, or y0 when that is negative;  tx = x0 - bw, or max(w - tw, 0) when
+ *           x0 - bw + tw > w.  The pixels of [tx, tx + tw) x [ty, ty + th) blend as the ring's do.
+ *   digits  tag pixel (px, py) is the tag's own pixel u = (px - tx) / s, r = (py - ty) / s (integer division); for 1 <= r <= 7 and u >= 1
+ *           with g = (u - 1) / 6, cc = (u - 1) % 6 < 5: where bit 4 - cc of row r - 1 of the glyph (digits [10][7] uint8, one byte a row) of the
+ *           label's digit g from the left is set, the pixel becomes white (255) if 299 C_r + 587 C_g + 114 C_b < 128000,
+ *           else black (0), opaque.
+ * Errors as the renderer's, and FGVC_ERR_INVALID_ARG for N, box_width, box_alpha or label_scale out of range, null boxes or box_colors with
+ * N > 0, labels without the digits table, negative frame strides, misaligned boxes or labels.  No workspace, no atomics. */
+int fgvc_render_boxes_u8(const uint8_t* frames, int64_t frames_stride_t, int64_t frames_stride_y, uint8_t* out, int64_t out_stride_t,
+                         int64_t out_stride_y, int T, int h, int w, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                         const uint8_t* palette, int alpha, int contour, const double* tracks, int64_t tracks_stride_p,
+                         int64_t tracks_stride_t, const uint8_t* visibles, int64_t visibles_stride_p, int64_t visibles_stride_t,
+                         const uint8_t* colors, int P, int radius, const double* icon, const int32_t* boxes, int64_t boxes_stride_t,
+                         const uint8_t* box_visibles, int64_t box_visibles_stride_t, const uint8_t* box_colors, int N, int box_width,
+                         int box_alpha, const int32_t* box_labels, int label_scale, const uint8_t* digits, void* stream);
 
 /* ---- A6: coarse-to-fine refine (local_attention.py:721-880), fine stage.
  *   coarse_arg [T][HW] int32: per key slot and query, the coarse cell picked by the coarse stage

@@ -4,6 +4,7 @@ mediapy: frames come and go through PIL).
 
     python tools/demo.py FRAMES_DIR --task points --query-points t x y [t x y ...] --out OUT
     python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
+    python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png [--boxes] [--box-labels] [--object-trails L] [--mot OUT.txt] --out OUT
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task points --query-points t x y ... --trails [L] [--trail-width X] [--trail-color track|time] --out OUT
@@ -37,6 +38,11 @@ propagated maps in, made on the device from the kept field in frame chunks (maps
 demo's second video shows: viz.render(trail=L), still one launch (fgvc_render_trails_u8).  --trail-width is the line
 width in pixels, --trail-color time the reference's colouring by time in place of the point's own colour.  It goes with --chain (a trail stops
 where a chained track ends or is not visible), with --out-video and with --host-render.
+--boxes (--task vos) draws every object's box on every frame it is present on, --box-labels its id on a tag above the box, --object-trails L the
+last L steps of its centroid with a dot on the centroid, and --mot OUT.txt writes the boxes as a MOTChallenge text file: the model runs with
+test_cfg.objects = dict(stats=True) (one launch of fgvc_seg_object_stats_u8 on the masks), viz.render(boxes=...) paints the
+boxes with the overlay in one launch, and the trails are a second call, viz.paint_trails, onto that output.  They go with --mask, --fuse,
+--edge-aware, --out-video and --host-render.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -254,11 +260,15 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     edge = {}
     if a.edge_aware:               # test_cfg.readout: label edges follow the frames' own
         edge = dict(readout=dict(type="guided", radius=a.edge_radius, sigma_space=1.0, sigma_range=a.edge_sigma_range))
+    if wants_objects(a):           # test_cfg.objects: the masks' boxes, centroids and areas, kept in a.objects
+        edge = dict(edge, objects=dict(stats=True))
+    a.objects = None
     if not a.mask:
         mask = _mask_png(a.first_mask, H, W, "--first-mask")
         model = build_model(a, dev, input=_input(a, None), masks="device", **edge)
         with torch.no_grad():
             out = model(test_mode=True, imgs=imgs, ref_seg_map=torch.from_numpy(mask)[None].to(dev), img_meta=meta)
+        a.objects = model.last_objects
         return out[0]
     refs = {}
     if a.first_mask:
@@ -275,6 +285,7 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     with torch.no_grad():
         out = model(test_mode=True, imgs=imgs, ref_seg_map=refs, img_meta=meta)
     lc = model.last_confidence
+    a.objects = model.last_objects
     if a.fuse:
         print("disagree: " + " ".join(str(v) for v in lc["disagree"].tolist()))
         print(f"annotate next by disagreement: frame {engine.next_frame_to_annotate_by(lc['disagree'], refs)}")
@@ -286,6 +297,29 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
         print("frame_score: " + " ".join(f"{v:.4f}" for v in lc["frame_score"].tolist()))
         print(f"annotate next: frame {engine.next_frame_to_annotate(lc['frame_score'], refs)}")
     return out[0]
+
+
+def wants_objects(a) -> bool:
+    return bool(a.boxes or a.box_labels or a.object_trails is not None or a.mot)
+
+
+def box_arguments(a, tr) -> dict:
+    """viz.render's box arguments for an engine.ObjectTracks: the objects 1 .. N - 1 (the background's row is left out, so 255 objects fit
+    the renderer's 255 boxes), each where it is present, in its palette colour, with its id on the tag."""
+    N = tr.present.shape[1]
+    kw = dict(boxes=tr.boxes[:, 1:], box_visibles=tr.present[:, 1:], box_colors=viz.davis_palette()[1:N])
+    if a.box_labels:
+        kw["box_labels"] = np.arange(1, N)
+    return kw
+
+
+def paint_object_trails(a, rendered, tr, backend):
+    """The centroids' last --object-trails steps and a dot on every centroid, onto the rendered frames: viz.paint_trails, a second call."""
+    tracks, vis = tr.centroid_tracks()
+    if tracks.shape[0] <= 1:
+        return rendered
+    colors = viz.davis_palette()[1:tracks.shape[0]]
+    return viz.paint_trails(rendered, tracks[1:], vis[1:], colors=colors, trail=a.object_trails, radius=a.radius, backend=backend)
 
 
 def run_flow(a, frames: np.ndarray, dev) -> dict:
@@ -395,6 +429,10 @@ def parse_args(argv=None):
     ap.add_argument("--edge-radius", type=int, default=2, choices=(1, 2, 3), help="with --edge-aware: cells around a pixel, per side")
     ap.add_argument("--edge-sigma-range", type=float, default=0.1, metavar="X",
                     help="with --edge-aware: the colour sigma in Lab-normalised units (untuned default)")
+    ap.add_argument("--boxes", action="store_true", help="--task vos: draw every object's box (test_cfg.objects, viz.render(boxes=...))")
+    ap.add_argument("--box-labels", action="store_true", help="--task vos: the boxes with the object's id on a tag (implies --boxes)")
+    ap.add_argument("--object-trails", type=int, default=None, metavar="L", help="--task vos: the last L steps (1 .. 64) of every object's centroid")
+    ap.add_argument("--mot", default=None, metavar="OUT.txt", help="--task vos: write the boxes as a MOTChallenge text file")
     ap.add_argument("--out", required=True)
     ap.add_argument("--host-render", action="store_true", help="paint (and, with --out-video, encode) with viz's numpy backend instead of the kernels")
     ap.add_argument("--out-video", default=None, metavar="OUT.y4m", help="also write the result as a YUV4MPEG2 file of 8-bit 4:2:0 frames")
@@ -436,6 +474,10 @@ def parse_args(argv=None):
         ap.error("--both-ways, --override, --fuse and --confidence go with --mask T PNG")
     if (a.edge_aware or a.edge_radius != 2 or a.edge_sigma_range != 0.1) and not (a.task == "vos" and a.edge_aware):
         ap.error("--edge-aware goes with --task vos; --edge-radius and --edge-sigma-range go with --edge-aware")
+    if a.task != "vos" and (a.boxes or a.box_labels or a.object_trails is not None or a.mot):
+        ap.error("--boxes, --box-labels, --object-trails and --mot go with --task vos")
+    if a.object_trails is not None and not 1 <= a.object_trails <= 64:
+        ap.error("--object-trails L: 1 .. 64")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
         ap.error("--yuv-matrix goes with a .y4m clip")
     if a.trails is not None and a.task != "points":
@@ -488,13 +530,23 @@ def main(argv=None):
     kw = dict(ids=ids, tracks=tracks, visibles=visibles, radius=a.radius, alpha=a.alpha, contour=not a.no_contour)
     if a.trails is not None:
         kw.update(trail=a.trails, linewidth=a.trail_width, trail_color_by=a.trail_color)
+    objects = getattr(a, "objects", None)
+    if objects is not None and (a.boxes or a.box_labels):
+        kw.update(box_arguments(a, objects))
+    if objects is not None and a.mot:
+        from fgvc_amd import datasets
+        print(f"{a.mot}: {datasets.write_mot(a.mot, objects)} boxes of {objects.present.shape[1] - 1} object(s) in the MOTChallenge text layout")
     if a.host_render:
         frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
         rendered = viz.render(frames, backend="host", **kw)
+        if objects is not None and a.object_trails is not None:
+            rendered = paint_object_trails(a, rendered, objects, "host")
         packed = write_video(a.out_video, rendered, video, dev, host=True) if video else None
     else:
         on_dev = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev)
         rendered = viz.render(on_dev, backend="hip", **kw)
+        if objects is not None and a.object_trails is not None:
+            rendered = paint_object_trails(a, rendered, objects, "hip")
         packed = write_video(a.out_video, rendered, video, dev) if video else None       # render -> encode on the device
         rendered = rendered.cpu().numpy()
     frames = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames
@@ -502,6 +554,8 @@ def main(argv=None):
     print(f"{a.out}: {len(rendered)} frames of {frames.shape[1]} x {frames.shape[2]} and demo.gif ({a.task}{'' if a.trails is None else f', trails of {a.trails}'}, "
           f"{'host' if a.host_render else 'hip'} renderer)")
     r = dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
+    if objects is not None:
+        r["objects"] = objects
     if video:
         r.update(video=packed.numpy(), video_settings=video)
     return r

@@ -9,6 +9,7 @@
     python tools/test.py CONFIG --task davis --chain [--chain-visibility frame|consistency] [--query-mode strided]   # flow chaining: section 18
     python tools/test.py CONFIG --task davis|vos|jhmdb|badja --raw-frames     # uint8 RGB frames into the model (test_cfg.input): section 14
     python tools/test.py CONFIG --task vos --data-root DIR --gpu-metrics     # masks stay on the device, J&F from fgvc_jf_counts_u8: section 15
+    python tools/test.py CONFIG --task vos --data-root DIR --boxes           # also the mean box IoU per sequence against the annotation's boxes: section 27
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -136,6 +137,10 @@ def main():
     ap.add_argument("--raw-frames", action="store_true",
                     help="hand the decoded uint8 frames to the model (datasets' raw=True) and set test_cfg.input = dict(type='rgb8', size=...): "
                          "resize, RGB -> Lab and normalisation run in the library's input kernel instead of the datasets' torch chain")
+    ap.add_argument("--boxes", action="store_true",
+                    help="--task vos: also print the mean box IoU per sequence of the predicted objects' boxes against the boxes of the "
+                         "ground-truth maps (metrics.mean_box_iou): both from ops.object_stats under --gpu-metrics, from the host contract "
+                         "otherwise")
     ap.add_argument("--gpu-metrics", action="store_true",
                     help="--task vos: keep the propagated masks on the device (test_cfg.masks='device') and score J&F from the counts of "
                          "the library's fgvc_jf_counts_u8 (metrics.davis_jf(backend='hip')): the same numbers, DESIGN.md section 15")
@@ -222,6 +227,8 @@ def main():
             raise SystemExit("--raw-frames runs on one GPU (--launcher none)")
         net_size = {"vos": None, "ytvos": None, **POSE_SIZE}.get(a.task, tuple(a.size))                                  # what each dataset resizes to
         test_cfg = dict(test_cfg, input=dict(type="rgb8", size=net_size, layout="thwc"))
+    if a.boxes and a.task != "vos":
+        raise SystemExit("--boxes goes with --task vos (the boxes of the mask path's objects)")
     if a.gpu_metrics:
         if a.task != "vos":
             raise SystemExit("--gpu-metrics goes with --task vos (the J&F of the mask path)")
@@ -258,8 +265,9 @@ def main():
     if a.task == "vos":        # semi-supervised VOS: the first annotation is propagated (VanillaTracker.forward_test_seg), scored by J&F
         if rank == 0:
             jf = davis_evaluate(model, Davis2017(a.data_root, split="val", device=dev, raw=a.raw_frames),
-                                backend="hip" if a.gpu_metrics else "host")
-            print(json.dumps({"J&F-Mean": round(jf["J&F-Mean"], 4), "J-Mean": round(jf["J-Mean"], 4), "F-Mean": round(jf["F-Mean"], 4)}))
+                                backend="hip" if a.gpu_metrics else "host", boxes=a.boxes)
+            print(json.dumps({"J&F-Mean": round(jf["J&F-Mean"], 4), "J-Mean": round(jf["J-Mean"], 4), "F-Mean": round(jf["F-Mean"], 4),
+                              **({"Box-IoU-Mean": round(jf["Box-IoU-Mean"], 4)} if a.boxes else {})}))
             for name, r in jf["sequences"].items():
                 print(json.dumps({"sequence": name, **{k: round(v, 4) for k, v in r.items()}}))
             if a.out:
