@@ -57,6 +57,12 @@ void yuv_out_tile(int*, int*);
 int jf_counts_launch(const uint8_t*, const uint8_t*, int, int, int, int, int, int64_t*, hipStream_t);
 int jf_tile_rows();
 int object_stats_launch(const uint8_t*, long long, long long, int, int, int, int, int64_t*, hipStream_t);
+int components_launch(const uint8_t*, long long, long long, int, int, int, int, int, int32_t*, hipStream_t);
+int clean_launch(const uint8_t*, long long, long long, int, int, int, int, int, int, int, int, long long, const uint8_t*, uint8_t*, long long,
+                 long long, int64_t*, void*, hipStream_t);
+void ccl_tile(int*, int*);
+long long ccl_blocks(int, int, int);
+size_t clean_workspace_bytes(int, int, int, int);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -822,6 +828,85 @@ int fgvc_seg_object_stats_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t i
                "%s: ids_stride_y: a row stride of at least w = %d bytes and a non-negative frame stride, got %lld, %lld", fn, w,
                (long long)ids_stride_y, (long long)ids_stride_t);
   return object_stats_launch(ids, ids_stride_t, ids_stride_y, T, h, w, n_ids, stats, (hipStream_t)stream);
+}
+
+int fgvc_seg_ccl_tile_rows(void) {
+  int rows, cols;
+  ccl_tile(&rows, &cols);
+  return rows;
+}
+
+int fgvc_seg_ccl_tile_cols(void) {
+  int rows, cols;
+  ccl_tile(&rows, &cols);
+  return cols;
+}
+
+// what the two component entries ask of a map read through its strides
+static int ccl_map_checks(const char* fn, const char* what, const void* p, int64_t stride_t, int64_t stride_y, int T, int h, int w) {
+  FGVC_REQUIRE(p, FGVC_ERR_INVALID_ARG, "%s: %s: null pointer", fn, what);
+  FGVC_REQUIRE(stride_y >= w && (T == 1 || stride_t >= 0), FGVC_ERR_INVALID_ARG,
+               "%s: %s_stride_y: a row stride of at least w = %d bytes and a non-negative frame stride, got %lld, %lld", fn, what, w,
+               (long long)stride_y, (long long)stride_t);
+  return FGVC_OK;
+}
+
+static int ccl_shape_checks(const char* fn, int T, int h, int w, int connectivity) {
+  FGVC_REQUIRE(T >= 1, FGVC_ERR_INVALID_ARG, "%s: T=%d (at least 1)", fn, T);
+  FGVC_REQUIRE(h >= 1, FGVC_ERR_INVALID_ARG, "%s: h=%d (at least 1)", fn, h);
+  FGVC_REQUIRE(w >= 1, FGVC_ERR_INVALID_ARG, "%s: w=%d (at least 1)", fn, w);
+  FGVC_REQUIRE((long long)h * w < (1ll << 31), FGVC_ERR_INVALID_ARG, "%s: h, w = %d, %d: a frame of 2^31 pixels or more (a label is an int32 index)",
+               fn, h, w);
+  FGVC_REQUIRE(connectivity == 4 || connectivity == 8, FGVC_ERR_INVALID_ARG, "%s: connectivity=%d (4 or 8)", fn, connectivity);
+  FGVC_REQUIRE(ccl_blocks(T, h, w) < (1ll << 31), FGVC_ERR_UNSUPPORTED, "%s: T=%d frames of %d x %d: 2^31 tiles or more (one workgroup a tile)", fn,
+               T, h, w);
+  return FGVC_OK;
+}
+
+int fgvc_seg_components_i32(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int connectivity, int background,
+                            int32_t* labels, void* stream) {
+  const char* fn = "fgvc_seg_components_i32";
+  FGVC_REQUIRE(labels, FGVC_ERR_INVALID_ARG, "%s: labels: null pointer", fn);
+  int rc = ccl_shape_checks(fn, T, h, w, connectivity);
+  if (rc != FGVC_OK) return rc;
+  rc = ccl_map_checks(fn, "ids", ids, ids_stride_t, ids_stride_y, T, h, w);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(background == 0 || background == 1, FGVC_ERR_INVALID_ARG, "%s: background=%d (0 or 1)", fn, background);
+  return components_launch(ids, ids_stride_t, ids_stride_y, T, h, w, connectivity, background, labels, (hipStream_t)stream);
+}
+
+size_t fgvc_seg_clean_workspace_bytes(int T, int h, int w, int n_ids) {
+  if (T < 1 || h < 1 || w < 1 || n_ids < 1 || n_ids > 256 || (long long)h * w >= (1ll << 31)) return 0;
+  return clean_workspace_bytes(T, h, w, n_ids);
+}
+
+int fgvc_seg_clean_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int n_ids, int connectivity, int min_area,
+                      int keep_largest, int fill_holes, int64_t max_hole_area, const uint8_t* frame_flags, uint8_t* out, int64_t out_stride_t,
+                      int64_t out_stride_y, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "fgvc_seg_clean_u8";
+  FGVC_REQUIRE(stats, FGVC_ERR_INVALID_ARG, "%s: stats: null pointer", fn);
+  FGVC_REQUIRE(workspace, FGVC_ERR_INVALID_ARG, "%s: workspace: null pointer", fn);
+  FGVC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, FGVC_ERR_INVALID_ARG, "%s: workspace: must be 8-byte aligned", fn);
+  FGVC_REQUIRE(n_ids >= 1 && n_ids <= 256, FGVC_ERR_INVALID_ARG, "%s: n_ids=%d (1 .. 256: the ids are bytes)", fn, n_ids);
+  int rc = ccl_shape_checks(fn, T, h, w, connectivity);
+  if (rc != FGVC_OK) return rc;
+  rc = ccl_map_checks(fn, "ids", ids, ids_stride_t, ids_stride_y, T, h, w);
+  if (rc != FGVC_OK) return rc;
+  rc = ccl_map_checks(fn, "out", out, out_stride_t, out_stride_y, T, h, w);
+  if (rc != FGVC_OK) return rc;
+  FGVC_REQUIRE(T == 1 || out_stride_t >= (h - 1) * (long long)out_stride_y + w, FGVC_ERR_INVALID_ARG,
+               "%s: out_stride_t: the frames of out must not overlap (strides %lld, %lld bytes for %d x %d)", fn, (long long)out_stride_t,
+               (long long)out_stride_y, h, w);
+  FGVC_REQUIRE(out != ids || (out_stride_t == ids_stride_t && out_stride_y == ids_stride_y), FGVC_ERR_INVALID_ARG,
+               "%s: out: in place (out == ids) needs the strides of ids", fn);
+  FGVC_REQUIRE(min_area >= 0, FGVC_ERR_INVALID_ARG, "%s: min_area=%d (at least 0)", fn, min_area);
+  FGVC_REQUIRE(keep_largest == 0 || keep_largest == 1, FGVC_ERR_INVALID_ARG, "%s: keep_largest=%d (0 or 1)", fn, keep_largest);
+  FGVC_REQUIRE(fill_holes == 0 || fill_holes == 1, FGVC_ERR_INVALID_ARG, "%s: fill_holes=%d (0 or 1)", fn, fill_holes);
+  const size_t need = clean_workspace_bytes(T, h, w, n_ids);
+  FGVC_REQUIRE(workspace_bytes >= need, FGVC_ERR_INVALID_ARG, "%s: workspace_bytes=%zu, %zu needed (fgvc_seg_clean_workspace_bytes)", fn,
+               workspace_bytes, need);
+  return clean_launch(ids, ids_stride_t, ids_stride_y, T, h, w, n_ids, connectivity, min_area, keep_largest, fill_holes, max_hole_area, frame_flags,
+                      out, out_stride_t, out_stride_y, stats, workspace, (hipStream_t)stream);
 }
 
 int fgvc_render_tile_rows(void) {

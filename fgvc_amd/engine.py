@@ -798,7 +798,8 @@ def _mask_readout(soft: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, p
 def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Tensor, pad: Tuple[int, int, int, int],
                     out_shape: Tuple[int, int], cfg, channels: Optional[int] = None, stats_out: Optional[list] = None,
                     events: Optional[dict] = None, affinity_stats: Optional[dict] = None, guide: Optional[torch.Tensor] = None,
-                    readout: Optional[ReadoutConfig] = None, objects_out: Optional[list] = None) -> torch.Tensor:
+                    readout: Optional[ReadoutConfig] = None, objects_out: Optional[list] = None, clean: Optional["CleanConfig"] = None,
+                    clean_out: Optional[list] = None) -> torch.Tensor:
     """Semi-supervised VOS for one clip.  feats_hwc: the clip's bank as run_affinity (TrackerConfig) or run_local_affinity (LocalConfig)
     takes it, encoded from the PADDED frames; seg_map (hp, wp) uint8 the padded first-frame index map; pad = (left, right, top, bottom) as
     pad_divide_by gives it; out_shape = (h0, w0).  On the local window the feature grid is whatever the encoder made of the padded
@@ -806,7 +807,9 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     Returns (T, h0, w0) uint8 on the device.  One host synchronisation: reading C = 1 + the largest id of the map at feature
     resolution (F.one_hot infers it the same way, so an id that vanishes there never appears in the output).
     readout (parse_readout's ReadoutConfig) with guide (T, 3, hp, wp) f32, the padded frames: the edge-aware read-out; None: the plain one.
-    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor (test_cfg.objects)."""
+    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor (test_cfg.objects).
+    clean (parse_clean's CleanConfig, test_cfg.clean): frames 1.. -- the read-out's -- are cleaned in place by ops.seg_clean with n_ids = C
+    before the object statistics; frame 0, the given map, is left alone.  clean_out (a list) receives the (T, C, 4) int64 statistics."""
     T, dev = feats_hwc.shape[0], feats_hwc.device
     _record(events, "labels")
     C = int(ops.seg_max_label(seg_map, Hf, Wf).item()) + 1
@@ -819,6 +822,8 @@ def propagate_masks(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_map: torch.Te
     _sweep_labels(bank, soft, sw, Hf, Wf, cfg.hard_prop)
     _record(events, "readout")
     masks = _mask_readout(soft, Hf, Wf, seg_map, pad, out_shape, cfg.norm_mask, guide, readout)
+    if clean is not None:
+        _clean_masks(masks, C, clean, np.arange(T) >= 1, clean_out)
     if objects_out is not None:
         objects_out.append(ops.object_stats(masks, C))
     _record(events, "end")
@@ -1059,7 +1064,8 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
                          out_shape: Tuple[int, int], cfg, rc: RefsConfig, channels: Optional[int] = None, stats_out: Optional[list] = None,
                          confidence: bool = False, sweeps: Optional[dict] = None, counters: Optional[dict] = None,
                          guide: Optional[torch.Tensor] = None, readout: Optional[ReadoutConfig] = None, cells: Optional[torch.Tensor] = None,
-                         disagree_out: Optional[list] = None, objects_out: Optional[list] = None):
+                         disagree_out: Optional[list] = None, objects_out: Optional[list] = None, clean: Optional["CleanConfig"] = None,
+                         clean_out: Optional[list] = None):
     """propagate_masks with index maps at any frames: seg_maps = {frame: padded (hp, wp) uint8 map on the device}; rc names the direction and
     the override rule (sweep_refs_host is the contract).  Returns (T, h0, w0) uint8 on the device; frame s0 (the earliest annotated one) is
     its given map, unpadded and nearest-resized, every other frame the read-out of its rows, frames before s0 under 'forward' zero.
@@ -1070,7 +1076,11 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
     rc.fuse='linear' with more than one annotated frame (fuse_refs_host is the contract): the forward sweep from the first and the backward
     sweep from the last annotated frame, blended between the maps by ops.seg_fuse_rows, then the same read-outs; disagree_out (a list)
     receives the (T,) int64 device tensor of per-frame disagreement counts.  With one annotated frame the call is direction='both'.
-    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor."""
+    objects_out (a list): receives ops.object_stats of the returned masks with n_ids = C, the (T, C, 8) int64 device tensor.
+    clean / clean_out as propagate_masks takes them: every frame a read-out launch wrote is cleaned -- frames s0 + 1 .. T - 1, later annotated
+    frames among them (their maps were injected into the rows, the read-out made the pixels), and frames 0 .. s0 - 1 where the backward
+    pass labels them; frame s0, the given map, and frames that stay zero under 'forward' are left alone.  conf and stats stay the raw
+    read-out's."""
     if readout is not None and guide is None:
         raise ValueError("the guided read-out needs the padded frames (guide=)")
     if isinstance(cfg, LocalConfig):
@@ -1154,6 +1164,11 @@ def propagate_masks_refs(feats_hwc: torch.Tensor, Hf: int, Wf: int, seg_maps: Di
             run(s0 + 1, bw, {}, torch.arange(s0 - 1, -1, -1, device=dev))
     ref = seg_maps[s0][lh:hp - uh, lw:wp - uw].float()[None, None]
     masks[s0] = torch.nn.functional.interpolate(ref, size=tuple(out_shape), mode="nearest")[0, 0].to(torch.uint8)
+    if clean is not None:
+        produced = np.arange(T) > s0
+        if s0 > 0 and (fused or both):
+            produced |= np.arange(T) < s0
+        _clean_masks(masks, C, clean, produced, clean_out)
     if objects_out is not None:
         objects_out.append(ops.object_stats(masks, C))
     if not confidence:
@@ -1430,6 +1445,73 @@ def parse_objects(spec) -> bool:
     if not isinstance(stats, bool):
         raise ValueError(f"test_cfg.objects.stats={stats!r}: True or False")
     return stats
+
+
+CLEAN_KEYS = ("min_area", "keep", "connectivity", "fill_holes", "max_hole_area")
+CLEAN_KEEPS = ("all", "largest")
+
+
+@dataclass(frozen=True)
+class CleanConfig:
+    """test_cfg.clean, parsed: the arguments of ops.seg_clean / metrics.clean_masks_host."""
+    min_area: int = 0
+    keep: str = "all"
+    connectivity: int = 8
+    fill_holes: bool = False
+    max_hole_area: Optional[int] = None
+
+    @property
+    def active(self) -> bool:
+        """whether the rule can change a pixel at all (a component has at least one pixel)"""
+        return self.min_area > 1 or self.keep == "largest" or self.fill_holes
+
+    def kwargs(self) -> dict:
+        return dict(min_area=self.min_area, keep=self.keep, connectivity=self.connectivity, fill_holes=self.fill_holes,
+                    max_hole_area=self.max_hole_area)
+
+
+def parse_clean(spec) -> Optional[CleanConfig]:
+    """test_cfg.clean (an extension key): None -> None; dict(min_area=0, keep='all' | 'largest', connectivity=8 | 4,
+    fill_holes=False, max_hole_area=None) -> a CleanConfig: the index-map call cleans the frames its read-out made (ops.seg_clean) before
+    the object statistics, the scoring and the host copy.  An unknown sub-key, a non-mapping or a bad value raises ValueError naming it.
+    A spec that changes nothing (min_area <= 1, keep='all', no fill) is accepted; the call then launches nothing for it."""
+    if spec is None:
+        return None
+    if not hasattr(spec, "keys"):
+        raise ValueError(f"test_cfg.clean={spec!r}: a dict with the keys {CLEAN_KEYS}")
+    unknown = sorted(set(spec.keys()) - set(CLEAN_KEYS))
+    if unknown:
+        raise ValueError(f"test_cfg.clean: unknown key(s) {unknown}; the keys are {CLEAN_KEYS}")
+
+    def integer(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    min_area = spec.get("min_area", 0)
+    if not integer(min_area) or not 0 <= min_area < 1 << 31:
+        raise ValueError(f"test_cfg.clean.min_area={min_area!r}: an integer 0 .. 2^31 - 1")
+    keep = spec.get("keep", "all")
+    if keep not in CLEAN_KEEPS:
+        raise ValueError(f"test_cfg.clean.keep={keep!r}: one of {CLEAN_KEEPS}")
+    connectivity = spec.get("connectivity", 8)
+    if not integer(connectivity) or connectivity not in (4, 8):
+        raise ValueError(f"test_cfg.clean.connectivity={connectivity!r}: 4 or 8")
+    fill_holes = spec.get("fill_holes", False)
+    if not isinstance(fill_holes, bool):
+        raise ValueError(f"test_cfg.clean.fill_holes={fill_holes!r}: True or False")
+    max_hole_area = spec.get("max_hole_area", None)
+    if max_hole_area is not None and (not integer(max_hole_area) or max_hole_area < 0):
+        raise ValueError(f"test_cfg.clean.max_hole_area={max_hole_area!r}: None or an integer >= 0")
+    return CleanConfig(int(min_area), keep, int(connectivity), fill_holes, None if max_hole_area is None else int(max_hole_area))
+
+
+def _clean_masks(masks: torch.Tensor, C: int, clean: CleanConfig, produced: np.ndarray, clean_out: Optional[list]) -> None:
+    """ops.seg_clean in place on the frames of masks (T, h, w) uint8 whose `produced` entry is true, n_ids = C; the (T, C, 4) int64 statistics
+    go to clean_out.  A spec that changes nothing, or no produced frame: nothing is launched and clean_out receives None."""
+    stats = None
+    if clean.active and produced.any() and masks.numel():
+        flags = None if produced.all() else torch.from_numpy(produced).to(masks.device)
+        _, stats = ops.seg_clean(masks, C, frames=flags, out=masks, **clean.kwargs())
+    if clean_out is not None:
+        clean_out.append(stats)
 
 
 @dataclass

@@ -562,3 +562,127 @@ def mean_box_iou(gt_ids, pred_ids, n_ids: int, backend: str = "host") -> float:
         sg, sp = object_stats_host(host(gt_ids), n_ids), object_stats_host(host(pred_ids), n_ids)
     iou = box_iou(sg[1:, 1:, 1:5], sp[1:, 1:, 1:5])
     return float(np.nanmean(iou)) if np.isfinite(iou).any() else float("nan")
+
+
+# ---- connected components of id maps: the rule of ops.seg_components / ops.seg_clean ----------------------------
+
+def _ids_3d(ids, what="ids") -> np.ndarray:
+    ids = np.asarray(ids)
+    if ids.ndim != 3:
+        raise ValueError(f"{what}: 3 dimensions (T, h, w), got {ids.shape}")
+    if ids.dtype.kind not in "iub":                          # (the mask call's float64 arrays hold small integers)
+        ids = np.rint(ids)
+    return ids.astype(np.int64)
+
+
+def components_host(ids, connectivity: int = 8, background: bool = False) -> np.ndarray:
+    """The contract of ops.seg_components (fgvc_seg_components_i32), in plain Python: ids (T, h, w) integers -> (T, h, w) int32.  Two
+    pixels of a frame belong together when they carry the same id and are neighbours: 4- or 8-neighbours (`connectivity`) for a non-zero
+    id, ALWAYS 4-neighbours for id 0.  A component is a maximal such set, and a pixel's label is the smallest linear index y * w + x of
+    its component (its root).  With background=False the pixels of id 0 get -1.  Frames are independent."""
+    ids = _ids_3d(ids)
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity={connectivity}: 4 or 8")
+    T, h, w = ids.shape
+    out = np.full((T, h, w), -1, np.int32)
+    for t in range(T):
+        m = ids[t].tolist()
+        parent = list(range(h * w))
+
+        def find(a):
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            return a
+
+        def union(a, b):
+            a, b = find(a), find(b)
+            if a != b:                                       # the smaller index stays the root: a root is its component's minimum
+                parent[max(a, b)] = min(a, b)
+
+        for y in range(h):
+            row, up = m[y], m[y - 1] if y else None
+            for x in range(w):
+                v, p = row[x], y * w + x
+                if x and row[x - 1] == v:
+                    union(p, p - 1)
+                if y and up[x] == v:
+                    union(p, p - w)
+                if y and v != 0 and connectivity == 8:
+                    if x and up[x - 1] == v:
+                        union(p, p - w - 1)
+                    if x + 1 < w and up[x + 1] == v:
+                        union(p, p - w + 1)
+        lab = np.array([find(p) for p in range(h * w)], np.int32).reshape(h, w)
+        out[t] = lab if background else np.where(ids[t] != 0, lab, -1)
+    return out
+
+
+def clean_masks_host(ids, n_ids: int, connectivity: int = 8, min_area: int = 0, keep: str = "all", fill_holes: bool = False,
+                     max_hole_area=None, frames=None):
+    """The contract of ops.seg_clean (fgvc_seg_clean_u8): ids (T, h, w) integers 0 .. 255 -> (out (T, h, w) uint8, stats (T, n_ids, 4)
+    int64), out = fill(drop(ids)) per frame, over the components of components_host.
+      drop: a component of an id 1 .. n_ids - 1 becomes 0 when its area is below min_area, and with keep='largest' also when it is not
+            the largest component of its id on the frame (equal areas: the smaller root wins).  Pixels of an id >= n_ids are copied; they
+            take part in nothing and cannot bound a hole.
+      fill (fill_holes, on the map AFTER the drop): a 4-connected component of id 0 becomes id o when it has no pixel on the frame's
+            outermost rows and columns, all its 4-neighbours that are not background carry the one id o < n_ids, and its area is at most
+            max_hole_area (None: any area).
+    frames: (T,) bools; a frame whose entry is false is copied and its stats are zero.  stats[t, o] = components of id o before the drop,
+    components kept, pixels dropped, pixels filled with o; row 0 is four zeros."""
+    ids = _ids_3d(ids)
+    n_ids = int(n_ids)
+    if not 1 <= n_ids <= 256:
+        raise ValueError(f"n_ids={n_ids}: 1 .. 256")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity={connectivity}: 4 or 8")
+    if keep not in ("all", "largest"):
+        raise ValueError(f"keep={keep!r}: 'all' or 'largest'")
+    if ids.size and (ids.min() < 0 or ids.max() > 255):
+        raise ValueError("ids: values 0 .. 255")
+    T, h, w = ids.shape
+    on = np.ones(T, bool) if frames is None else np.asarray(frames).astype(bool)
+    if on.shape != (T,):
+        raise ValueError(f"frames: shape ({T},), got {on.shape}")
+    out = ids.astype(np.uint8)
+    stats = np.zeros((T, n_ids, 4), np.int64)
+    for t in np.nonzero(on)[0].tolist():
+        if h == 0 or w == 0:
+            continue
+        m = out[t]
+        part = (m > 0) & (m < n_ids)
+        lab = components_host(np.where(part, m, 0)[None], connectivity)[0]
+        roots, area = np.unique(lab[part], return_counts=True)           # ascending roots
+        root_id = m.reshape(-1)[roots]
+        dropped = []
+        for o in np.unique(root_id).tolist():
+            sel = np.nonzero(root_id == o)[0]
+            kept = area[sel] >= min_area
+            if keep == "largest":
+                kept &= np.arange(sel.size) == int(np.argmax(area[sel]))   # the first maximum: the smallest root
+            stats[t, o, 0], stats[t, o, 1], stats[t, o, 2] = sel.size, int(kept.sum()), int(area[sel][~kept].sum())
+            dropped.extend(roots[sel][~kept].tolist())
+        m[np.isin(lab, np.array(dropped, np.int32)) & part] = 0
+        if not fill_holes:
+            continue
+        bg = m == 0
+        lab = components_host((~bg)[None], 4, background=True)[0]          # id 0: 4-neighbours
+        n = h * w
+        edge = np.zeros((h, w), bool)
+        edge[0, :] = edge[-1, :] = edge[:, 0] = edge[:, -1] = True
+        open_ = np.zeros(n, bool)
+        open_[lab[bg & edge]] = True
+        lo, hi = np.full(n, 256, np.int64), np.full(n, -1, np.int64)
+        for a, b in (((slice(1, None), slice(None)), (slice(None, -1), slice(None))), ((slice(None, -1), slice(None)), (slice(1, None), slice(None))),
+                     ((slice(None), slice(1, None)), (slice(None), slice(None, -1))), ((slice(None), slice(None, -1)), (slice(None), slice(1, None)))):
+            pair = bg[a] & ~bg[b]                                          # a background pixel and its neighbour that is not
+            np.minimum.at(lo, lab[a][pair], m[b][pair].astype(np.int64))
+            np.maximum.at(hi, lab[a][pair], m[b][pair].astype(np.int64))
+        broots, barea = np.unique(lab[bg], return_counts=True)
+        for r, a in zip(broots.tolist(), barea.tolist()):
+            o = int(lo[r])
+            if open_[r] or lo[r] != hi[r] or o >= n_ids or (max_hole_area is not None and a > max_hole_area):
+                continue
+            m[(lab == r) & bg] = o
+            stats[t, o, 3] += a
+    return out, stats

@@ -105,6 +105,7 @@ class LabelSession:
         model._refuse_occlusion("the mask call (imgs= / ref_seg_map=)")
         model._refuse_refs()
         model._refuse_readout()
+        model._refuse_clean()
         if imgs.shape[0] != 1 or imgs.shape[1] != 1:
             raise NotImplementedError("fgvc_amd: the mask path runs batch size 1; call it once per video")
         if not imgs.is_cuda:
@@ -131,6 +132,7 @@ class LabelSession:
         sweep (engine.fuse_refs_host); the per-frame counts of cells on which the two disagree stay in self.last_disagree, and the session
         keeps the lists of (first annotated frame, 'fw') and (last annotated frame, 'bw') only."""
         self.model.last_objects = None
+        self.model.last_clean = None
         if self.feats is None:
             raise RuntimeError("LabelSession: propagate after close()")
         base = self.model.refs_cfg or engine.RefsConfig()
@@ -141,13 +143,16 @@ class LabelSession:
         segs = {t: torch.nn.functional.pad(m.to(self.device, torch.uint8), self.pad).contiguous() for t, m in maps.items()}
         stats, disagree = [], []
         objects = [] if self.model.objects_stats else None
+        cleaned = []
         out = engine.propagate_masks_refs(self.feats, self.Hf, self.Wf, segs, self.pad, self.out_shape, self.cfg, rc,
                                           channels=self.model.feat_channels, stats_out=stats, confidence=bool(confidence),
                                           sweeps=self._sweeps, counters=self.counters, guide=self.guide,
                                           readout=self.model.readout_cfg if self.guide is not None else None, cells=self.cells,
-                                          disagree_out=disagree, objects_out=objects)
+                                          disagree_out=disagree, objects_out=objects, clean=self.model.clean_cfg, clean_out=cleaned)
         if objects:
             self.model.last_objects = engine.ObjectTracks(objects[0])
+        if cleaned:
+            self.model.last_clean = dict(stats=cleaned[0], config=self.model.clean_cfg)
         self.last_disagree = None
         if rc.fuse is not None:            # one annotated frame: nothing was fused, nothing disagrees
             self.last_disagree = disagree[0].cpu() if disagree else torch.zeros(self.n_frames, dtype=torch.int64)
@@ -185,6 +190,8 @@ class VanillaTracker(BaseTracker):
         self.readout_cfg = engine.parse_readout(self.test_cfg.get("readout", None))   # test_cfg.readout (None / type='bilinear': the plain read-out)
         self.objects_stats = engine.parse_objects(self.test_cfg.get("objects", None))  # test_cfg.objects = dict(stats=True); the index-map call only
         self.last_objects = None           # engine.ObjectTracks of the masks the last index-map call returned with test_cfg.objects set, else None
+        self.clean_cfg = engine.parse_clean(self.test_cfg.get("clean", None))      # test_cfg.clean (None: the read-out's masks are returned as they are)
+        self.last_clean = None             # dict(stats=(T, C, 4) int64 device tensor | None for a spec that changes nothing, config=CleanConfig) of the last index-map call with test_cfg.clean set, else None
 
     # ---- A1/A2: encoder, every frame exactly once, features stay on the device ------------------
     def extract_feat(self, imgs):
@@ -599,6 +606,8 @@ class VanillaTracker(BaseTracker):
         self._refuse_occlusion("the mask / heat-map / soft-map call (imgs= / ref_seg_map=)")
         self._refuse_readout(soft=torch.is_tensor(ref_seg_map) and ref_seg_map.ndim == 4)
         self.last_objects = None
+        self.last_clean = None
+        self._refuse_clean()
         if self.objects_stats and (g("coords", False) or g("return_maps", False)):
             raise NotImplementedError("fgvc_amd: test_cfg.objects describes the id maps of the index-map call; coords=True / return_maps=True "
                                       "(soft labels) return none -- remove one of the keys")
@@ -645,16 +654,26 @@ class VanillaTracker(BaseTracker):
         feats, Hf, Wf = self._label_feats(frames, index_map=True)
         stats, self.label_stats = [], {}
         objects = [] if self.objects_stats else None
+        cleaned = []
         masks = engine.propagate_masks(feats, Hf, Wf, seg, pad, (h0, w0), cfg, channels=self.feat_channels, stats_out=stats,
                                        affinity_stats=self.label_stats, guide=self._readout_guide(frames, Hf, Wf),
-                                       readout=self.readout_cfg, objects_out=objects)
+                                       readout=self.readout_cfg, objects_out=objects, clean=self.clean_cfg, clean_out=cleaned)
         if objects:
             self.last_objects = engine.ObjectTracks(objects[0])
+        if cleaned:
+            self.last_clean = dict(stats=cleaned[0], config=self.clean_cfg)
         self._refine_stats = stats or None
         self._check_kernels()
         if self.masks_form == "device":
             return [masks]
         return [masks.cpu().numpy().astype("float64")]
+
+    def _refuse_clean(self):
+        """test_cfg.clean cleans the id maps of the index-map call: refused by name with the calls that return none."""
+        g = self.test_cfg.get
+        if self.clean_cfg is not None and (g("coords", False) or g("return_maps", False)):
+            raise NotImplementedError("fgvc_amd: test_cfg.clean cleans the id maps of the index-map call; coords=True / return_maps=True "
+                                      "(soft labels) return none -- remove one of the keys")
 
     # ---- the edge-aware read-out: test_cfg.readout (an extension key; DESIGN.md section 24) -------------------------------------------------
     def _refuse_readout(self, soft: bool = False):

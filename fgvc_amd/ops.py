@@ -2114,6 +2114,126 @@ def object_stats(ids: torch.Tensor, n_ids: int, out: Optional[torch.Tensor] = No
     return out
 
 
+# ---- connected components of id maps: labels, despeckle, keep largest, fill holes ------------------------------
+
+CCL_TILE = (16, 64)     # rows, columns one workgroup of the labelling kernels owns (= fgvc_seg_ccl_tile_rows/_cols(); the tests put components on its seams)
+CLEAN_WORDS = ("components", "kept", "dropped_pixels", "filled_pixels")
+
+
+def _ccl_ids(ids: torch.Tensor) -> torch.Tensor:
+    if not ids.is_cuda:
+        raise _lib.FgvcHipError("ids must be on the GPU (fgvc_amd has no CPU path)")
+    if ids.dtype != torch.uint8:
+        raise TypeError(f"ids: expected torch.uint8 object ids, got {ids.dtype}")
+    if ids.dim() != 3:
+        raise ValueError(f"ids: 3 dimensions (T, h, w), got {tuple(ids.shape)}")
+    T, h, w = ids.shape
+    if h * w >= 1 << 31:
+        raise ValueError(f"ids: a frame of {h} x {w} has 2^31 pixels or more")
+    return ids
+
+
+def _strided_rows(m: torch.Tensor) -> bool:
+    return m.stride(2) == 1 and m.stride(1) >= m.shape[2] and m.stride(0) >= 0
+
+
+def seg_components(ids: torch.Tensor, connectivity: int = 8, background: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ids (T, h, w) uint8 on the GPU -> (T, h, w) int32: each pixel's label is the smallest index y * w + x of its connected component
+    -- pixels of one id that are 4- or 8-neighbours (`connectivity`; id 0 always 4) -- and -1 on id 0 unless background=True:
+    metrics.components_host word for word, in three launches of fgvc_seg_components_i32 on the current stream.  The map is read through
+    its frame and row strides (pixels must be packed, else a contiguous copy is made).  `out`: a contiguous (T, h, w) int32 tensor on ids'
+    device; every element is written."""
+    ids = _ccl_ids(ids)
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity={connectivity}: 4 or 8")
+    T, h, w = ids.shape
+    if out is None:
+        out = torch.empty((T, h, w), device=ids.device, dtype=torch.int32)
+    elif tuple(out.shape) != (T, h, w) or out.dtype != torch.int32 or out.device != ids.device or not out.is_contiguous():
+        raise ValueError(f"out: a contiguous int32 tensor of shape {(T, h, w)} on {ids.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if T == 0 or h == 0 or w == 0:
+        return out
+    if not _strided_rows(ids):
+        ids = ids.contiguous()
+    _lib.call("fgvc_seg_components_i32", _ptr(ids), ids.stride(0), ids.stride(1), T, h, w, int(connectivity), int(bool(background)), _ptr(out),
+              _stream(ids))
+    return out
+
+
+def seg_clean_workspace_bytes(T: int, h: int, w: int, n_ids: int) -> int:
+    """The bytes of device memory ops.seg_clean needs as `workspace` for a (T, h, w) map (fgvc_seg_clean_workspace_bytes)."""
+    return int(_lib.load().fgvc_seg_clean_workspace_bytes(int(T), int(h), int(w), int(n_ids)))
+
+
+def seg_clean(ids: torch.Tensor, n_ids: int, connectivity: int = 8, min_area: int = 0, keep: str = "all", fill_holes: bool = False,
+              max_hole_area: Optional[int] = None, frames: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """ids (T, h, w) uint8 on the GPU -> (out (T, h, w) uint8, stats (T, n_ids, 4) int64): out = fill(drop(ids)) per frame,
+    metrics.clean_masks_host word for word (fgvc_seg_clean_u8: four launches, five with keep='largest', four more with fill_holes, on the
+    current stream).  Drop: a component of an id 1 .. n_ids - 1 becomes 0 when it has fewer than min_area pixels, with keep='largest' also
+    when it is not the largest of its id on the frame (equal areas: the smaller root).  Fill: a 4-connected background component inside
+    the frame whose neighbours carry one id o < n_ids, of at most max_hole_area pixels (None: any), becomes o.  frames: (T,) bools on
+    the device; a frame whose entry is false is copied and its stats are zero.  stats[t, o] = CLEAN_WORDS.  ids is read through its frame
+    and row strides (pixels must be packed, else a contiguous copy is made); `out` may be ids itself, or a (T, h, w) uint8 tensor with packed
+    pixels on ids' device that does not overlap it; `stats`: contiguous (T, n_ids, 4) int64; `workspace`: a contiguous uint8 tensor of at least
+    seg_clean_workspace_bytes(T, h, w, n_ids) bytes, whose contents do not matter (allocated when None).  Every element of out and stats
+    is written."""
+    ids = _ccl_ids(ids)
+    n_ids = int(n_ids)
+    if not 1 <= n_ids <= 256:
+        raise ValueError(f"n_ids={n_ids}: 1 .. 256 (the ids are bytes)")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity={connectivity}: 4 or 8")
+    if keep not in ("all", "largest"):
+        raise ValueError(f"keep={keep!r}: 'all' or 'largest'")
+    min_area = int(min_area)
+    if not 0 <= min_area < 1 << 31:
+        raise ValueError(f"min_area={min_area}: 0 .. 2^31 - 1")
+    if max_hole_area is not None and int(max_hole_area) < 0:
+        raise ValueError(f"max_hole_area={max_hole_area}: at least 0, or None")
+    T, h, w = ids.shape
+    dev = ids.device
+    if frames is not None and (tuple(frames.shape) != (T,) or frames.dtype != torch.bool or frames.device != dev):
+        raise ValueError(f"frames: a bool tensor of shape ({T},) on {dev}, got {frames.dtype} {tuple(frames.shape)} on {frames.device}")
+    in_place = out is ids
+    if out is not None and not in_place and (tuple(out.shape) != (T, h, w) or out.dtype != torch.uint8 or out.device != dev
+                                             or not (T == 0 or h == 0 or w == 0 or _strided_rows(out))):
+        raise ValueError(f"out: ids itself or a uint8 tensor of shape {(T, h, w)} with packed pixels on {dev}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    shape = (T, n_ids, 4)
+    if stats is None:
+        stats = torch.empty(shape, device=dev, dtype=torch.int64)
+    elif tuple(stats.shape) != shape or stats.dtype != torch.int64 or stats.device != dev or not stats.is_contiguous():
+        raise ValueError(f"stats: a contiguous int64 tensor of shape {shape} on {dev}, got {stats.dtype} {tuple(stats.shape)} on {stats.device}")
+    if out is None:
+        out = torch.empty((T, h, w), device=dev, dtype=torch.uint8)
+    if T == 0:
+        return out, stats
+    if h == 0 or w == 0:
+        return out, stats.zero_()
+    if not _strided_rows(ids):
+        if in_place:
+            raise ValueError("out: in place needs ids with packed pixels, rows that do not overlap and a non-negative frame stride")
+        ids = ids.contiguous()
+    if in_place:
+        out = ids
+    if (T > 1 and out.stride(0) < (h - 1) * out.stride(1) + w):
+        raise ValueError("out: its frames must not overlap")
+    need = seg_clean_workspace_bytes(T, h, w, n_ids)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"workspace: a contiguous uint8 tensor of at least {need} bytes on {dev} (seg_clean_workspace_bytes), got "
+                         f"{workspace.dtype} of {workspace.numel()} elements on {workspace.device}")
+    if frames is not None:
+        frames = frames.contiguous()
+    _lib.call("fgvc_seg_clean_u8", _ptr(ids), ids.stride(0), ids.stride(1), T, h, w, n_ids, int(connectivity), min_area,
+              int(keep == "largest"), int(bool(fill_holes)), -1 if max_hole_area is None else int(max_hole_area),
+              _ptr(frames) if frames is not None else None, _ptr(out), out.stride(0), out.stride(1), _ptr(stats), _ptr(workspace),
+              workspace.numel(), _stream(ids))
+    return out, stats
+
+
 # ---- render: mask overlay and point icons onto uint8 video (DESIGN.md section 16) -------------------------------------------------------
 
 RENDER_TILE = (8, 256)  # rows, columns one workgroup of fgvc_render_frames_u8 owns (= fgvc_render_tile_rows/_cols(); the tests put points on its corners)

@@ -501,6 +501,37 @@ int fgvc_jf_tile_rows(void);
 int fgvc_seg_object_stats_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int n_ids, int64_t* stats,
                              void* stream);
 
+/* ---- Connected components of id maps: labels, and the cleaning rule on top of them (drop small components or all but
+ * the largest of an id, then fill holes); metrics.components_host and metrics.clean_masks_host word for word.
+ *   ids    [T][h][w] uint8 through its own frame and row strides in bytes (pixels are packed).
+ *   labels [T][h][w] int32, contiguous.  Two pixels of a frame belong together when they carry one id and are neighbours: 4- or 8-neighbours
+ *          (`connectivity`) for a non-zero id, always 4-neighbours for id 0.  A pixel's label is the smallest index y * w + x of its
+ *          component; with background == 0 the pixels of id 0 get -1.  Three launches (tile, seam, flatten); no workspace.
+ * fgvc_seg_clean_u8: out = fill(drop(ids)) per frame.  Drop: a component of an id 1 .. n_ids - 1 becomes 0 when its area is below min_area,
+ * and with keep_largest also when it is not the largest of its id on the frame (equal areas: the smaller root wins); ids >= n_ids are copied
+ * and take part in nothing.  Fill (fill_holes, on the map after the drop): a 4-connected component of id 0 with no pixel on the frame's outermost
+ * rows and columns, whose 4-neighbours that are not background all carry one id o < n_ids, and of at most max_hole_area pixels (negative: any
+ * area), becomes o.  frame_flags [T] uint8 or null: a frame whose flag is 0 is copied and its stats are zero.
+ *   out    [T][h][w] uint8 through its own strides; may be ids itself (same strides), must not overlap it otherwise.
+ *   stats  [T][n_ids][4] int64: components of the id before the drop, components kept, pixels dropped, pixels filled with the id.
+ *   workspace: at least fgvc_seg_clean_workspace_bytes(T, h, w, n_ids) bytes of device memory, 8-byte aligned, owned by the caller.  The kernels
+ *          write every word of it they later read: nothing has to be cleared, and what it held before cannot matter.
+ * Every element of out, stats and labels is written.  Four launches, five with keep_largest, four more with fill_holes, all on `stream`; the
+ * entries neither allocate nor synchronise, and no kernel waits for another workgroup.  All atomics are integer: the outputs do not depend on
+ * the order of arrival.  FGVC_ERR_INVALID_ARG, with a message naming the argument, for a null pointer, n_ids outside 1 .. 256, T, h or w below 1,
+ * a frame of 2^31 pixels or more, a connectivity other than 4 or 8, a row stride below w, a negative frame stride, overlapping frames of out,
+ * other strides for an in-place out, a negative min_area, a flag that is neither 0 nor 1, a workspace that is misaligned or too small;
+ * FGVC_ERR_UNSUPPORTED for 2^31 tiles or more -- all before any launch.  The two tile functions give the rows and columns one workgroup labels
+ * in LDS (tests put components on their multiples). */
+int fgvc_seg_components_i32(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int connectivity, int background,
+                            int32_t* labels, void* stream);
+int fgvc_seg_clean_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y, int T, int h, int w, int n_ids, int connectivity, int min_area,
+                      int keep_largest, int fill_holes, int64_t max_hole_area, const uint8_t* frame_flags, uint8_t* out, int64_t out_stride_t,
+                      int64_t out_stride_y, int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+size_t fgvc_seg_clean_workspace_bytes(int T, int h, int w, int n_ids);
+int fgvc_seg_ccl_tile_rows(void);
+int fgvc_seg_ccl_tile_cols(void);
+
 /* ---- Render: mask overlay and point icons onto uint8 RGB video, all T frames in one launch; fgvc_amd/viz.py's host
  * backend bit for bit.
  *   frames, out [T][h][w][3] uint8, each through its own frame and row strides in bytes (pixels are packed: 3 bytes); `out` may be `frames`

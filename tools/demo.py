@@ -41,7 +41,8 @@ where a chained track ends or is not visible), with --out-video and with --host-
 --boxes (--task vos) draws every object's box on every frame it is present on, --box-labels its id on a tag above the box, --object-trails L the
 last L steps of its centroid with a dot on the centroid, and --mot OUT.txt writes the boxes as a MOTChallenge text file: the model runs with
 test_cfg.objects = dict(stats=True) (one launch of fgvc_seg_object_stats_u8 on the masks), viz.render(boxes=...) paints the
-boxes with the overlay in one launch, and the trails are a second call, viz.paint_trails, onto that output.  They go with --mask, --fuse,
+boxes with the overlay in one launch, and the trails are a second call, viz.paint_trails, onto that output.  --clean [--min-area N] [--keep-largest] [--fill-holes]
+[--max-hole N] cleans the propagated masks first (test_cfg.clean).  They go with --mask, --fuse,
 --edge-aware, --out-video and --host-render.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
@@ -262,13 +263,16 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
         edge = dict(readout=dict(type="guided", radius=a.edge_radius, sigma_space=1.0, sigma_range=a.edge_sigma_range))
     if wants_objects(a):           # test_cfg.objects: the masks' boxes, centroids and areas, kept in a.objects
         edge = dict(edge, objects=dict(stats=True))
-    a.objects = None
+    if a.clean:                    # test_cfg.clean: despeckle, keep the largest part, fill holes -- before the boxes
+        edge = dict(edge, clean=dict(min_area=a.min_area, keep="largest" if a.keep_largest else "all", fill_holes=a.fill_holes,
+                                     max_hole_area=a.max_hole))
+    a.objects = a.cleaned = None
     if not a.mask:
         mask = _mask_png(a.first_mask, H, W, "--first-mask")
         model = build_model(a, dev, input=_input(a, None), masks="device", **edge)
         with torch.no_grad():
             out = model(test_mode=True, imgs=imgs, ref_seg_map=torch.from_numpy(mask)[None].to(dev), img_meta=meta)
-        a.objects = model.last_objects
+        a.objects, a.cleaned = model.last_objects, model.last_clean
         return out[0]
     refs = {}
     if a.first_mask:
@@ -285,7 +289,7 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
     with torch.no_grad():
         out = model(test_mode=True, imgs=imgs, ref_seg_map=refs, img_meta=meta)
     lc = model.last_confidence
-    a.objects = model.last_objects
+    a.objects, a.cleaned = model.last_objects, model.last_clean
     if a.fuse:
         print("disagree: " + " ".join(str(v) for v in lc["disagree"].tolist()))
         print(f"annotate next by disagreement: frame {engine.next_frame_to_annotate_by(lc['disagree'], refs)}")
@@ -433,6 +437,12 @@ def parse_args(argv=None):
     ap.add_argument("--box-labels", action="store_true", help="--task vos: the boxes with the object's id on a tag (implies --boxes)")
     ap.add_argument("--object-trails", type=int, default=None, metavar="L", help="--task vos: the last L steps (1 .. 64) of every object's centroid")
     ap.add_argument("--mot", default=None, metavar="OUT.txt", help="--task vos: write the boxes as a MOTChallenge text file")
+    ap.add_argument("--clean", action="store_true",
+                    help="--task vos: clean the propagated masks on the device before anything reads them (test_cfg.clean, ops.seg_clean)")
+    ap.add_argument("--min-area", type=int, default=0, metavar="N", help="with --clean: drop connected parts of an object below N pixels")
+    ap.add_argument("--keep-largest", action="store_true", help="with --clean: keep only the largest connected part of every object")
+    ap.add_argument("--fill-holes", action="store_true", help="with --clean: fill background enclosed by one object")
+    ap.add_argument("--max-hole", type=int, default=None, metavar="N", help="with --fill-holes: only holes of at most N pixels")
     ap.add_argument("--out", required=True)
     ap.add_argument("--host-render", action="store_true", help="paint (and, with --out-video, encode) with viz's numpy backend instead of the kernels")
     ap.add_argument("--out-video", default=None, metavar="OUT.y4m", help="also write the result as a YUV4MPEG2 file of 8-bit 4:2:0 frames")
@@ -476,6 +486,8 @@ def parse_args(argv=None):
         ap.error("--edge-aware goes with --task vos; --edge-radius and --edge-sigma-range go with --edge-aware")
     if a.task != "vos" and (a.boxes or a.box_labels or a.object_trails is not None or a.mot):
         ap.error("--boxes, --box-labels, --object-trails and --mot go with --task vos")
+    if (a.clean or a.min_area or a.keep_largest or a.fill_holes or a.max_hole is not None) and not (a.task == "vos" and a.clean):
+        ap.error("--clean goes with --task vos; --min-area, --keep-largest, --fill-holes and --max-hole go with --clean")
     if a.object_trails is not None and not 1 <= a.object_trails <= 64:
         ap.error("--object-trails L: 1 .. 64")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
@@ -556,6 +568,11 @@ def main(argv=None):
     r = dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
     if objects is not None:
         r["objects"] = objects
+    if getattr(a, "cleaned", None) is not None:
+        r["clean"] = a.cleaned
+        if a.cleaned["stats"] is not None:
+            st = a.cleaned["stats"][:, 1:].sum((0, 1)).tolist()
+            print(f"clean: {st[0]} component(s), {st[1]} kept, {st[2]} pixel(s) dropped, {st[3]} filled")
     if video:
         r.update(video=packed.numpy(), video_settings=video)
     return r

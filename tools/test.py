@@ -10,6 +10,7 @@
     python tools/test.py CONFIG --task davis|vos|jhmdb|badja --raw-frames     # uint8 RGB frames into the model (test_cfg.input): section 14
     python tools/test.py CONFIG --task vos --data-root DIR --gpu-metrics     # masks stay on the device, J&F from fgvc_jf_counts_u8: section 15
     python tools/test.py CONFIG --task vos --data-root DIR --boxes           # also the mean box IoU per sequence against the annotation's boxes: section 27
+    python tools/test.py CONFIG --task vos --data-root DIR --clean --keep-largest --fill-holes [--min-area N] [--max-hole N]   # test_cfg.clean: section 28
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/test.py CONFIG --launcher pytorch
 
 CONFIG may be the reference's own configs/eval/res18_d1_eval.py.  The TAP-Vid / JHMDB files are not available
@@ -147,6 +148,13 @@ def main():
     ap.add_argument("--readout", choices=["bilinear", "guided"], default=None,
                     help="--task vos: the mask read-out (test_cfg.readout = dict(type=...)); 'guided' is the edge-aware one, whose effect on "
                          "real DAVIS J&F is unmeasured")
+    ap.add_argument("--clean", action="store_true",
+                    help="--task vos: clean the propagated masks on the device before they are scored (test_cfg.clean = dict(...), "
+                         "ops.seg_clean; DESIGN.md section 28); its effect on real DAVIS J&F is unmeasured")
+    ap.add_argument("--min-area", type=int, default=0, metavar="N", help="with --clean: drop connected parts of an object below N pixels")
+    ap.add_argument("--keep-largest", action="store_true", help="with --clean: keep only the largest connected part of every object")
+    ap.add_argument("--fill-holes", action="store_true", help="with --clean: fill background enclosed by one object")
+    ap.add_argument("--max-hole", type=int, default=None, metavar="N", help="with --fill-holes: only holes of at most N pixels")
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-dir", default=None, help="write summaries<task>.json / results_df<task>.csv / results_list<task>.pkl there "
                                                     "(the files of the reference's save_results, tapvid.py:316-350)")
@@ -233,6 +241,14 @@ def main():
         if a.task != "vos":
             raise SystemExit("--gpu-metrics goes with --task vos (the J&F of the mask path)")
         test_cfg = dict(test_cfg, masks="device")
+    if a.clean or a.min_area or a.keep_largest or a.fill_holes or a.max_hole is not None:
+        if not a.clean or a.task not in ("vos", "ytvos"):
+            raise SystemExit("--clean goes with --task vos (the index maps of the mask path); --min-area, --keep-largest, --fill-holes and "
+                             "--max-hole go with --clean")
+        if distributed:
+            raise SystemExit("--clean runs on one GPU (--launcher none); the multi-GPU path is not covered")
+        test_cfg = dict(test_cfg, clean=dict(min_area=a.min_area, keep="largest" if a.keep_largest else "all", fill_holes=a.fill_holes,
+                                             max_hole_area=a.max_hole))
     if a.readout is not None:
         if a.task not in ("vos", "ytvos"):
             raise SystemExit("--readout goes with --task vos (the index-map read-out of the mask path)")
