@@ -115,6 +115,10 @@ SIGNATURES = {
     "fgvc_seg_clean_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
     "fgvc_seg_ccl_tile_rows": (_i, []),
     "fgvc_seg_ccl_tile_cols": (_i, []),
+    "fgvc_seg_object_windows_i64": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "fgvc_frames_object_crops_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+    "fgvc_frames_object_crops_u8": (_i, [_p, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _p, _i, _i, _i, _i, _i, _i, _i, _p, C.c_int64,
+                                         C.c_int64, _i, _i, _p, _i, _p, _p, _p, C.c_size_t, _p]),
     "fgvc_render_frames_u8": (_i, [*_RENDER_HEAD, _p]),
     "fgvc_render_trails_u8": (_i, [*_RENDER_HEAD, _i, C.c_double, C.c_double, C.c_double, _p, _p, _p]),
     "fgvc_render_pose_u8": (_i, [*_RENDER_HEAD, _p, _i, _p, C.c_double, C.c_double, C.c_double, C.c_double, _p, _i, _i, C.c_int64, C.c_int64,

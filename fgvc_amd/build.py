@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "lib", "libfgvc_hip.so")
 LIB_ABLATIONS = os.path.join(HERE, "lib", "libfgvc_hip_ablations.so")      # the same objects, fgvc_set_option accepts the results-wrong profiling switches
-SOURCES = ["capi.hip", "pair_topk.hip", "pair_topk_v5.hip", "conv_split.hip", "conv_s2.hip", "conv64.hip", "stem7.hip", "post.hip", "corr_volume.hip", "corr_volume_f8.hip", "corr_volume_f6.hip", "local.hip", "dense_attend.hip", "refine.hip", "seg.hip", "cycle.hip", "flow.hip", "chain.hip", "input.hip", "input_yuv.hip", "output_yuv.hip", "jf.hip", "render.hip", "trails.hip", "pose.hip", "guided.hip", "fuse.hip", "objects.hip", "boxes.hip", "components.hip"]
+SOURCES = ["capi.hip", "pair_topk.hip", "pair_topk_v5.hip", "conv_split.hip", "conv_s2.hip", "conv64.hip", "stem7.hip", "post.hip", "corr_volume.hip", "corr_volume_f8.hip", "corr_volume_f6.hip", "local.hip", "dense_attend.hip", "refine.hip", "seg.hip", "cycle.hip", "flow.hip", "chain.hip", "input.hip", "input_yuv.hip", "output_yuv.hip", "jf.hip", "render.hip", "trails.hip", "pose.hip", "guided.hip", "fuse.hip", "objects.hip", "boxes.hip", "components.hip", "crops.hip"]
 # every header is a dependency of every object; read from the tree, so a new or regenerated .hpp / .inc (tools/gen_*.py) cannot be forgotten
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))) + [os.path.join(ROOT, "include", "fgvc_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -63,6 +63,11 @@ int clean_launch(const uint8_t*, long long, long long, int, int, int, int, int, 
 void ccl_tile(int*, int*);
 long long ccl_blocks(int, int, int);
 size_t clean_workspace_bytes(int, int, int, int);
+int object_windows_launch(const int64_t*, int, int, const int32_t*, int, int, int, int, int, int, int, int, int, int, int64_t*, hipStream_t);
+size_t object_crops_workspace_bytes(int, int, int, int, int);
+long long object_crops_blocks(int, int, int, int);
+int object_crops_launch(const uint8_t*, int, int, int, long long, long long, long long, long long, const int64_t*, int, int, int, int, int, int, int,
+                        const uint8_t*, long long, long long, int, int, const int32_t*, int, uint8_t*, uint8_t*, void*, hipStream_t);
 int c2f_refine_launch(const int32_t*, const float*, const float*, const float*, int, int, int, int, int, int, int,
                       int, float, int, float*, int32_t*, float*, hipStream_t);
 
@@ -907,6 +912,70 @@ int fgvc_seg_clean_u8(const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stri
                workspace_bytes, need);
   return clean_launch(ids, ids_stride_t, ids_stride_y, T, h, w, n_ids, connectivity, min_area, keep_largest, fill_holes, max_hole_area, frame_flags,
                       out, out_stride_t, out_stride_y, stats, workspace, (hipStream_t)stream);
+}
+
+int fgvc_seg_object_windows_i64(const int64_t* stats, int T, int n_ids, const int32_t* objects, int M, int size_h, int size_w, int pad_q,
+                                int min_side, int smooth, int mask_h, int mask_w, int frame_h, int frame_w, int64_t* windows, void* stream) {
+  const char* fn = "fgvc_seg_object_windows_i64";
+  FGVC_REQUIRE(T >= 0 && M >= 0, FGVC_ERR_INVALID_ARG, "%s: T=%d, M=%d (at least 0)", fn, T, M);
+  FGVC_REQUIRE(n_ids >= 1, FGVC_ERR_INVALID_ARG, "%s: n_ids=%d (at least 1)", fn, n_ids);
+  FGVC_REQUIRE(size_h >= 1 && size_h <= 1024 && size_w >= 1 && size_w <= 1024, FGVC_ERR_INVALID_ARG, "%s: size = %d, %d (1 .. 1024 a side)", fn,
+               size_h, size_w);
+  FGVC_REQUIRE(pad_q >= 0 && pad_q <= 4096, FGVC_ERR_INVALID_ARG, "%s: pad_q=%d (0 .. 4096 = pad 0 .. 4 in 1/1024)", fn, pad_q);
+  FGVC_REQUIRE(min_side >= 1 && min_side <= 32768, FGVC_ERR_INVALID_ARG, "%s: min_side=%d (1 .. 32768)", fn, min_side);
+  FGVC_REQUIRE(smooth >= 0 && smooth < (1 << 20), FGVC_ERR_INVALID_ARG, "%s: smooth=%d (0 .. 2^20 - 1)", fn, smooth);
+  FGVC_REQUIRE(mask_h >= 1 && mask_h <= 32768 && mask_w >= 1 && mask_w <= 32768, FGVC_ERR_INVALID_ARG,
+               "%s: mask_h, mask_w = %d, %d (1 .. 32768)", fn, mask_h, mask_w);
+  FGVC_REQUIRE(frame_h >= 1 && frame_h <= 32768 && frame_w >= 1 && frame_w <= 32768, FGVC_ERR_INVALID_ARG,
+               "%s: frame_h, frame_w = %d, %d (1 .. 32768)", fn, frame_h, frame_w);
+  if (T == 0 || M == 0) return FGVC_OK;
+  FGVC_REQUIRE(stats && objects && windows, FGVC_ERR_INVALID_ARG, "%s: stats, objects or windows: null pointer", fn);
+  FGVC_REQUIRE((long long)T * M < (1ll << 31), FGVC_ERR_INVALID_ARG, "%s: T M = %lld windows (below 2^31)", fn, (long long)T * M);
+  return object_windows_launch(stats, T, n_ids, objects, M, size_h, size_w, pad_q, min_side, smooth, mask_h, mask_w, frame_h, frame_w, windows,
+                               (hipStream_t)stream);
+}
+
+size_t fgvc_frames_object_crops_workspace_bytes(int T, int M, int size_h, int size_w, int max_taps) {
+  if (T < 1 || M < 1 || size_h < 1 || size_h > 1024 || size_w < 1 || size_w > 1024 || max_taps < 4 || max_taps > 256) return 0;
+  return object_crops_workspace_bytes(T, M, size_h, size_w, max_taps);
+}
+
+int fgvc_frames_object_crops_u8(const uint8_t* frames, int T, int H, int W, int64_t frames_stride_t, int64_t frames_stride_y,
+                                int64_t frames_stride_x, int64_t frames_stride_c, const int64_t* windows, int window_words, int M, int size_h,
+                                int size_w, int fill_r, int fill_g, int fill_b, const uint8_t* ids, int64_t ids_stride_t, int64_t ids_stride_y,
+                                int mask_h, int mask_w, const int32_t* objects, int max_taps, uint8_t* crops, uint8_t* masks, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  const char* fn = "fgvc_frames_object_crops_u8";
+  FGVC_REQUIRE(T >= 0 && M >= 0, FGVC_ERR_INVALID_ARG, "%s: T=%d, M=%d (at least 0)", fn, T, M);
+  FGVC_REQUIRE(H >= 1 && H <= 32768 && W >= 1 && W <= 32768, FGVC_ERR_INVALID_ARG, "%s: H, W = %d, %d (1 .. 32768)", fn, H, W);
+  FGVC_REQUIRE(window_words == 4 || window_words == 8, FGVC_ERR_INVALID_ARG, "%s: window_words=%d (4 or 8)", fn, window_words);
+  FGVC_REQUIRE(size_h >= 1 && size_h <= 1024 && size_w >= 1 && size_w <= 1024, FGVC_ERR_INVALID_ARG, "%s: size = %d, %d (1 .. 1024 a side)", fn,
+               size_h, size_w);
+  FGVC_REQUIRE(max_taps >= 4 && max_taps <= 256, FGVC_ERR_INVALID_ARG, "%s: max_taps=%d (4 .. 256 taps per axis)", fn, max_taps);
+  FGVC_REQUIRE((unsigned)fill_r < 256u && (unsigned)fill_g < 256u && (unsigned)fill_b < 256u, FGVC_ERR_INVALID_ARG,
+               "%s: fill = %d, %d, %d (bytes)", fn, fill_r, fill_g, fill_b);
+  FGVC_REQUIRE((masks != nullptr) == (ids != nullptr), FGVC_ERR_INVALID_ARG, "%s: ids and masks: both or neither", fn);
+  if (T == 0 || M == 0) return FGVC_OK;
+  FGVC_REQUIRE(frames && windows && crops, FGVC_ERR_INVALID_ARG, "%s: frames, windows or crops: null pointer", fn);
+  FGVC_REQUIRE((reinterpret_cast<uintptr_t>(windows) & 7u) == 0, FGVC_ERR_INVALID_ARG, "%s: windows: must be 8-byte aligned", fn);
+  if (ids) {
+    FGVC_REQUIRE(objects, FGVC_ERR_INVALID_ARG, "%s: objects: null pointer with ids", fn);
+    FGVC_REQUIRE(mask_h >= 1 && mask_h <= 32768 && mask_w >= 1 && mask_w <= 32768, FGVC_ERR_INVALID_ARG,
+                 "%s: mask_h, mask_w = %d, %d (1 .. 32768)", fn, mask_h, mask_w);
+    FGVC_REQUIRE(ids_stride_y >= mask_w && (T == 1 || ids_stride_t >= 0), FGVC_ERR_INVALID_ARG,
+                 "%s: ids_stride_y: a row stride of at least mask_w = %d bytes and a non-negative frame stride, got %lld, %lld", fn, mask_w,
+                 (long long)ids_stride_y, (long long)ids_stride_t);
+  }
+  FGVC_REQUIRE(object_crops_blocks(T, M, size_h, size_w) > 0, FGVC_ERR_INVALID_ARG, "%s: T M = %lld crops of %d x %d: too many workgroups", fn,
+               (long long)T * M, size_h, size_w);
+  FGVC_REQUIRE(workspace, FGVC_ERR_INVALID_ARG, "%s: workspace: null pointer", fn);
+  FGVC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, FGVC_ERR_INVALID_ARG, "%s: workspace: must be 4-byte aligned", fn);
+  const size_t need = object_crops_workspace_bytes(T, M, size_h, size_w, max_taps);
+  FGVC_REQUIRE(workspace_bytes >= need, FGVC_ERR_INVALID_ARG, "%s: workspace_bytes=%zu, %zu needed (fgvc_frames_object_crops_workspace_bytes)",
+               fn, workspace_bytes, need);
+  return object_crops_launch(frames, T, H, W, frames_stride_t, frames_stride_y, frames_stride_x, frames_stride_c, windows, window_words, M, size_h,
+                             size_w, fill_r, fill_g, fill_b, ids, ids_stride_t, ids_stride_y, mask_h, mask_w, objects, max_taps, crops, masks,
+                             workspace, (hipStream_t)stream);
 }
 
 int fgvc_render_tile_rows(void) {

@@ -1570,6 +1570,105 @@ class ObjectTracks:
         c = np.nan_to_num(self.centroids - 0.5, nan=0.0)
         return np.ascontiguousarray(c.transpose(1, 0, 2)), np.ascontiguousarray(self.present.T)
 
+    def _on_device(self) -> bool:
+        return isinstance(self.stats, torch.Tensor) and self.stats.is_cuda
+
+    def windows(self, size, pad: float = 0.125, min_side: int = 8, smooth: int = 0, mask_size=None, frame_size=None, objects=None):
+        """The crop windows (T, M, 8) int64 that follow the objects (default: ids 1 .. N - 1), by the window rule of
+        metrics.object_windows_host: words 0 .. 3 in the pixels of mask_size = (h, w), the id map the statistics
+        came from, words 4 .. 7 in those of frame_size = (H, W) (None: mask_size).  With `stats` on the GPU: one launch of
+        ops.object_windows, the result stays there and nothing is read back; with host stats: the host contract, a numpy array."""
+        if self._on_device():
+            return ops.object_windows(self.stats, size, pad, min_side, smooth, mask_size, frame_size, objects)
+        from . import metrics
+        s = self.stats.detach().numpy() if isinstance(self.stats, torch.Tensor) else np.asarray(self.stats)
+        return metrics.object_windows_host(s, size, pad, min_side, smooth, mask_size, frame_size, objects)
+
+    def crops(self, frames_u8, size=(128, 128), pad: float = 0.125, min_side: int = 8, smooth: int = 0, mask_size=None, objects=None,
+              masks: bool = False, ids=None, layout: str = "thwc", fill=None) -> "ObjectCrops":
+        """An ObjectCrops of the uint8 RGB frames ((T, H, W, 3) 'thwc' or (T, 3, H, W) 'tchw'): every object's window (`windows`, with
+        frame_size the frames' own, which may be larger than the mask: a clip tracked at 480p, cropped from its 1080p source) resampled
+        onto `size` by the rule of viz.crop_windows_host.  masks=True with ids (T, h, w) uint8, the id map: also every object's mask in
+        its window.  mask_size: None takes ids' size, without ids the frames'.  With `stats` on the GPU the frames (and ids) are GPU
+        tensors and the chain is ops.object_windows + ops.object_crops: three launches, nothing read back, the results stay on the
+        device.  With host stats: numpy arrays through the two host contracts."""
+        if layout not in ops.INPUT_LAYOUTS:
+            raise ValueError(f"layout={layout!r}: one of {ops.INPUT_LAYOUTS}")
+        if masks and ids is None:
+            raise ValueError("masks=True needs ids=, the (T, h, w) id map")
+        shape = tuple(frames_u8.shape)
+        if len(shape) != 4:
+            raise ValueError(f"frames_u8: 4 dimensions, got {shape}")
+        frame_size = shape[1:3] if layout == "thwc" else shape[2:4]
+        if mask_size is None:
+            mask_size = tuple(ids.shape[1:3]) if ids is not None else frame_size
+        n_ids = self.stats.shape[1]
+        objs = list(range(1, n_ids)) if objects is None else [int(o) for o in objects]
+        win = self.windows(size, pad, min_side, smooth, mask_size, frame_size, objs)
+        size = (int(size[0]), int(size[1]))
+        if self._on_device():
+            got = ops.object_crops(frames_u8, win, size, layout, fill, ids if masks else None, objs if masks else None)
+        else:
+            from . import viz
+            f = frames_u8.detach().cpu().numpy() if isinstance(frames_u8, torch.Tensor) else np.asarray(frames_u8)
+            m = None if not masks else (ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids))
+            f = f if layout == "thwc" else f.transpose(0, 2, 3, 1)
+            got = viz.crop_windows_host(f, win, size, None if fill is None else np.asarray(fill, np.uint8), m, objs if masks else None)
+        c, mk = got if masks else (got, None)
+        return ObjectCrops(c, mk, win, objs, size)
+
+
+@dataclass
+class ObjectCrops:
+    """What ObjectTracks.crops returns: crops (T, M, S_h, S_w, 3) uint8, masks (T, M, S_h, S_w) uint8 or None, windows (T, M, 8) int64
+    (tensors on the device or arrays, as the chain made them), objects (the M ids) and size = (S_h, S_w).  to_crop / from_crop are the
+    affine map between frame pixels and crop pixels of window (t, j), on the host: frame x in [fx0, fx1) <-> crop x in [0, S_w)."""
+    crops: object
+    masks: object
+    windows: object
+    objects: List[int]
+    size: Tuple[int, int]
+    _host_windows: Optional[np.ndarray] = field(default=None, init=False, repr=False, compare=False)
+
+    def _host(self) -> np.ndarray:
+        if self._host_windows is None:
+            w = self.windows
+            self._host_windows = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+        return self._host_windows
+
+    def _win(self, t: int, j: int):
+        x0, y0, x1, y1 = (float(v) for v in self._host()[t, j, -4:])
+        if x1 <= x0 or y1 <= y0:
+            raise ValueError(f"window ({t}, {j}) is empty: the object is absent on that frame")
+        return x0, y0, x1, y1
+
+    @property
+    def valid(self) -> np.ndarray:
+        """(T, M) bool: the window is not empty (the object is present on the frame)"""
+        w = self._host()
+        return (w[..., -2] > w[..., -4]) & (w[..., -1] > w[..., -3])
+
+    def to_crop(self, xy, t: int, j: int, pixel_centers: bool = False) -> np.ndarray:
+        """Frame coordinates (..., 2) as (x, y) -> coordinates in crop (t, j), float64.  The coordinates are continuous, a pixel p covering
+        [p, p + 1); with pixel_centers=True they are pixel indices (the centre of pixel p is p) on both sides."""
+        x0, y0, x1, y1 = self._win(t, j)
+        p = np.asarray(xy, np.float64)
+        if p.shape[-1] != 2:
+            raise ValueError(f"xy: (..., 2) as (x, y), got {p.shape}")
+        half = 0.5 if pixel_centers else 0.0
+        s = np.array([self.size[1] / (x1 - x0), self.size[0] / (y1 - y0)])
+        return (p + half - np.array([x0, y0])) * s - half
+
+    def from_crop(self, xy, t: int, j: int, pixel_centers: bool = False) -> np.ndarray:
+        """The inverse of to_crop: coordinates in crop (t, j) -> frame coordinates."""
+        x0, y0, x1, y1 = self._win(t, j)
+        p = np.asarray(xy, np.float64)
+        if p.shape[-1] != 2:
+            raise ValueError(f"xy: (..., 2) as (x, y), got {p.shape}")
+        half = 0.5 if pixel_centers else 0.0
+        s = np.array([(x1 - x0) / self.size[1], (y1 - y0) / self.size[0]])
+        return (p + half) * s + np.array([x0, y0]) - half
+
 
 def backward_fields(feats_hwc: torch.Tensor, Hf: int, Wf: int, cfg: LocalConfig, scale: int, stats: Optional[dict] = None) -> torch.Tensor:
     """The clip's T - 1 backward coordinate fields (T-1, HW, 2) f32, (x, y) image pixels interleaved: fields[g - 1] = get_coord(query =

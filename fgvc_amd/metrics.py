@@ -686,3 +686,88 @@ def clean_masks_host(ids, n_ids: int, connectivity: int = 8, min_area: int = 0, 
             m[(lab == r) & bg] = o
             stats[t, o, 3] += a
     return out, stats
+
+
+# ---- object crops: the window rule ------------------------------------------------------------------------------
+
+WINDOW_MAX_SIDE = 32768        # mask and frame sides above it are refused
+WINDOW_MAX_SIZE = 1024         # output sides S_h, S_w: 1 .. 1024
+WINDOW_MAX_PAD = 4.0
+WINDOW_PAD_ONE = 1024          # pad crosses the C ABI as pad_q = int(round(pad * 1024))
+
+
+def window_args(n_ids: int, size, pad, min_side, smooth, mask_size, frame_size, objects):
+    """The host half of the window rule, shared by object_windows_host and ops.object_windows: checks every argument by name and returns
+    (objects list, S_h, S_w, pad_q, min_side, smooth, h, w, H, W) as Python ints."""
+    try:
+        S_h, S_w = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size={size!r}: (S_h, S_w)") from None
+    if not (1 <= S_h <= WINDOW_MAX_SIZE and 1 <= S_w <= WINDOW_MAX_SIZE):
+        raise ValueError(f"size={tuple(size)}: S_h and S_w in 1 .. {WINDOW_MAX_SIZE}")
+    pad = float(pad)
+    if not 0.0 <= pad <= WINDOW_MAX_PAD:                        # (NaN fails both comparisons)
+        raise ValueError(f"pad={pad}: 0 .. {WINDOW_MAX_PAD:g}")
+    pad_q = int(round(pad * WINDOW_PAD_ONE))
+    min_side, smooth = int(min_side), int(smooth)
+    if not 1 <= min_side <= WINDOW_MAX_SIDE:
+        raise ValueError(f"min_side={min_side}: 1 .. {WINDOW_MAX_SIDE}")
+    if not 0 <= smooth < 1 << 20:
+        raise ValueError(f"smooth={smooth}: 0 .. 2^20 - 1 frames on each side")
+    if mask_size is None:
+        raise ValueError("mask_size: (h, w) of the id map the statistics were taken from")
+    h, w = (int(s) for s in mask_size)
+    H, W = (h, w) if frame_size is None else (int(s) for s in frame_size)
+    for name, v in (("mask_size h", h), ("mask_size w", w), ("frame_size H", H), ("frame_size W", W)):
+        if not 1 <= v <= WINDOW_MAX_SIDE:
+            raise ValueError(f"{name}={v}: 1 .. {WINDOW_MAX_SIDE}")
+    objects = list(range(1, n_ids)) if objects is None else [int(o) for o in objects]
+    for o in objects:
+        if not 0 <= o < n_ids:
+            raise ValueError(f"objects: id {o} outside 0 .. {n_ids - 1} (the statistics have {n_ids} rows)")
+    return objects, S_h, S_w, pad_q, min_side, smooth, h, w, H, W
+
+
+def _cdiv(a: int, b: int) -> int:
+    """ceiling division, right for negative numerators too (b > 0)"""
+    return -((-a) // b)
+
+
+def object_windows_host(stats, size, pad: float = 0.125, min_side: int = 8, smooth: int = 0, mask_size=None, frame_size=None,
+                        objects=None) -> np.ndarray:
+    """The contract of ops.object_windows (fgvc_seg_object_windows_i64), in Python integers: stats (T, N, 8) int64 as object_stats_host
+    gives them -> windows (T, M, 8) int64 for the M ids of `objects` (default 1 .. N - 1).  size = (S_h, S_w) the crop's size, pad 0 .. 4
+    as pad_q = int(round(pad * 1024)), min_side >= 1, smooth = r >= 0 frames on each side, mask_size = (h, w) of the id map, frame_size
+    = (H, W) of the frames the crops are taken from (None: mask_size).  // is floor division and cdiv ceiling division.  For frame t, id o:
+        U = {u : |u - t| <= r, 0 <= u < T, area[u, o] > 0};  area[t, o] == 0: eight zeros (no window).  Otherwise n = |U|,
+        Wm = max_U (x1 - x0), Hm = max_U (y1 - y0)                              (the maximum: smoothing never clips the object)
+        Wp = max(min_side, Wm + 2 cdiv(Wm pad_q, 1024)), Hp likewise
+        Wp S_h < Hp S_w: Wp = cdiv(Hp S_w, S_h), else Hp = cdiv(Wp S_h, S_w)    (the output's aspect, by growing one side)
+        wx0 = (sum_U (x0 + x1) - n Wp) // (2 n), wx1 = wx0 + Wp, y likewise     (never clamped: the window may leave the frame)
+    words 0 .. 3: (wx0, wy0, wx1, wy1) in mask pixels; words 4 .. 7: (wx0 W // w, wy0 H // h, cdiv(wx1 W, w), cdiv(wy1 H, h)) in frame
+    pixels -- the same four with frame_size == mask_size."""
+    s = np.asarray(stats)
+    if s.ndim != 3 or s.shape[2] != 8 or s.dtype != np.int64:
+        raise ValueError(f"stats: (T, N, 8) int64, got {s.dtype} {s.shape}")
+    T, N = s.shape[:2]
+    objects, S_h, S_w, pad_q, min_side, r, h, w, H, W = window_args(N, size, pad, min_side, smooth, mask_size, frame_size, objects)
+    out = np.zeros((T, len(objects), 8), np.int64)
+    for j, o in enumerate(objects):
+        rows = s[:, o].tolist()
+        for t in range(T):
+            if rows[t][0] <= 0:
+                continue
+            U = [rows[u] for u in range(max(0, t - r), min(T, t + r + 1)) if rows[u][0] > 0]
+            n = len(U)
+            Wm, Hm = max(u[3] - u[1] for u in U), max(u[4] - u[2] for u in U)
+            Wp = max(min_side, Wm + 2 * _cdiv(Wm * pad_q, WINDOW_PAD_ONE))
+            Hp = max(min_side, Hm + 2 * _cdiv(Hm * pad_q, WINDOW_PAD_ONE))
+            if Wp * S_h < Hp * S_w:
+                Wp = _cdiv(Hp * S_w, S_h)
+            else:
+                Hp = _cdiv(Wp * S_h, S_w)
+            wx0 = (sum(u[1] + u[3] for u in U) - n * Wp) // (2 * n)
+            wy0 = (sum(u[2] + u[4] for u in U) - n * Hp) // (2 * n)
+            wx1, wy1 = wx0 + Wp, wy0 + Hp
+            out[t, j] = (wx0, wy0, wx1, wy1, wx0 * W // w, wy0 * H // h, _cdiv(wx1 * W, w), _cdiv(wy1 * H, h))
+    return out

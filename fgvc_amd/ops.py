@@ -2234,6 +2234,163 @@ def seg_clean(ids: torch.Tensor, n_ids: int, connectivity: int = 8, min_area: in
     return out, stats
 
 
+# ---- object crops: windows that follow each object, resampled on the device -----------------------------------------
+
+def _objects_tensor(objects, device) -> torch.Tensor:
+    return torch.tensor(list(objects), dtype=torch.int32, device=device)
+
+
+def object_windows(stats: torch.Tensor, size, pad: float = 0.125, min_side: int = 8, smooth: int = 0, mask_size=None, frame_size=None,
+                   objects=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """stats (T, N, 8) int64 on the GPU, as object_stats gives them -> windows (T, M, 8) int64 for the M ids of `objects` (a sequence of
+    Python ints on the host; default 1 .. N - 1): per frame and object the crop window of size's aspect around the object's box, grown by
+    `pad` and at least `min_side`, averaged over the `smooth` frames on each side on which the object is present; words 0 .. 3 in mask
+    pixels (mask_size = (h, w)), words 4 .. 7 in the pixels of frame_size = (H, W) (None: mask_size); eight zeros where the object is
+    absent -- metrics.object_windows_host word for word, in one launch of fgvc_seg_object_windows_i64 on the current stream.  Nothing is read
+    back.  Refused by name before the launch: a size outside 1 .. 1024, pad outside 0 .. 4, a side above 32768, an id outside 0 .. N - 1.
+    `out`: a contiguous (T, M, 8) int64 tensor on stats' device; every element is written."""
+    from . import metrics
+    if not isinstance(stats, torch.Tensor) or not stats.is_cuda:
+        raise _lib.FgvcHipError("stats must be on the GPU (fgvc_amd has no CPU path; metrics.object_windows_host is the host contract)")
+    if stats.dtype != torch.int64 or stats.dim() != 3 or stats.shape[2] != 8:
+        raise ValueError(f"stats: (T, N, 8) int64, got {stats.dtype} {tuple(stats.shape)}")
+    T, N = stats.shape[:2]
+    objs, S_h, S_w, pad_q, min_side, smooth, h, w, H, W = metrics.window_args(N, size, pad, min_side, smooth, mask_size, frame_size, objects)
+    M = len(objs)
+    out = _out(out, (T, M, 8), torch.int64, stats.device)
+    if T == 0 or M == 0:
+        return out
+    stats = stats.contiguous()
+    o = _objects_tensor(objs, stats.device)
+    _lib.call("fgvc_seg_object_windows_i64", _ptr(stats), T, N, _ptr(o), M, S_h, S_w, pad_q, min_side, smooth, h, w, H, W, _ptr(out),
+              _stream(stats))
+    return out
+
+
+def _crop_size(size) -> Tuple[int, int]:
+    from . import viz
+    try:
+        S_h, S_w = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size={size!r}: (S_h, S_w)") from None
+    if not (1 <= S_h <= viz.CROP_MAX_SIZE and 1 <= S_w <= viz.CROP_MAX_SIZE):
+        raise ValueError(f"size={tuple(size)}: S_h and S_w in 1 .. {viz.CROP_MAX_SIZE}")
+    return S_h, S_w
+
+
+def _crop_taps(max_taps, frame_size, size) -> int:
+    from . import viz
+    taps = viz.crop_default_taps(frame_size, size) if max_taps is None else int(max_taps)
+    if not 4 <= taps <= viz.CROP_MAX_TAPS:
+        raise ValueError(f"max_taps={taps}: 4 .. {viz.CROP_MAX_TAPS} taps per axis")
+    return taps
+
+
+def object_crops_workspace_bytes(T: int, M: int, size, frame_size=None, max_taps: Optional[int] = None) -> int:
+    """The bytes of device memory ops.object_crops needs as `workspace` for T x M crops of `size` (fgvc_frames_object_crops_workspace_bytes):
+    the coefficient table, 4 (S_h + S_w)(2 + max_taps) bytes a crop.  max_taps None: viz.crop_default_taps(frame_size, size), what
+    object_crops takes by default for frames of frame_size = (H, W).  Known on the host without reading a window back."""
+    S_h, S_w = _crop_size(size)
+    if max_taps is None and frame_size is None:
+        raise ValueError("frame_size: (H, W) of the frames, or max_taps")
+    taps = _crop_taps(max_taps, frame_size, (S_h, S_w))
+    if int(T) < 1 or int(M) < 1:
+        return 0
+    return int(_lib.load().fgvc_frames_object_crops_workspace_bytes(int(T), int(M), S_h, S_w, taps))
+
+
+def object_crops(frames_u8: torch.Tensor, windows: torch.Tensor, size, layout: str = "thwc", fill=None, ids: Optional[torch.Tensor] = None,
+                 objects=None, out: Optional[torch.Tensor] = None, mask_out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None, max_taps: Optional[int] = None):
+    """uint8 RGB frames (T, H, W, 3) ('thwc') or (T, 3, H, W) ('tchw') on the GPU and windows (T, M, 8) int64 as object_windows gives them
+    -- or (T, M, 4) integer windows (x0, y0, x1, y1) of the caller's own -- -> crops (T, M, S_h, S_w, 3) uint8: every window resampled onto
+    size = (S_h, S_w) with the triangle filter widened by the scale (anti-aliased; Pillow's BILINEAR resize with box=), fixed-point
+    coefficients, horizontal pass then vertical with a uint8 intermediate, everything outside the frame `fill` ((3,) uint8 values on the
+    host, default zeros) -- viz.crop_windows_host byte for byte, in two launches of fgvc_frames_object_crops_u8 on the current stream.
+    With ids (T, h, w) uint8 and objects (M ids, Python ints) also masks (T, M, S_h, S_w) uint8 (255 where the nearest pixel of the
+    mask-space window carries the object's id), returned as a pair.  The frames are read through their strides (a slice, a window of a
+    larger tensor, a permuted view is not copied); ids through its frame and row strides.  A window that is empty, has a coordinate of
+    2^30 or more in magnitude or needs more than max_taps taps on an axis (viz.crop_window_ok; max_taps None:
+    viz.crop_default_taps, enough for windows up to twice the frame's side; at most 256) gives a crop of `fill` and a mask of zeros.
+    `out`, `mask_out`: contiguous uint8 tensors of those shapes; `workspace`: a contiguous uint8 tensor of at least
+    object_crops_workspace_bytes(T, M, size, (H, W), max_taps) bytes whose contents do not matter (allocated when None).  Nothing is read
+    back."""
+    if layout not in INPUT_LAYOUTS:
+        raise ValueError(f"layout={layout!r}: one of {INPUT_LAYOUTS}")
+    if not frames_u8.is_cuda:
+        raise _lib.FgvcHipError("frames_u8 must be on the GPU (fgvc_amd has no CPU path; viz.crop_windows_host is the host contract)")
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError(f"frames_u8: expected torch.uint8, got {frames_u8.dtype}")
+    if frames_u8.dim() != 4:
+        raise ValueError(f"frames_u8: 4 dimensions ({'T, H, W, 3' if layout == 'thwc' else 'T, 3, H, W'}), got {tuple(frames_u8.shape)}")
+    f = frames_u8 if layout == "thwc" else frames_u8.permute(0, 2, 3, 1)
+    T, H, W, ch = f.shape
+    dev = f.device
+    if ch != 3:
+        raise ValueError(f"frames_u8: 3 channels (RGB) in layout {layout!r}, got {ch} (shape {tuple(frames_u8.shape)})")
+    if T and not (1 <= H <= 32768 and 1 <= W <= 32768):
+        raise ValueError(f"frames_u8: H, W = {H}, {W} (1 .. 32768)")
+    S_h, S_w = _crop_size(size)
+    if not isinstance(windows, torch.Tensor) or windows.device != dev:
+        raise ValueError(f"windows: a tensor on {dev} with the frames")
+    if windows.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise TypeError(f"windows: expected an integer type, got {windows.dtype}")
+    if windows.dim() != 3 or windows.shape[0] != T or windows.shape[2] not in (4, 8):
+        raise ValueError(f"windows: ({T}, M, 8) or ({T}, M, 4) to go with the frames, got {tuple(windows.shape)}")
+    M, words = windows.shape[1], windows.shape[2]
+    win = windows.to(torch.int64).contiguous()
+    if fill is None:
+        fill = (0, 0, 0)
+    fill = [int(v) for v in (fill.tolist() if hasattr(fill, "tolist") else fill)]
+    if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+        raise ValueError(f"fill={fill}: three bytes (R, G, B)")
+    if (ids is None) != (objects is None):
+        raise ValueError("ids and objects: both or neither")
+    if mask_out is not None and ids is None:
+        raise ValueError("mask_out: without ids there are no masks")
+    h = w = 0
+    obj = None
+    if ids is not None:
+        if not isinstance(ids, torch.Tensor) or ids.device != dev or ids.dtype != torch.uint8:
+            raise ValueError(f"ids: a uint8 tensor on {dev} with the frames")
+        if ids.dim() != 3 or ids.shape[0] != T:
+            raise ValueError(f"ids: ({T}, h, w) to go with the frames, got {tuple(ids.shape)}")
+        h, w = ids.shape[1:]
+        if T and not (1 <= h <= 32768 and 1 <= w <= 32768):
+            raise ValueError(f"ids: h, w = {h}, {w} (1 .. 32768)")
+        objs = [int(o) for o in objects]
+        if len(objs) != M:
+            raise ValueError(f"objects: {M} ids to go with the windows, got {len(objs)}")
+        for o in objs:
+            if not 0 <= o <= 255:
+                raise ValueError(f"objects: id {o} outside 0 .. 255 (the ids are bytes)")
+        if not _strided_rows(ids):
+            ids = ids.contiguous()
+        obj = _objects_tensor(objs, dev)
+    taps = _crop_taps(max_taps, (max(H, 1), max(W, 1)), (S_h, S_w))
+    out = _out(out, (T, M, S_h, S_w, 3), torch.uint8, dev)
+    masks = None
+    if ids is not None:
+        try:
+            masks = _out(mask_out, (T, M, S_h, S_w), torch.uint8, dev)
+        except ValueError as e:
+            raise ValueError("mask_" + str(e)) from None
+    if T == 0 or M == 0:
+        return out if masks is None else (out, masks)
+    need = int(_lib.load().fgvc_frames_object_crops_workspace_bytes(T, M, S_h, S_w, taps))
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"workspace: a contiguous uint8 tensor of at least {need} bytes on {dev} (object_crops_workspace_bytes), got "
+                         f"{workspace.dtype} of {workspace.numel()} elements on {workspace.device}")
+    st, sy, sx, sc = f.stride()
+    _lib.call("fgvc_frames_object_crops_u8", _ptr(f), T, H, W, st, sy, sx, sc, _ptr(win), words, M, S_h, S_w, *fill,
+              None if ids is None else _ptr(ids), 0 if ids is None else ids.stride(0), 0 if ids is None else ids.stride(1), h, w,
+              None if obj is None else _ptr(obj), taps, _ptr(out), None if masks is None else _ptr(masks), _ptr(workspace),
+              workspace.numel(), _stream(f))
+    return out if masks is None else (out, masks)
+
+
 # ---- render: mask overlay and point icons onto uint8 video (DESIGN.md section 16) -------------------------------------------------------
 
 RENDER_TILE = (8, 256)  # rows, columns one workgroup of fgvc_render_frames_u8 owns (= fgvc_render_tile_rows/_cols(); the tests put points on its corners)

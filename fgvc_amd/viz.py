@@ -948,3 +948,159 @@ def frames_to_yuv420(frames, fmt: str = "i420", matrix: str = "bt601", range: st
         return out if on_device else out.cpu().numpy()
     packed = datasets.pack_yuv420(*datasets.rgb8_to_yuv420(f.cpu(), matrix, range, siting), fmt)
     return packed if is_tensor else packed.numpy()
+
+
+# ---- object crops: the resampling rule --------------------------------------------------------------------------
+
+CROP_BITS = 22                 # the coefficients' fixed point: K = int(0.5 + k 2^22), sums rounded with 2^21 and shifted by 22
+CROP_MAX_SIZE = 1024           # output sides: 1 .. 1024
+CROP_MAX_TAPS = 256            # the most taps per axis the device entry keeps for one output
+CROP_LIMIT = 2 ** 30           # a window coordinate at or beyond it in magnitude: the window is not resampled
+
+
+def crop_axis_taps(span: int, n: int) -> int:
+    """The bound on the taps of one output of an axis with window length `span` and n outputs that the device entry sizes its table by:
+    2 ceil(max(span, n) / n) + 2 >= floor(c + fs + 0.5) - floor(c - fs + 0.5) for every centre c, with fs = max(span / n, 1)."""
+    return 2 * (-(-max(int(span), int(n)) // int(n))) + 2
+
+
+def crop_default_taps(frame_size, size) -> int:
+    """The default max_taps of ops.object_crops: enough for every window up to twice the frame's side on each axis, at most CROP_MAX_TAPS."""
+    (H, W), (S_h, S_w) = frame_size, size
+    return min(CROP_MAX_TAPS, max(crop_axis_taps(2 * int(H), S_h), crop_axis_taps(2 * int(W), S_w)))
+
+
+def crop_window_ok(x0: int, y0: int, x1: int, y1: int, size, max_taps: Optional[int] = None) -> bool:
+    """Whether a window is resampled: not empty (x1 > x0 and y1 > y0), every coordinate below CROP_LIMIT in magnitude and, with max_taps,
+    crop_axis_taps of both axes within it.  Any other window gives a crop of `fill` and a mask of zeros."""
+    if x1 <= x0 or y1 <= y0 or max(abs(x0), abs(y0), abs(x1), abs(y1)) >= CROP_LIMIT:
+        return False
+    return max_taps is None or (crop_axis_taps(x1 - x0, size[1]) <= max_taps and crop_axis_taps(y1 - y0, size[0]) <= max_taps)
+
+
+def crop_axis_coefficients(a0: int, a1: int, n: int):
+    """One axis of the resampling rule: the integer window [a0, a1) onto n outputs -> (lo (n,) int64, K: a list of n int64 arrays).  Output
+    j sums K[j][i] * src[lo[j] + i].  The triangle filter widened by the scale, as Pillow's BILINEAR resize with box= applies it, in
+    float64 with every operation rounded, left to right; the taps' sum runs in increasing order and the coefficients are fixed point:
+    K = int(0.5 + k 2^22).  lo is a floor, not a truncation (it can be negative), and neither end is clipped to the frame."""
+    scale = np.float64(a1 - a0) / np.float64(n)
+    fs = max(scale, np.float64(1.0))
+    inv = np.float64(1.0) / fs
+    center = np.float64(a0) + (np.arange(n, dtype=np.float64) + np.float64(0.5)) * scale
+    lo = np.floor(center - fs + np.float64(0.5)).astype(np.int64)
+    hi = np.floor(center + fs + np.float64(0.5)).astype(np.int64)
+    cnt = hi - lo
+    q = np.arange(int(cnt.max()), dtype=np.int64)[None, :]                  # all outputs at once; the loop over the taps stays sequential
+    a = np.abs(((lo[:, None] + q).astype(np.float64) - center[:, None] + np.float64(0.5)) * inv)
+    v = np.where((a < 1.0) & (q < cnt[:, None]), np.float64(1.0) - a, np.float64(0.0))
+    ww = np.zeros(n, np.float64)
+    for i in range(v.shape[1]):
+        ww = ww + v[:, i]                                                  # (past an output's last tap this adds 0.0: exact)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        k = np.where(ww[:, None] != 0.0, v / ww[:, None], v)
+    K = (np.float64(0.5) + k * np.float64(1 << CROP_BITS)).astype(np.int64)
+    return lo, [K[j, :cnt[j]] for j in range(n)]
+
+
+def _crop_axis_matrix(a0: int, a1: int, n: int):
+    """crop_axis_coefficients as a dense (n, span) int64 matrix over the source indices [base, base + span)"""
+    los, Ks = crop_axis_coefficients(a0, a1, n)
+    base = int(los.min())
+    span = max(int(lo) + len(k) for lo, k in zip(los, Ks)) - base
+    M = np.zeros((n, max(span, 1)), np.int64)
+    for j, (lo, k) in enumerate(zip(los, Ks)):
+        M[j, int(lo) - base:int(lo) - base + len(k)] = k
+    return base, M
+
+
+def _clip8_round(x: np.ndarray) -> np.ndarray:
+    return np.clip((x + (1 << (CROP_BITS - 1))) >> CROP_BITS, 0, 255)
+
+
+def crop_windows_host(frames, windows, size, fill=None, ids=None, objects=None, max_taps: Optional[int] = None):
+    """The contract of ops.object_crops (fgvc_frames_object_crops_u8), in numpy: frames (T, H, W, 3) uint8 RGB, windows (T, M, 8) int64 as
+    metrics.object_windows_host gives them (the frame-space words 4 .. 7 are resampled, the mask-space words 0 .. 3 sample the ids) or
+    (T, M, 4) integer windows (x0, y0, x1, y1) of the caller's own (both spaces equal), size = (S_h, S_w) -> crops (T, M, S_h, S_w, 3)
+    uint8; with ids (T, h, w) and objects (M ids) also masks (T, M, S_h, S_w) uint8, as a pair.
+    Per axis the coefficients are crop_axis_coefficients'; horizontal pass first, then vertical, with a uint8 intermediate:
+        tmp = clip8((2^21 + sum_i Kx_i src_i) >> 22),  out = clip8((2^21 + sum_i Ky_i tmp_i) >> 22)
+    where src outside the frame is fill[c] ((3,) uint8, default zeros): Pillow's Image.resize((S_w, S_h), BILINEAR, box=window) on a frame
+    padded with `fill`.  Masks are sampled at the nearest pixel of the mask-space window in integers: mx = wx0 + ((2 xx + 1) Wp) // (2 S_w),
+    my likewise; 255 where (my, mx) is inside the map and ids[t, my, mx] == objects[j], else 0.  A window that is not crop_window_ok(...,
+    max_taps) -- empty, beyond CROP_LIMIT or, where max_taps is given, with more taps on an axis -- gives a crop of `fill` and a mask of zeros."""
+    f = np.asarray(frames)
+    if f.ndim != 4 or f.shape[3] != 3 or f.dtype != np.uint8:
+        raise ValueError(f"frames: (T, H, W, 3) uint8, got {f.dtype} {f.shape}")
+    win = np.asarray(windows)
+    if win.ndim != 3 or win.shape[0] != f.shape[0] or win.shape[2] not in (4, 8) or win.dtype.kind not in "iu":
+        raise ValueError(f"windows: ({f.shape[0]}, M, 8) or ({f.shape[0]}, M, 4) integers, got {win.dtype} {win.shape}")
+    win = win.astype(np.int64)
+    S_h, S_w = (int(s) for s in size)
+    if not (1 <= S_h <= CROP_MAX_SIZE and 1 <= S_w <= CROP_MAX_SIZE):
+        raise ValueError(f"size={tuple(size)}: S_h and S_w in 1 .. {CROP_MAX_SIZE}")
+    fill = np.zeros(3, np.uint8) if fill is None else np.asarray(fill)
+    if fill.shape != (3,) or fill.dtype != np.uint8:
+        raise ValueError(f"fill: (3,) uint8, got {fill.dtype} {fill.shape}")
+    T, H, W, _ = f.shape
+    M = win.shape[1]
+    if (ids is None) != (objects is None):
+        raise ValueError("ids and objects: both or neither")
+    if ids is not None:
+        ids = np.asarray(ids)
+        objects = [int(o) for o in objects]
+        if ids.ndim != 3 or ids.shape[0] != T or len(objects) != M:
+            raise ValueError(f"ids: ({T}, h, w) with {M} objects, got {ids.shape} and {len(objects)} objects")
+    crops = np.empty((T, M, S_h, S_w, 3), np.uint8)
+    crops[...] = fill
+    masks = None if ids is None else np.zeros((T, M, S_h, S_w), np.uint8)
+    fw, mw = win[..., -4:], win[..., :4]
+    for t in range(T):
+        for j in range(M):
+            x0, y0, x1, y1 = fw[t, j].tolist()
+            if not crop_window_ok(x0, y0, x1, y1, (S_h, S_w), max_taps):
+                continue
+            bx, Kx = _crop_axis_matrix(x0, x1, S_w)
+            by, Ky = _crop_axis_matrix(y0, y1, S_h)
+            src = np.empty((Ky.shape[1], Kx.shape[1], 3), np.int64)
+            src[...] = fill
+            ya, yb, xa, xb = max(by, 0), min(by + Ky.shape[1], H), max(bx, 0), min(bx + Kx.shape[1], W)
+            if ya < yb and xa < xb:
+                src[ya - by:yb - by, xa - bx:xb - bx] = f[t, ya:yb, xa:xb]
+            tmp = _clip8_round(np.einsum("yxc,ox->yoc", src, Kx))
+            crops[t, j] = _clip8_round(np.einsum("py,yoc->poc", Ky, tmp)).astype(np.uint8)
+            if masks is not None:
+                wx0, wy0, wx1, wy1 = mw[t, j].tolist()
+                if wx1 <= wx0 or wy1 <= wy0 or max(abs(wx0), abs(wy0), abs(wx1), abs(wy1)) >= CROP_LIMIT:
+                    continue
+                mx = wx0 + ((2 * np.arange(S_w, dtype=np.int64) + 1) * (wx1 - wx0)) // (2 * S_w)
+                my = wy0 + ((2 * np.arange(S_h, dtype=np.int64) + 1) * (wy1 - wy0)) // (2 * S_h)
+                okx, oky = (mx >= 0) & (mx < ids.shape[2]), (my >= 0) & (my < ids.shape[1])
+                got = ids[t][np.clip(my, 0, ids.shape[1] - 1)[:, None], np.clip(mx, 0, ids.shape[2] - 1)[None, :]] == objects[j]
+                masks[t, j] = np.where(got & oky[:, None] & okx[None, :], 255, 0)
+    return crops if masks is None else (crops, masks)
+
+
+def contact_sheet(crops, valid=None, cols: Optional[int] = None) -> np.ndarray:
+    """Tiles crops (T, M, S_h, S_w, 3) uint8 into one (rows S_h, cols S_w, 3) image on the host: the T M crops in (t, j) order, row-major,
+    `cols` a row (None: M, so a row is a frame and a column an object).  valid (T, M) bools: a crop whose entry is false is left black."""
+    c = _numpy(crops)
+    if c.ndim != 5 or c.shape[4] != 3 or c.dtype != np.uint8:
+        raise ValueError(f"crops: (T, M, S_h, S_w, 3) uint8, got {c.dtype} {c.shape}")
+    T, M, S_h, S_w, _ = c.shape
+    n = T * M
+    cols = max(M, 1) if cols is None else int(cols)
+    if cols < 1:
+        raise ValueError(f"cols={cols}: at least 1")
+    if valid is not None:
+        valid = np.asarray(_numpy(valid)).astype(bool)
+        if valid.shape != (T, M):
+            raise ValueError(f"valid: {(T, M)} bools, got {valid.shape}")
+    rows = -(-n // cols)
+    sheet = np.zeros((rows * S_h, cols * S_w, 3), np.uint8)
+    flat = c.reshape(n, S_h, S_w, 3)
+    for i in range(n):
+        if valid is not None and not valid.reshape(-1)[i]:
+            continue
+        r, q = divmod(i, cols)
+        sheet[r * S_h:(r + 1) * S_h, q * S_w:(q + 1) * S_w] = flat[i]
+    return sheet

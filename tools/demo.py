@@ -4,7 +4,7 @@ mediapy: frames come and go through PIL).
 
     python tools/demo.py FRAMES_DIR --task points --query-points t x y [t x y ...] --out OUT
     python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png --out OUT
-    python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png [--boxes] [--box-labels] [--object-trails L] [--mot OUT.txt] --out OUT
+    python tools/demo.py FRAMES_DIR --task vos --first-mask MASK.png [--boxes] [--box-labels] [--object-trails L] [--mot OUT.txt] [--crops DIR] --out OUT
     python tools/demo.py --synthetic 8 240 320 --task points --query-points 0 100 80 0 200 120 --out OUT
     python tools/demo.py FRAMES_DIR --task points --chain [--chain-visibility consistency] --query-points t x y ... --out OUT
     python tools/demo.py FRAMES_DIR --task points --query-points t x y ... --trails [L] [--trail-width X] [--trail-color track|time] --out OUT
@@ -44,6 +44,10 @@ test_cfg.objects = dict(stats=True) (one launch of fgvc_seg_object_stats_u8 on t
 boxes with the overlay in one launch, and the trails are a second call, viz.paint_trails, onto that output.  --clean [--min-area N] [--keep-largest] [--fill-holes]
 [--max-hole N] cleans the propagated masks first (test_cfg.clean).  They go with --mask, --fuse,
 --edge-aware, --out-video and --host-render.
+--crops DIR [--crop-size H W] [--crop-pad X] [--crop-smooth R] [--crop-masks] (--task vos) writes every object's crop: a window that follows
+the object (metrics.object_windows_host's rule), resampled anti-aliased from the decoded uint8 frames onto H x W on the
+device (ops.object_windows + ops.object_crops: three launches for the clip), as DIR/obj%02d/frame_%05d.png with a contact sheet sheet.png per
+object, and with --out-video and even crop sides one DIR/obj%02d.y4m per object through the same encoder.
 Query points are (t, x, y) in the pixel frame of the clip; with --size h w the model runs at that size and the tracks are scaled back.
 Without --checkpoint the encoder has its seeded initial weights: the pipeline runs, the tracks mean little.
 """
@@ -304,7 +308,7 @@ def run_vos(a, frames: np.ndarray, dev) -> torch.Tensor:
 
 
 def wants_objects(a) -> bool:
-    return bool(a.boxes or a.box_labels or a.object_trails is not None or a.mot)
+    return bool(a.boxes or a.box_labels or a.object_trails is not None or a.mot or a.crops)
 
 
 def box_arguments(a, tr) -> dict:
@@ -315,6 +319,37 @@ def box_arguments(a, tr) -> dict:
     if a.box_labels:
         kw["box_labels"] = np.arange(1, N)
     return kw
+
+
+def write_crops(a, frames, ids, tr, video, dev) -> dict:
+    """--crops DIR: every object's window on every frame, resampled onto --crop-size from the decoded uint8 frames
+    (with YUV input: the bytes the renderer takes) -- ObjectTracks.crops on the device statistics, three launches for the clip, nothing
+    read back before the results -- written as DIR/obj%02d/frame_%05d.png (the frames the object is present on) and DIR/obj%02d/sheet.png
+    (viz.contact_sheet of all frames, absent ones black), with --crop-masks also mask_%05d.png, with --out-video and even crop sides
+    DIR/obj%02d.y4m through the same encoder."""
+    from PIL import Image
+    on_dev = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(frames).to(dev)
+    size = tuple(a.crop_size)
+    oc = tr.crops(on_dev, size=size, pad=a.crop_pad, smooth=a.crop_smooth, masks=a.crop_masks, ids=ids if a.crop_masks else None,
+                  mask_size=tuple(ids.shape[1:]))
+    crops, valid = oc.crops.cpu().numpy(), oc.valid
+    masks = oc.masks.cpu().numpy() if a.crop_masks else None
+    T = crops.shape[0]
+    cols = max(1, min(T, 10))
+    for j, o in enumerate(oc.objects):
+        d = os.path.join(a.crops, f"obj{o:02d}")
+        os.makedirs(d, exist_ok=True)
+        for t in range(T):
+            if valid[t, j]:
+                Image.fromarray(crops[t, j]).save(os.path.join(d, f"frame_{t:05d}.png"))
+                if masks is not None:
+                    Image.fromarray(masks[t, j]).save(os.path.join(d, f"mask_{t:05d}.png"))
+        Image.fromarray(viz.contact_sheet(crops[:, j:j + 1], valid[:, j:j + 1], cols=cols)).save(os.path.join(d, "sheet.png"))
+        if video and size[0] % 2 == 0 and size[1] % 2 == 0:
+            write_video(os.path.join(a.crops, f"obj{o:02d}.y4m"), oc.crops[:, j].contiguous(), video, dev, host=a.host_render)
+    print(f"{a.crops}: {int(valid.sum())} crops of {size[0]} x {size[1]} for {len(oc.objects)} object(s) as obj%02d/frame_%05d.png and sheet.png"
+          f"{', masks' if a.crop_masks else ''} (pad {a.crop_pad}, smooth {a.crop_smooth})")
+    return dict(crops=crops, crop_masks=masks, crop_windows=oc.windows.cpu().numpy(), crop_valid=valid)
 
 
 def paint_object_trails(a, rendered, tr, backend):
@@ -437,6 +472,11 @@ def parse_args(argv=None):
     ap.add_argument("--box-labels", action="store_true", help="--task vos: the boxes with the object's id on a tag (implies --boxes)")
     ap.add_argument("--object-trails", type=int, default=None, metavar="L", help="--task vos: the last L steps (1 .. 64) of every object's centroid")
     ap.add_argument("--mot", default=None, metavar="OUT.txt", help="--task vos: write the boxes as a MOTChallenge text file")
+    ap.add_argument("--crops", default=None, metavar="DIR", help="--task vos: write every object's crop per frame and a contact sheet (test_cfg.objects)")
+    ap.add_argument("--crop-size", type=int, nargs=2, default=(128, 128), metavar=("H", "W"), help="with --crops: the crops' size")
+    ap.add_argument("--crop-pad", type=float, default=0.125, metavar="X", help="with --crops: the box grows by this share of its side, 0 .. 4")
+    ap.add_argument("--crop-smooth", type=int, default=0, metavar="R", help="with --crops: average the window over R frames on each side")
+    ap.add_argument("--crop-masks", action="store_true", help="with --crops: also every object's mask in its window")
     ap.add_argument("--clean", action="store_true",
                     help="--task vos: clean the propagated masks on the device before anything reads them (test_cfg.clean, ops.seg_clean)")
     ap.add_argument("--min-area", type=int, default=0, metavar="N", help="with --clean: drop connected parts of an object below N pixels")
@@ -488,6 +528,8 @@ def parse_args(argv=None):
         ap.error("--boxes, --box-labels, --object-trails and --mot go with --task vos")
     if (a.clean or a.min_area or a.keep_largest or a.fill_holes or a.max_hole is not None) and not (a.task == "vos" and a.clean):
         ap.error("--clean goes with --task vos; --min-area, --keep-largest, --fill-holes and --max-hole go with --clean")
+    if (a.crops or tuple(a.crop_size) != (128, 128) or a.crop_pad != 0.125 or a.crop_smooth or a.crop_masks) and not (a.task == "vos" and a.crops):
+        ap.error("--crops goes with --task vos; --crop-size, --crop-pad, --crop-smooth and --crop-masks go with --crops")
     if a.object_trails is not None and not 1 <= a.object_trails <= 64:
         ap.error("--object-trails L: 1 .. 64")
     if a.yuv_matrix and not (a.frames or "").lower().endswith(".y4m"):
@@ -568,6 +610,8 @@ def main(argv=None):
     r = dict(frames=frames, tracks=tracks, visibles=visibles, query_points=points, ids=None if ids is None else ids.cpu().numpy(), rendered=rendered)
     if objects is not None:
         r["objects"] = objects
+    if objects is not None and a.crops:
+        r.update(write_crops(a, frames, ids, objects, video, dev))
     if getattr(a, "cleaned", None) is not None:
         r["clean"] = a.cleaned
         if a.cleaned["stats"] is not None:
